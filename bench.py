@@ -13,6 +13,8 @@ collective is the RCCL broadcast of the 32-byte colour-coefficient block.
   python bench.py --gpus N             # spawns N ranks itself (one per GPU, RCCL), rank 0 prints the line
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W     # the same under torchrun
+  python bench.py --dump-outputs DIR   # also write the last timed step's outputs to DIR/*.npy (seeded inputs:
+                                       # two builds compare output for output)
 
 Prints ONE JSON line on rank 0 (contract in the task brief): value = whole-job frames/s,
 `roofline` = algorithmic bytes / HIP-event kernel time vs the 8 TB/s HBM peak,
@@ -37,6 +39,8 @@ sys.path.insert(0, str(ROOT))
 
 HBM_PEAK_GBPS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec
 HBM_COPY_CEILING_GBPS = 6290.0  # measured float4 copy ceiling (same guide)
+DUMP_BYTES = 48 << 20           # --dump-outputs: all the files of one job together (every rank's share included)
+DUMP_SEED = 8191                # --dump-outputs: the sampled positions, the same in every run and every build
 
 
 def parse():
@@ -70,7 +74,14 @@ def parse():
                     help="the long form of the line (every note, the full roofline object of every secondary entry, ~18 KB: what "
                          "profiles/rNN_bench_line.json keeps).  The default line is the SAME measurements in < 7 500 characters, "
                          "weakest kernels last, so that a reader who keeps only the tail of the line sees every entry (VERDICT r05)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed -- every rank's destination surfaces as a "
+                         "caller receives them -- to DIR/*.npy as float32 (sampled positions: float64; see dump_outputs): "
+                         f"all of it when it fits {DUMP_BYTES >> 20} MiB, otherwise the same seeded sample of positions in every frame")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def synth_nv12(width, height, seed):
@@ -259,6 +270,33 @@ def preflight_memory(shim, dev, need_bytes, what):
         raise SystemExit(f"bench.py: {what} needs {need_bytes / 2**30:.1f} GiB on GPU {dev}, {free_b / 2**30:.1f} GiB of "
                          f"{total_b / 2**30:.1f} GiB are free -- lower --frames")
     return free_b, total_b
+
+
+def dump_outputs(dsts, out_dir, rank, world):
+    """What the last timed step left in this rank's destination surfaces, i.e. the tensors a caller of the path receives
+    (torch.from_dlpack of each surface: pitch padding excluded), as float32 .npy files in `out_dir`.  When the rank's share
+    of DUMP_BYTES holds every element: <name>.npy of shape (frames, *frame shape).  Otherwise <name>.npy of shape
+    (frames, k): the same k positions of every frame (the first and the last element and a DUMP_SEED-seeded sample), and
+    <name>_index.npy (float64): those positions as flat indices into one frame.  <name> is "dst", "dst_rank<r>" for N > 1."""
+    import torch
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    name = "dst" if world == 1 else f"dst_rank{rank}"
+    frames = [torch.from_dlpack(d) for d in dsts]
+    shape = tuple(frames[0].shape)
+    n = int(np.prod(shape))
+    budget = DUMP_BYTES // world
+    if len(frames) * n * 4 <= budget:
+        np.save(out_dir / f"{name}.npy", torch.stack(frames).float().cpu().numpy())
+        return {name: [len(frames), *shape]}
+    k = max(2, min(n, budget // (4 * len(frames) + 8)))
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.unique(np.concatenate([[0, n - 1], rng.choice(n, k - 2, replace=False)]))
+    pos = tuple(torch.as_tensor(a, device=frames[0].device) for a in np.unravel_index(idx, shape))
+    np.save(out_dir / f"{name}.npy", torch.stack([f[pos] for f in frames]).float().cpu().numpy())
+    np.save(out_dir / f"{name}_index.npy", idx.astype(np.float64))
+    return {name: [len(frames), len(idx)], f"{name}_index": [len(idx)]}
 
 
 def host_fed_rate(vali, pipe_args, coeffs_ctx, seconds, W, H):
@@ -490,6 +528,8 @@ def main():
     for a, b in ev:
         shim.event_destroy(dev, a)
         shim.event_destroy(dev, b)
+    # the outputs of the last timed step, before anything else runs on the surfaces (fence() synchronised the device)
+    dumped = dump_outputs(pipe.dsts, args.dump_outputs, rank, world) if args.dump_outputs else None
 
     per_rank_kernel_ms, ranks_seen = [float(np.mean(kernel_ms))], 1
     if dist is not None:
@@ -595,6 +635,8 @@ def main():
             out["parity_vs_oracle"] = parity
         if verification is not None:
             out["verification"] = verification
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays_of_rank0": dumped}
         out["host_placement"] = {"numa_bound_cpus": (f"{numa_cpus[0]}-{numa_cpus[-1]} ({len(numa_cpus)} CPUs)" if numa_cpus else None),
                                  "pci_bus_id": shim.device_pci_bus_id(dev), "gpu_state": clocks}
         if world == 1 and args.ingest_seconds > 0:

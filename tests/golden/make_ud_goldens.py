@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Crop the reference's own UD golden files (tests/data/640x360_*.raw, produced by
 reference tests/test_PySurfaceUD.py from frame 0 of test.mp4 / test_hevc10.mkv) to their
-first ROWS rows and store them compressed.  Run in the build container only
-(/root/reference is not on the GPU box).  These are DATA fixtures of the reference's
+first ROWS rows and store them compressed.  Run where the reference's tests/data is:
+  python tests/golden/make_ud_goldens.py /path/to/reference/tests/data
+These are DATA fixtures of the reference's
 test-suite; the source frame they were computed from needs a video decoder and is not
 reproducible offline, so the tests use them through pixel-wise identities."""
 import sys
@@ -10,7 +11,9 @@ from pathlib import Path
 
 import numpy as np
 
-REF = Path("/root/reference/tests/data")
+if len(sys.argv) < 2:
+    raise SystemExit("usage: make_ud_goldens.py /path/to/reference/tests/data")
+REF = Path(sys.argv[1])
 OUT = Path(__file__).resolve().parent
 W, H, ROWS = 640, 360, 120
 

@@ -215,14 +215,10 @@ def test_log_level_and_probe_validate_their_arguments(vali, tmp_path):
 
 
 def test_real_pyav_decodes_the_reference_video_when_installed(vali):
-    """With a real PyAV and the reference's data next to it (never the case in the build container): frame 0 of
-    test.mp4, resized 2:1, is the committed fixture test_small.nv12."""
+    """With a real PyAV: frame 0 of the reference's test.mp4 (committed as tests/golden/test.mp4), resized 2:1, is the
+    committed fixture test_small.nv12."""
     av = pytest.importorskip("av")  # noqa: F841
-    import os
-    path = os.environ.get("VALI_REFERENCE_VIDEO", "/root/reference/tests/data/test.mp4")
-    if not os.path.exists(path):
-        pytest.skip("reference video not present")
-    dec = vali.PyDecoder(path, {}, gpu_id=-1)
+    dec = vali.PyDecoder(str(GOLDEN / "test.mp4"), {}, gpu_id=-1)
     assert (dec.Width, dec.Height, dec.Format) == (848, 464, vali.YUV420)
     frame = np.ndarray(shape=(0,), dtype=np.uint8)
     assert dec.DecodeSingleFrame(frame)[0]

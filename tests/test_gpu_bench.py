@@ -157,26 +157,90 @@ def test_bench_gpus_flag_spawns_the_ranks_itself(gpu):
     assert j["verification"]["frames_mismatching"] == 0 and "cpu_baseline" not in j
 
 
-def test_bench_eight_ranks_functional_on_one_gpu(gpu):
-    """BASELINE configs[4]'s shape (8 ranks, contiguous frame shards, one coefficient broadcast, checksum all-reduce)
-    without 8 GPUs: `bench.py --gpus 8` starts its eight ranks itself, they share this box's GPU and the collectives run
-    over gloo.  Functional proof only -- no scaling curve has been measured on hardware."""
+def _self_spawned_ranks_64_frames(n):
+    """`bench.py --gpus n` starts its n ranks itself over a global batch of 64 1080p frames, collectives over gloo (ranks
+    share a GPU when the node has fewer than n): contiguous frame shards, one coefficient broadcast, checksum all-reduce."""
+    per = 64 // n
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["VALI_BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "8", "--frames", "8", "--width", "1920",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", str(n), "--frames", str(per), "--width", "1920",
                         "--height", "1080", "--steps", "2", "--warmup", "1", "--ramp-ms", "0"],
                        capture_output=True, text=True, timeout=1200, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     j = last_json(r.stdout)
-    assert j["n_gpus"] == 8 and j["ranks_seen"] == 8 and j["launcher"] == "self-spawned"
-    assert j["config"]["global_batch"] == 64 and j["config"]["frames_per_gpu"] == 8
-    assert len(j["per_rank_kernel_ms"]) == 8 and all(v > 0 for v in j["per_rank_kernel_ms"])
+    assert j["n_gpus"] == n and j["ranks_seen"] == n and j["launcher"] == "self-spawned"
+    assert j["config"]["global_batch"] == 64 and j["config"]["frames_per_gpu"] == per
+    assert len(j["per_rank_kernel_ms"]) == n and all(v > 0 for v in j["per_rank_kernel_ms"])
     assert j["verification"] == {"frames_verified_on_gpu": 64, "frames_mismatching": 0,
                                  "checksum_of_checksums": j["verification"]["checksum_of_checksums"]}
     assert j["parity_vs_oracle"]["max_abs_diff_lsb"] == 0
     # the shards: contiguous, disjoint, in rank order, covering the global batch exactly
-    assert j["rank_shards"] == [[8 * r_, 8 * r_ + 8] for r_ in range(8)]
+    assert j["rank_shards"] == [[per * r_, per * r_ + per] for r_ in range(n)]
     assert "cpu_baseline" not in j and "secondary" not in j
+    return j
+
+
+def test_bench_eight_ranks_functional_on_one_gpu(gpu, vali):
+    """BASELINE configs[4]'s shape (8 ranks, 8 frames each).  Each rank holds a device open: eight of them on one GPU, plus
+    the test process, are more processes on a device than a shared node allows, so this runs on a node with 8 GPUs (one
+    rank each).  Functional proof only -- no scaling curve has been measured on hardware."""
+    n = vali.GetNumGpus()
+    if n < 8:
+        pytest.skip(f"needs 8 GPUs (one per rank), found {n}")
+    j = _self_spawned_ranks_64_frames(8)
+    assert j["rank_devices"] == list(range(8))
+
+
+def test_bench_four_ranks_share_one_gpu(gpu):
+    """The same global batch as BASELINE configs[4] (64 frames) over four ranks that share this node's GPU: the
+    self-spawned N>2 path (sharding, broadcast, checksum all-reduce, per-rank report) on a one-GPU node."""
+    _self_spawned_ranks_64_frames(4)
+
+
+def test_bench_dump_outputs_are_the_last_timed_steps_outputs(gpu, oracle, tmp_path):
+    """--dump-outputs DIR: the destination surfaces of the last timed step as float32 .npy -- the whole batch when it is small
+    (equal to the oracle's conversion of the seeded inputs), otherwise the same seeded positions of every frame, equal from
+    run to run, all files under 64 MB."""
+    import importlib.util
+
+    import numpy as np
+
+    from vali_amd import tasks
+
+    def run(frames, w, h, out):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--frames", str(frames), "--width", str(w), "--height", str(h),
+                            "--steps", "3", "--warmup", "1", "--ramp-ms", "0", "--cpu-seconds", "0", "--ingest-seconds", "0",
+                            "--no-secondary", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = last_json(r.stdout)
+        assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["dump_outputs"]["dir"] == str(out)
+        assert sum(p.stat().st_size for p in out.iterdir()) < 64e6
+        return j["dump_outputs"]["arrays_of_rank0"]
+
+    spec = importlib.util.spec_from_file_location("_bench", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    k = oracle.csc_from_tuple(tasks.CSC_NPP_709CSC)
+
+    assert run(4, 640, 360, tmp_path / "small") == {"dst": [4, 360, 640, 3]}
+    got = np.load(tmp_path / "small" / "dst.npy")
+    assert got.dtype == np.float32
+    for i in range(4):
+        want = oracle.nv12_to_rgb(bench.synth_nv12(640, 360, i), 640, 360, k, "RGB").reshape(360, 640, 3)
+        assert np.array_equal(got[i], want.astype(np.float32)), i
+
+    a = run(16, 1920, 1080, tmp_path / "big1")
+    assert a == run(16, 1920, 1080, tmp_path / "big2")
+    n = a["dst_index"][0]
+    assert a["dst"] == [16, n] and n > 100000
+    d1, d2 = np.load(tmp_path / "big1" / "dst.npy"), np.load(tmp_path / "big2" / "dst.npy")
+    idx = np.load(tmp_path / "big1" / "dst_index.npy")
+    assert d1.dtype == np.float32 and np.array_equal(d1, d2)
+    assert np.array_equal(idx, np.load(tmp_path / "big2" / "dst_index.npy"))
+    assert idx[0] == 0 and idx[-1] == 1080 * 1920 * 3 - 1
+    for i in (0, 15):                # frame 15 was filled from seed frame 15 % 8
+        want = oracle.nv12_to_rgb(bench.synth_nv12(1920, 1080, i % 8), 1920, 1080, k, "RGB").reshape(-1)
+        assert np.array_equal(d1[i], want[idx.astype(np.int64)].astype(np.float32)), i
 
 
 def test_bench_line_carries_the_gpu_state(gpu):

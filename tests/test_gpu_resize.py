@@ -318,6 +318,19 @@ def test_columns_first_batch_and_rows_per_wave(vali, gpu, oracle, rows_mode):
     assert np.array_equal(np.isnan(got), nan) and np.array_equal(got[~nan].view(np.uint32), want[~nan].view(np.uint32))
 
 
+def plane_geometry(fmt, *dims, min_w=0):
+    """A geometry listed for one plane, as the geometry of a whole `fmt` surface (sw, sh[, dw, dh]).  A 4:2:0 surface has
+    even sizes: when a listed size is odd (or the source width is below `min_w`), every size is doubled, so that the
+    chroma planes take exactly the listed geometry and the luma plane twice it.  A 4:2:2 surface has even widths: odd
+    widths are doubled the same way."""
+    dims = list(dims)
+    if fmt in ("NV12", "YUV420", "P10") and (any(d & 1 for d in dims) or dims[0] < min_w):
+        dims = [2 * d for d in dims]
+    elif fmt == "YUV422" and any(d & 1 for d in dims[0::2]):
+        dims[0::2] = [2 * d for d in dims[0::2]]
+    return dims
+
+
 # ---- one-channel planes exactly doubled both ways (vali_amd/csrc/resize_up2.hip) -------------------------------------
 # (source size): widths that are / are not multiples of 4 per plane (the second kind keeps the general kernel), one wave per
 # row and several, 1 .. 3 rows (every tap clamped), heights around the rows-per-wave forms
@@ -328,9 +341,7 @@ UP2_SIZES = [(8, 2), (16, 6), (248, 20), (256, 64), (500, 37), (1000, 130), (960
 @pytest.mark.parametrize("size", UP2_SIZES)
 @pytest.mark.parametrize("interp", ["lanczos", "cubic"])
 def test_doubled_planes_bit_exact(vali, gpu, oracle, fmt, size, interp):
-    sw, sh = size
-    if fmt in ("YUV420", "NV12", "P10") and (sw | sh) & 1:
-        pytest.skip("4:2:0 needs even sizes")
+    sw, sh = plane_geometry(fmt, *size)
     dt = DT.get(fmt, np.uint8)
     n = vali.Surface.Make(vali.PixelFormat[fmt], sw, sh, gpu).HostSize // np.dtype(dt).itemsize
     rng = np.random.default_rng(sw * 13 + sh)
@@ -468,11 +479,7 @@ ROWS_GEOMS = [(1280, 720, 1920, 1080), (640, 360, 854, 480), (100, 40, 250, 90),
 @pytest.mark.parametrize("geom", ROWS_GEOMS)
 @pytest.mark.parametrize("interp", ["lanczos", "cubic"])
 def test_growing_planes_bit_exact(vali, gpu, oracle, fmt, geom, interp):
-    sw, sh, dw, dh = geom
-    if fmt in ("NV12", "YUV420", "P10") and ((sw | sh | dw | dh) & 1):
-        pytest.skip("4:2:0 surfaces have even sizes")
-    if fmt == "YUV422" and ((sw | dw) & 1):
-        pytest.skip("4:2:2 surfaces have even widths")
+    sw, sh, dw, dh = plane_geometry(fmt, *geom)
     dt = DT.get(fmt, np.uint8)
     n = vali.Surface.Make(vali.PixelFormat[fmt], sw, sh, gpu).HostSize // np.dtype(dt).itemsize
     rng = np.random.default_rng(sw * 7 + dh)
@@ -499,9 +506,7 @@ X23_GEOMS = [(4, 2, 6, 3), (6, 4, 9, 6), (8, 6, 12, 9), (254, 34, 381, 51), (256
 @pytest.mark.parametrize("geom", X23_GEOMS)
 @pytest.mark.parametrize("interp", ["lanczos", "cubic"])
 def test_three_to_two_enlargement_bit_exact(vali, gpu, oracle, fmt, geom, interp):
-    sw, sh, dw, dh = geom
-    if fmt in ("NV12", "YUV420", "P10") and ((sw | sh | dw | dh) & 1 or sw < 8):
-        pytest.skip("4:2:0 surfaces have even sizes (and the chroma planes need 4 source pixels for this form)")
+    sw, sh, dw, dh = plane_geometry(fmt, *geom, min_w=8)    # (this form needs 4 source pixels in the chroma planes)
     dt = DT.get(fmt, np.uint8)
     n = vali.Surface.Make(vali.PixelFormat[fmt], sw, sh, gpu).HostSize // np.dtype(dt).itemsize
     rng = np.random.default_rng(sw * 3 + dh)

@@ -24,7 +24,9 @@ def main():
         import av
     except ImportError:
         raise SystemExit("PyAV (`import av`) is not installed on this box")
-    src = Path(sys.argv[1] if len(sys.argv) > 1 else "/root/reference/tests/data")
+    if len(sys.argv) < 2:
+        raise SystemExit("usage: make_reference_fixtures.py /path/to/reference/tests/data [out_dir]")
+    src = Path(sys.argv[1])
     out = Path(sys.argv[2] if len(sys.argv) > 2 else ".")
     out.mkdir(parents=True, exist_ok=True)
     container = av.open(str(src / "test.mp4"))

@@ -2,7 +2,7 @@
 # usage: tools/prof_pmc.sh TAG "<command>" : kernel stats + several PMC passes (each its own run), csv under gpurun_out/prof_TAG
 set -u
 TAG=$1; CMD=$2
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)   # the checkout this script belongs to
 OUT=$REPO/gpurun_out/prof_$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- $CMD > $OUT/trace.log 2>&1

@@ -5,7 +5,7 @@
 # (32 / 64 / 128-byte fabric requests), partial-line writes, write-request stalls, tag stalls, L2 hit rates.
 set -u
 TAG=$1; CMD=$2
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)   # the checkout this script belongs to
 OUT=$REPO/gpurun_out/tcc_$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 i=0

@@ -5,7 +5,7 @@
 #   usage: tools/profile.sh TAG [bench args...]
 set -u
 TAG=${1:-r01}; shift || true
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)   # the checkout this script belongs to
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

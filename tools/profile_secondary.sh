@@ -5,7 +5,7 @@
 #   usage: tools/profile_secondary.sh TAG
 set -u
 TAG=${1:-r01s}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)   # the checkout this script belongs to
 cd /tmp && export TMPDIR=/tmp
 for CFG in cfg3 cfg4 preproc; do
   OUT=$REPO/gpurun_out/prof_$TAG/$CFG
