@@ -377,17 +377,19 @@ VALI_API int vali_rotate_coeffs(double angle_deg, float* c, float* s);
 
 /* ---- tuning switches and tracing -------------------------------------------------------------
  *
- * Every alternative kernel form the library keeps for A/B measurements and for path-coverage tests is
- * selected through this ONE table (no getenv anywhere else in the library).  A switch never changes a
- * result -- every form is bit-identical (tests/test_gpu_tuning.py runs each operator under every value) --
- * only which kernel produces it.  Values are process-wide and may be changed at any time between calls.
+ * Every alternative kernel form the library keeps for path-coverage tests and measurements is selected
+ * through this ONE table (no getenv anywhere else in the library).  Forms that only a switch could reach are
+ * retired: their keys keep their numbers and are accepted without effect, and a retired value of a live key
+ * selects the default form.  A switch never changes a result -- every form is bit-identical
+ * (tests/test_gpu_tuning.py runs each operator under every value) -- only which kernel produces it.  Values are process-wide and may be changed at any time between calls.
  * Initial values: the default below, or the environment variable of the same name (VALI_<KEY>) read once,
  * when the library is first used.
  */
 enum vali_tuning_key {
   VALI_TUNE_NV12_ROWPAIRS = 0,        /* row pairs stacked in one workgroup of the streaming converters; 0 = auto */
   VALI_TUNE_WAVES_PER_CU = 1,         /* residency cap of the streaming converters; 0 = auto                      */
-  VALI_TUNE_NV12_DIRECT_STORE = 2,    /* 1: NV12->RGB stores 48 B per lane instead of going through the LDS strip */
+  VALI_TUNE_NV12_DIRECT_STORE = 2,    /* no effect (retired: selected per-lane 48 B stores of NV12->RGB instead of the LDS
+                                         strip, measured slower); the key keeps its number                         */
   VALI_TUNE_RESIZE_FORCE_GATHER = 3,  /* 1: every resize geometry through the direct-gather form                  */
   VALI_TUNE_RESIZE_POINT = 4,         /* 0: arithmetic form at integer scale factors; 2: staged point form only (default 1) */
   VALI_TUNE_UD_FORCE_GATHER = 5,      /* 1: every UD geometry through the direct-gather form, no exact-ratio kernels */
@@ -395,8 +397,8 @@ enum vali_tuning_key {
                                          exact-ratio kernels for output widths that are multiples of 8; 2: for all */
   VALI_TUNE_UD_OCC5 = 7,              /* no effect since round 2 (selected a 96-register instantiation of the staged UD
                                          kernel, removed: it spilled); the key keeps its number                       */
-  VALI_TUNE_ROTATE_NO_TILE = 8,       /* 1: quarter / half turns through the bilinear kernel; 2: column-major tile walk;
-                                         3: fused UD + quarter turn on 128-row tiles (default 64)                  */
+  VALI_TUNE_ROTATE_NO_TILE = 8,       /* 1: quarter / half turns through the bilinear kernel (retired values: 2, a
+                                         column-major tile walk, and 3, fused UD + quarter turn on 128-row tiles)    */
   VALI_TUNE_ROCTX = 9,                /* 1: a roctx range around every operator entry point (see below)            */
   VALI_TUNE_RESIZE_NO_SEPARABLE = 10, /* Lanczos / bicubic rows per wave: 0 by launch size, 1: few, 2: fewest (and the slot walk
                                          where the 3:2-both-ways form has a static one), 3: most (growing planes: 32-row waves), 4: growing planes on
@@ -411,12 +413,13 @@ enum vali_tuning_key {
                                          that grow along x too: row pass from registers, no LDS stage); 0: round 2's LDS-ring kernel  */
   VALI_TUNE_RESIZE_COLS = 14,         /* Lanczos / bicubic of planes that shrink, general ratios: 0 (default) a workgroup = one wave that
                                          walks the source rows + one that runs the pass along the rows (round 5), taps from per-geometry
-                                         tables (tap_table.hip); 2: the same, taps computed in the kernel; 1: both passes in every wave
-                                         (round 4's form)                                                             */
+                                         tables (tap_table.hip); 2: the same, taps computed in the kernel (retired value: 1, both
+                                         passes in every wave, round 4's form)                                        */
   VALI_TUNE_ROTATE_AFFINE = 15,       /* rotation by an angle that is no canonical quarter / half turn: 0 (default) a workgroup stages the source
                                          box of its destination tile in LDS (round 6), tile shape by launch size; 1: per-pixel gathers from global
-                                         memory (round 2's form, also taken for planes narrower than a staged row); tile shapes: 2 = 32 x 64,
-                                         3 = 64 x 32, 4 = 64 x 64, 5 = 64 x 128 (one-channel 8-bit planes), 6 = 32 x 32   */
+                                         memory (round 2's form, also taken for planes narrower than a staged row); tile shapes:
+                                         3 = 64 x 32, 4 = 64 x 64, 5 = 64 x 128 (one-channel 8-bit planes), 6 = 32 x 32 (retired value:
+                                         2, 32 x 64)                                                                  */
   VALI_TUNE_TAP_MAX_TABLES = 16,      /* tap tables (Lanczos / bicubic axes) kept per device before the least recently used is evicted; default 1024, at least 8
                                          (they share one 32 MiB arena per device, reserved by the first Lanczos / bicubic call on it)        */
   VALI_TUNE_TAP_FALLBACKS = 17,       /* COUNTER (read with vali_tuning_get, reset by setting 0): resize calls that got no tap table outside a

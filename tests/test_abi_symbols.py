@@ -74,3 +74,19 @@ def test_tuning_table_round_trip_without_a_gpu():
     import pytest
     with pytest.raises(KeyError):
         vali_amd.tuning.Get("NO_SUCH_SWITCH")
+
+
+def test_tuning_table_accepts_retired_keys_and_values():
+    """Retired forms keep the ABI: the two reserved keys and the retired values of live keys are still accepted
+    (they select the default form; include/vali_hip.h)."""
+    from vali_amd._native import shim
+
+    retired = [(shim.TUNE_NV12_DIRECT_STORE, 1), (shim.TUNE_UD_OCC5, 1), (shim.TUNE_RESIZE_COLS, 1),
+               (shim.TUNE_ROTATE_NO_TILE, 2), (shim.TUNE_ROTATE_NO_TILE, 3), (shim.TUNE_ROTATE_AFFINE, 2)]
+    for key, value in retired:
+        old = shim.tuning_get(key)
+        try:
+            assert shim.tuning_set(key, value) == 0, (key, value)
+            assert shim.tuning_get(key) == value, (key, value)
+        finally:
+            assert shim.tuning_set(key, old) == 0

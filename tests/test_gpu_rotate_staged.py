@@ -11,7 +11,7 @@ pytestmark = pytest.mark.gpu
 
 FORMATS = {"RGB": (np.uint8, 3), "BGR": (np.uint8, 3), "Y": (np.uint8, 1), "YUV444": (np.uint8, 1), "YUV420": (np.uint8, 1),
            "YUV444_10bit": (np.uint16, 1), "RGB_32F": (np.float32, 3)}
-FORMS = (0, 2, 3, 4, 5, 6, 1)      # 1 = the gather form (round 2), the others stage in LDS (5: 64 x 128 tiles, one-channel 8-bit planes)
+FORMS = (0, 3, 4, 5, 6, 1)      # 1 = the gather form (round 2), the others stage in LDS (5: 64 x 128 tiles, one-channel 8-bit planes)
 
 
 def _run(vali, gpu, oracle, fmt, sw, sh, dw, dh, angle, sx, sy, forms=FORMS, seed=0, batch=1):

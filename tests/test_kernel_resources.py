@@ -58,11 +58,8 @@ def test_the_hot_kernels_spill_nothing_and_keep_their_occupancy():
     """the kernels the bench lines are quoted on: no spilled SGPR, and the waves per SIMD their design counts on"""
     k = kernels()
     want = {"k_nv12_rgb8": 8, "k_ud_half": 8, "k_ud_half_t": 4, "k_resize_cols_x2IhLi12ELi6ELi3E": 5,
-            # the general columns-first form: 3 slots at 1.98:1, 4 at 4:3 / 5:4 -- NV12, packed RGB, P10: the fourth wave per SIMD
-            "k_resize_colsIhLi12ELi6ELi3E": 4, "k_resize_colsIhLi12ELi6ELi4E": 4, "k_resize_colsIhLi3ELi6ELi3E": 4,
-            "k_resize_colsIhLi3ELi6ELi4E": 4, "k_resize_colsItLi12ELi6ELi3E": 4,
-            # ... on specialised waves (round 5; the last figure is the consumer's sets): six waves per SIMD at 3 slots,
-            # five with wide tiles or 4 slots
+            # the general columns-first form on specialised waves (3 slots at 1.98:1, 4 at 4:3 / 5:4; the last figure is the
+            # consumer's sets): six waves per SIMD at 3 slots, five with wide tiles or 4 slots
             "k_resize_cols_wsIhLi12ELi6ELi3ELi4E": 6, "k_resize_cols_wsIhLi12ELi6ELi3ELi5E": 5, "k_resize_cols_wsIhLi12ELi6ELi4ELi5E": 5,
             "k_resize_cols_wsIhLi3ELi6ELi4ELi5E": 5, "k_resize_cols_wsIhLi3ELi6ELi3ELi4E": 6,
             "k_resize_up2IhLi6ELb0E": 6, "k_resize_up2IhLi6ELb1E": 6, "k_resize_up2ItLi6ELb0E": 6,   # (the workgroups-per-CU figures of launch_resize_up2)

@@ -4,8 +4,8 @@ variant run for ~`seconds` of steady load with the chip's state (sysfs: sclk, mc
 Prints one JSON line per variant: {"variant", "us_per_frame", "frac", "sclk_mhz": [min, max], "power_w": [min, max], ...}.
 
   python tools/power_ab.py [frames=256] [seconds=1.0]
-Variants: the library's default (packed RGB through the LDS strip), the direct-store form (no strip), planar RGB (no strip, three
-row stores), residency caps of 16 / 24 / 32 waves per CU, and BGR -- interleaved twice so that drift of the box shows."""
+Variants: the library's default (packed RGB through the LDS strip), planar RGB (no strip, three row stores), residency caps
+of 16 / 24 / 32 waves per CU, and BGR -- interleaved twice so that drift of the box shows."""
 import json
 import sys
 import time
@@ -22,8 +22,7 @@ seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 1.0
 W, H = 3840, 2160
 bus = shim.device_pci_bus_id(DEV)
 cc = vali.ColorspaceConversionContext(vali.ColorSpace.BT_709, vali.ColorRange.MPEG)
-VARIANTS = [("default RGB (LDS strip)", vali.RGB, {}), ("RGB direct store (no strip)", vali.RGB, {"NV12_DIRECT_STORE": 1}),
-            ("RGB_PLANAR (no strip)", vali.RGB_PLANAR, {}), ("RGB, 16 waves per CU", vali.RGB, {"WAVES_PER_CU": 16}),
+VARIANTS = [("default RGB (LDS strip)", vali.RGB, {}), ("RGB_PLANAR (no strip)", vali.RGB_PLANAR, {}), ("RGB, 16 waves per CU", vali.RGB, {"WAVES_PER_CU": 16}),
             ("RGB, 24 waves per CU", vali.RGB, {"WAVES_PER_CU": 24}), ("RGB, 32 waves per CU", vali.RGB, {"WAVES_PER_CU": 32}),
             ("BGR (LDS strip)", vali.BGR, {})]
 pipes = {}

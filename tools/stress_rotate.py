@@ -33,7 +33,7 @@ while time.time() - t0 < budget:
     if even: w, h = max(2, w // 2 * 2), max(2, h // 2 * 2)
     n90 = (int(round(angle)) + 360) % 360 if quarter else 0
     dw, dh = (h, w) if n90 in (90, 270) else (w, h)
-    vali.tuning.Set("ROTATE_NO_TILE", int(rng.integers(3)) if quarter else 0)
+    vali.tuning.Set("ROTATE_NO_TILE", int(rng.integers(2)) if quarter else 0)
     pf = vali.PixelFormat[name]
     src = vali.Surface.Make(pf, w, h, DEV)
     nel = src.HostSize // np.dtype(dt).itemsize

@@ -12,7 +12,8 @@
 // One 256-thread workgroup = one row pair x 4096 px.  grid.x walks the tiles of a
 // frame through the XCD-contiguous TileMap (dev_util.hpp), grid.y = frame.
 // Packed stores go through a per-wave LDS strip so each store instruction writes
-// 1 KiB contiguous, non-temporal.  Residency is capped at 16 waves per CU by the
+// 1 KiB contiguous, non-temporal (+9.5 % over each lane storing its own 48 B,
+// DESIGN.md section 3).  Residency is capped at 16 waves per CU by the
 // dynamic-LDS size: fewer concurrent row streams per L2 measured +4% HBM
 // throughput at 2160p (profiles/r01_variants.md: 5.56 -> 6.16 TB/s in total).
 // Arithmetic (bit-exact with oracle/vali_oracle.c: vali_oracle_nv12_to_rgb):
@@ -91,10 +92,8 @@ __device__ __forceinline__ void convert_group(const uint4& ya, const uint4& yb, 
   }
 }
 
-// STAGED: packed rows leave through the per-wave LDS strip (3 x 1 KiB contiguous per
-// wave and row, non-temporal); !STAGED: each lane stores its own 3 x 16 B at a 48 B lane
-// stride (kept as the measured alternative, see DESIGN.md "store path A/B").
-template <int LAYOUT, bool STAGED>
+// Packed rows leave through the per-wave LDS strip (3 x 1 KiB contiguous per wave and row, non-temporal).
+template <int LAYOUT>
 __global__ void __launch_bounds__(kBlock) k_nv12_rgb8(const Nv12RgbArgs a) {
   // dynamic LDS: [0, 12 KiB) = the 4 per-wave strips; the rest only caps residency
   extern __shared__ uint4 dyn_lds[];
@@ -165,17 +164,6 @@ __global__ void __launch_bounds__(kBlock) k_nv12_rgb8(const Nv12RgbArgs a) {
           store16_nt(p, make_uint4(o0[4 * c], o0[4 * c + 1], o0[4 * c + 2], o0[4 * c + 3]));
           store16_nt(p + dp, make_uint4(o1[4 * c], o1[4 * c + 1], o1[4 * c + 2], o1[4 * c + 3]));
         }
-      }
-    } else if constexpr (!STAGED) {
-      if (lane_valid) {
-        uint4* p = reinterpret_cast<uint4*>(pd0 + (size_t)row0 * dp + (size_t)g * 48);
-        p[0] = make_uint4(o0[0], o0[1], o0[2], o0[3]);
-        p[1] = make_uint4(o0[4], o0[5], o0[6], o0[7]);
-        p[2] = make_uint4(o0[8], o0[9], o0[10], o0[11]);
-        uint4* q = reinterpret_cast<uint4*>(pd0 + (size_t)(row0 + 1) * dp + (size_t)g * 48);
-        q[0] = make_uint4(o1[0], o1[1], o1[2], o1[3]);
-        q[1] = make_uint4(o1[4], o1[5], o1[6], o1[7]);
-        q[2] = make_uint4(o1[8], o1[9], o1[10], o1[11]);
       }
     } else {
       PackedStrip& strip = strips[wave];
@@ -250,27 +238,19 @@ static int launch_nv12_rgb(Nv12RgbArgs& a, int width, int height, int n, int dst
   a.map = make_tile_map((groups + row_block - 1) / row_block, ((height + 1) / 2 + a.rp - 1) / a.rp, (u32)n);
   block = row_block * a.rp;
   const dim3 grid = tile_grid(a.map);
-  // A/B switches (include/vali_hip.h: vali_tuning_key)
-  const bool direct = tuning(VALI_TUNE_NV12_DIRECT_STORE) == 1;
   const int waves_override = tuning(VALI_TUNE_WAVES_PER_CU);
   const int waves_per_cu = waves_override > 0 ? waves_override : streaming_waves_per_cu(groups, row_block, 16);
   const unsigned lds =
       residency_lds_bytes(block, waves_per_cu, (unsigned)sizeof(PackedStrip) * (unsigned)((block + kWave - 1) / kWave));
   switch (dst_format) {
   case VALI_FMT_RGB:
-    if (direct)
-      hipLaunchKernelGGL((k_nv12_rgb8<LAYOUT_RGB, false>), grid, dim3(block), lds, stream, a);
-    else
-      hipLaunchKernelGGL((k_nv12_rgb8<LAYOUT_RGB, true>), grid, dim3(block), lds, stream, a);
+    hipLaunchKernelGGL((k_nv12_rgb8<LAYOUT_RGB>), grid, dim3(block), lds, stream, a);
     break;
   case VALI_FMT_BGR:
-    if (direct)
-      hipLaunchKernelGGL((k_nv12_rgb8<LAYOUT_BGR, false>), grid, dim3(block), lds, stream, a);
-    else
-      hipLaunchKernelGGL((k_nv12_rgb8<LAYOUT_BGR, true>), grid, dim3(block), lds, stream, a);
+    hipLaunchKernelGGL((k_nv12_rgb8<LAYOUT_BGR>), grid, dim3(block), lds, stream, a);
     break;
   case VALI_FMT_RGB_PLANAR:
-    hipLaunchKernelGGL((k_nv12_rgb8<LAYOUT_PLANAR, true>), grid, dim3(block), lds, stream, a);
+    hipLaunchKernelGGL((k_nv12_rgb8<LAYOUT_PLANAR>), grid, dim3(block), lds, stream, a);
     break;
   default:
     return fail(VALI_ERR_UNSUPPORTED, "nv12_to_rgb: unsupported dst format %d", dst_format);

@@ -39,10 +39,6 @@ template <int I> __device__ __forceinline__ u32 ubyte(u32 w) {
 // v_cvt_pk_u8_f32 does exactly that in one instruction and also merges the
 // byte into `old`; tests/test_gpu_quantizer.py pins the instruction against
 // the portable form over a dense sweep of inputs.
-#ifndef VALI_USE_CVT_PK_U8
-#define VALI_USE_CVT_PK_U8 1
-#endif
-
 __device__ __forceinline__ u32 quantize_u8_portable(float v) {
   float r = __builtin_rintf(v);
   r = __builtin_fminf(__builtin_fmaxf(r, 0.0f), 255.0f);
@@ -50,20 +46,10 @@ __device__ __forceinline__ u32 quantize_u8_portable(float v) {
 }
 
 template <int SEL> __device__ __forceinline__ u32 pack_u8(float v, u32 old) {
-#if VALI_USE_CVT_PK_U8
   return __builtin_amdgcn_cvt_pk_u8_f32(v, SEL, old);
-#else
-  return old | (quantize_u8_portable(v) << (8 * SEL));
-#endif
 }
 
-__device__ __forceinline__ u32 quantize_u8(float v) {
-#if VALI_USE_CVT_PK_U8
-  return __builtin_amdgcn_cvt_pk_u8_f32(v, 0, 0u);
-#else
-  return quantize_u8_portable(v);
-#endif
-}
+__device__ __forceinline__ u32 quantize_u8(float v) { return __builtin_amdgcn_cvt_pk_u8_f32(v, 0, 0u); }
 
 // ---- arithmetic shared by several kernels (each restated in oracle/vali_oracle*.c) -----
 // YUV -> RGB in the vali_csc form: R = cy*(Y-y0) + crv*V', G = cy*(Y-y0) + (cgu*U' + cgv*V'),
@@ -147,7 +133,7 @@ template <typename T> __device__ __forceinline__ void gstore_u_nt(void* p, T v) 
 // FASTER than the global_* forms (6.18 vs 6.11 TB/s, 3 interleaved repetitions, profiles/r01_variants.md).
 // NEVER in a kernel that keeps loads in flight across a loop: while a flat access is pending the compiler must treat
 // vmcnt as out of order and turns every wait into vmcnt(0) -- one flat_store per row of the exact-2x UD kernel
-// drained its whole prefetch (round 2).  Those kernels use gload16 / gstore16 and the VALI_GLOBAL forms only.
+// drained its whole prefetch (round 2).  Those kernels use gload16 / gstore16_nt and the VALI_GLOBAL forms only.
 __device__ __forceinline__ void store16_nt(void* p, uint4 v) {
   const v4u32 w = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(w, (v4u32*)p);
@@ -201,10 +187,6 @@ __device__ __forceinline__ uint4 gload16_nt(const void* p) {
   const v4u32 w = __builtin_nontemporal_load((const VALI_GLOBAL v4u32*)p);
   return make_uint4(w.x, w.y, w.z, w.w);
 }
-__device__ __forceinline__ void gstore16(void* p, uint4 v) {
-  const v4u32 w = {v.x, v.y, v.z, v.w};
-  *(VALI_GLOBAL v4u32*)p = w;
-}
 __device__ __forceinline__ void gstore16_nt(void* p, uint4 v) { // whole 128-byte lines per wave instruction only
   const v4u32 w = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(w, (VALI_GLOBAL v4u32*)p);
@@ -212,10 +194,6 @@ __device__ __forceinline__ void gstore16_nt(void* p, uint4 v) { // whole 128-byt
 __device__ __forceinline__ uint2 load8(const void* p) {
   const v2u32 w = *(const VALI_GLOBAL v2u32*)p;
   return make_uint2(w.x, w.y);
-}
-__device__ __forceinline__ void store8(void* p, uint2 v) {
-  const v2u32 w = {v.x, v.y};
-  *(VALI_GLOBAL v2u32*)p = w;
 }
 __device__ __forceinline__ void store8_nt(void* p, uint2 v) {
   const v2u32 w = {v.x, v.y};
@@ -618,14 +596,6 @@ template <> __device__ __forceinline__ u32 finish_bits<uint16_t>(float v) {
 }
 template <> __device__ __forceinline__ u32 finish_bits<float>(float v) { return __float_as_uint(v); }
 
-#ifndef VALI_PX4_NT
-#define VALI_PX4_NT 1
-#endif
-#if VALI_PX4_NT
-#define VALI_PX4_ST(T) gstore_nt<T>
-#else
-#define VALI_PX4_ST(T) gstore<T>
-#endif
 template <typename T, int C>
 __device__ __forceinline__ void store_px4(uint8_t* dst, const float (&res)[4][C], u32 mask) {
   constexpr int E = (int)sizeof(T), N = 4 * C, NB = N * E, PER = 4 / E; // PER elements per dword
@@ -647,7 +617,7 @@ __device__ __forceinline__ void store_px4(uint8_t* dst, const float (&res)[4][C]
     // covers whole 128-byte lines) goes out non-temporal; the wider groups are 2-3 pieces per lane, NB bytes apart.
     if constexpr (NB == 16) {
       const v4u32 q = {w[0], w[1], w[2], w[3]};
-      VALI_PX4_ST(v4u32)(dst, q);
+      gstore_nt<v4u32>(dst, q);
     } else if constexpr (NB % 16 == 0) {
 #pragma unroll
       for (int k = 0; k < NB / 16; ++k) {
@@ -656,7 +626,7 @@ __device__ __forceinline__ void store_px4(uint8_t* dst, const float (&res)[4][C]
       }
     } else if constexpr (NB == 8) {
       const v2u32 q = {w[0], w[1]};
-      VALI_PX4_ST(v2u32)(dst, q);
+      gstore_nt<v2u32>(dst, q);
     } else if constexpr (NB % 8 == 0) {
 #pragma unroll
       for (int k = 0; k < NB / 8; ++k) {
@@ -666,9 +636,9 @@ __device__ __forceinline__ void store_px4(uint8_t* dst, const float (&res)[4][C]
     } else if constexpr (NB == 12) {
       typedef unsigned v3u32 __attribute__((ext_vector_type(3)));
       const v3u32 q = {w[0], w[1], w[2]};
-      VALI_PX4_ST(v3u32)(dst, q); // global_store_dwordx3 (needs 4-byte alignment only)
+      gstore_nt<v3u32>(dst, q); // global_store_dwordx3 (needs 4-byte alignment only)
     } else if constexpr (NB == 4) {
-      VALI_PX4_ST(u32)(dst, w[0]);
+      gstore_nt<u32>(dst, w[0]);
     } else {
 #pragma unroll
       for (int k = 0; k < NB / 4; ++k)

@@ -20,11 +20,13 @@
 //   horizontal pass two completed dst rows at a time: their columns go to a strip in LDS whose slots hold one column of
 //                   BOTH rows (channels of interleaved planes de-interleaved into segments, so every plane is the
 //                   1-channel problem; even and odd positions in separate halves: around 2:1 neighbouring lanes then read
-//                   neighbouring slots) and the wave filters along x: lane l takes elements l, l + 64, l + 128, l + 192
+//                   neighbouring slots) and a second wave filters along x: lane l takes elements l, l + 64, l + 128, ...
 //                   of the tile; a tap is one ds_read_b64 + one v_pk_fma_f32 for two output samples (the weight's half
 //                   broadcast by op_sel), e over the even taps, o over the odd ones, e + o: the specification's order; the
-//                   results are transposed through 2 KiB of LDS so a lane stores 4 adjacent elements of both rows.  The
-//                   tile's column taps are evaluated once per workgroup (wave w the w-th set).
+//                   results are transposed through LDS so a lane stores 4 adjacent elements of both rows.  The column
+//                   taps come from per-geometry tables (tap_table.hip), or are computed in the kernel without one.
+//
+// The general form runs the two passes on the two waves of one workgroup (cols_tile_ws: a producer and a consumer).
 //
 // Per output sample at 2:1: 4 conversions + 6-8 packed FMAs (vertical) + 3 LDS reads + 3 packed FMAs (horizontal) + the
 // quantiser, against 13 conversions + 2.16 x (funnel shifts + 3 packed FMAs) + 3 in round 2's rows-first kernel.  Exact
@@ -43,8 +45,6 @@ constexpr int kColEl = 8;                    // source elements per lane and row
 constexpr int kColSpan = kWave * kColEl;     // 512 source elements per tile row
 constexpr int kColPadL = 4, kColPadR = 4;    // replicas of the first / last pixel
 constexpr int kColStrip = 560;               // SLOTS (float pairs: one column of two dst rows) of a wave's strip: ES segments, pads included
-constexpr int kColLds = 2 * (kColStrip + 256); // floats: + the output transposition (256 elements x 2 rows)
-constexpr int kColWave = kColLds + 576;        // floats of a wave: + its program (kColProg)
 
 // A channel segment of the strip is two halves of kColHalf slots: positions (pixels) of even index in front, of odd index
 // behind.  Around 2:1 the windows of neighbouring dst pixels start two positions apart: their k-th taps are then
@@ -62,14 +62,6 @@ template <int HA, int HB> __device__ __forceinline__ v2f32 pk_mov(v2f32 a, v2f32
   else if constexpr (HA == 1 && HB == 1) asm("v_pk_mov_b32 %0, %1, %2 op_sel:[1,1]" : "=v"(r) : "v"(a), "v"(b));
   else if constexpr (HA == 1) asm("v_pk_mov_b32 %0, %1, %2 op_sel:[1,0]" : "=v"(r) : "v"(a), "v"(b));
   else asm("v_pk_mov_b32 %0, %1, %2 op_sel:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
-// (a[H], a[H]): its own assembly string, so that the compiler cannot fold it into pk_mov's by selecting the operands
-template <int H> __device__ __forceinline__ v2f32 pk_dup(v2f32 a) {
-  v2f32 r;
-  if constexpr (H == 0) asm("v_pk_mov_b32 %0, %1, %1" : "=v"(r) : "v"(a));
-  else asm("v_pk_mov_b32 %0, %1, %1 op_sel:[1,1]" : "=v"(r) : "v"(a));
   return r;
 }
 
@@ -482,279 +474,14 @@ template <typename T> __device__ __forceinline__ void conv8(const u32 (&d)[2 * s
 // slot of strip position q: even positions in the front half of a channel segment, odd ones in the back half
 template <int ES> __device__ __forceinline__ int col_slot(int q) { return (q >> 1) + (q & 1) * kColHalf<ES>; }
 
-template <typename T, int ES, int TAPS, int P>
-__device__ __forceinline__ void cols_tile(const uint8_t* sp, int spitch, int sw, int sh, uint8_t* dp, int dpitch,
-                                          int dw, int dh, u32 tx, u32 ty, int N, int rps, float* lds) {
-  constexpr int kBefore = LzTap<TAPS>::kBefore;
-  constexpr int EB = (int)sizeof(T);
-  constexpr int ND = 2 * EB;                                    // dwords of a lane's 8 elements
-  constexpr int D = EB == 4 ? 3 : EB == 2 ? 3 : P >= 4 ? 2 : 4; // source rows in flight (registers: 8 EB bytes per lane and row; the 4- and 6-slot kernels trade two rows for their fourth wave per SIMD)
-  constexpr int HALF = kColHalf<ES>, SEG = 2 * HALF;            // slots
-  const int lane = threadIdx.x & 63;
-  v2f32* const strip = reinterpret_cast<v2f32*>(lds);           // one slot = one column of TWO dst rows
-  v2f32* const obuf = strip + kColStrip;
-  const u32 lds_base = (u32)(uintptr_t)(__attribute__((address_space(3))) float*)lds; // LDS byte address of the strip
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int dwe = dw * ES, row_el = sw * ES;
-  const int e0 = (int)tx * N, e_last = min(e0 + N, dwe) - 1;
-  const float scale_x = (float)sw / (float)dw;
-
-  // ---- column taps: a lane filters elements lane, lane + 64, lane + 128, lane + 192 of the tile.  The four waves of the
-  // workgroup work on the same tile columns (rows ty * 4 + wave): wave w evaluates the w-th set, all four read them back --
-  // a tap set is ~130 instructions, four of them per wave were a quarter of the kernel's vector instructions ----
-  v2f32 wq[4][TAPS / 2]; // (w0, w1), (w2, w3), ..
-  int ci[4];
-  if constexpr (EB == 4) { // float planes are bound by their memory stream: no workgroup barriers in front of the walk
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const LzTap<TAPS> c = make_lz_tap<TAPS>(min(e0 + p * kWave + lane, e_last) / ES, scale_x);
-#pragma unroll
-      for (int k = 0; k < TAPS / 2; ++k)
-        wq[p][k] = (v2f32){c.w[2 * k], c.w[2 * k + 1]};
-      ci[p] = c.i;
-    }
-  } else {
-    const LzTap<TAPS> c = make_lz_tap<TAPS>(min(e0 + wave * kWave + lane, e_last) / ES, scale_x);
-#pragma unroll
-    for (int k = 0; k < TAPS; ++k)
-      lds[k * kWave + lane] = c.w[k];
-    reinterpret_cast<int*>(lds)[TAPS * kWave + lane] = c.i;
-    __syncthreads();
-    const float* const all = lds - wave * kColWave;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-#pragma unroll
-      for (int k = 0; k < TAPS / 2; ++k)
-        wq[p][k] = (v2f32){all[p * kColWave + 2 * k * kWave + lane], all[p * kColWave + (2 * k + 1) * kWave + lane]};
-      ci[p] = reinterpret_cast<const int*>(all)[p * kColWave + TAPS * kWave + lane];
-    }
-    __syncthreads();
-  }
-  ColProg r;
-  if (!cols_rows<TAPS, P, EB == 4, D>(sh, dh, ty * kWavesPerBlock + (u32)wave, rps, lds + kColLds, r))
-    return;
-
-  // ---- the tile's source span along x (wave-uniform) ----
-  const int px_first = e0 / ES, px_last = e_last / ES;
-  const int ux0 = (int)__builtin_floorf((float)px_first * scale_x) - kBefore - 1;
-  const int ux1 = (int)__builtin_floorf((float)px_last * scale_x) + TAPS + 1 - kBefore;
-  const int sx0 = clampi(ux0, sw - 1), sx1 = clampi(ux1, sw - 1);
-  const int j_begin = (sx0 * ES) & ~(kColEl - 1);               // first element the wave loads
-  const int px_begin = j_begin / ES;
-  const int nl = min((((sx1 + 1) * ES - j_begin) + kColEl - 1) / kColEl, kWave); // lanes with data
-  // the last chunk of a row slides left to END with the row: no byte outside the row is ever read (borrowed surfaces
-  // end where their last row ends); the elements it shares with its neighbour are written twice with the same value
-  const bool ragged = j_begin + kColEl * nl > row_el;           // wave-uniform: only a row's last tile
-  const int j0 = min(j_begin + kColEl * min(lane, nl - 1), row_el - kColEl);
-
-  // strip slots of this lane's 8 elements.  1- and 2-element pixels: its pixels are consecutive positions q0 .. -- those
-  // of q0's parity are one run of adjacent slots (wpos[0] ..), the others another (wpos[1] ..); q0 % 4 == 0 unless the
-  // chunk slid (kColPadL = 4): the runs then start on 16 bytes
-  int wpos[ES == 3 ? kColEl : 2];
-  if constexpr (ES == 3) {
-#pragma unroll
-    for (int q = 0; q < kColEl; ++q) {
-      const int j = j0 + q, px = j / 3;
-      wpos[q] = (j - px * 3) * SEG + col_slot<ES>(kColPadL + px - px_begin);
-    }
-  } else {
-    const int q0 = kColPadL + j0 / ES - px_begin;
-    wpos[0] = col_slot<ES>(q0);
-    wpos[1] = col_slot<ES>(q0 + 1);
-  }
-
-  // ---- horizontal pass set-up: the strip slots of the even and odd taps of this lane's 4 elements ----
-  u32 ha[4][2]; // LDS byte addresses: taps 0, 2, 4 at ha[p][0] + 0, 8, 16; taps 1, 3, 5 at ha[p][1] + 0, 8, 16
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const int e = min(e0 + p * kWave + lane, e_last);
-    const int px = e / ES, ch = e - px * ES;
-    const int q = kColPadL + (min(ci[p], sw - 1) - kBefore - px_begin); // >= kColPadL - kBefore
-    ha[p][0] = lds_base + 8u * (u32)(ch * SEG + col_slot<ES>(q));
-    ha[p][1] = lds_base + 8u * (u32)(ch * SEG + col_slot<ES>(q + 1));
-  }
-  const bool pad_left = ux0 < 0, pad_right = ux1 > sw - 1;                 // wave-uniform
-  const int edge = kColPadL + (sw - 1) - px_begin;                         // the last pixel of the row
-  const int eb = e0 + 4 * lane;                                            // store: 4 adjacent elements
-  const int n_out = min(4, e_last + 1 - eb);
-  // whole dwords from every lane that stores, on 4-byte aligned rows: one store, no per-lane alignment test
-  const bool plain_store = EB == 1 && ((e_last + 1 - e0) & 3) == 0 && ((((uintptr_t)dp) | (uintptr_t)dpitch) & 3u) == 0; // wave-uniform
-
-  auto store_row = [&](int rr, float v0, float v1, float v2, float v3) {
-    uint8_t* const out = dp + (u32)((r.y_first + rr) * dpitch) + (size_t)eb * EB;
-    if (plain_store) {
-      u32 q = __builtin_amdgcn_cvt_pk_u8_f32(v0, 0u, 0u);
-      q = __builtin_amdgcn_cvt_pk_u8_f32(v1, 1u, q);
-      q = __builtin_amdgcn_cvt_pk_u8_f32(v2, 2u, q);
-      q = __builtin_amdgcn_cvt_pk_u8_f32(v3, 3u, q);
-      gstore_nt<u32>(out, q);
-    } else {
-      const float res[4][1] = {{v0}, {v1}, {v2}, {v3}};
-      store_px4<T, 1>(out, res, (1u << n_out) - 1u);
-    }
-  };
-
-  // The pass along the rows takes dst rows in PAIRS: the columns of row rr (even) wait in registers until row rr + 1
-  // completes, then a strip slot holds one column of BOTH rows, so a tap is one ds_read_b64 + one v_pk_fma_f32 whose
-  // weight is the same for both halves -- six of each per two output samples, at any window start (the first r03 form
-  // read aligned float pairs of ONE row: eight of each, and an add).  A wave's last row may be single: it runs as a
-  // pair with itself.  (Writing the halves of a slot as the rows complete, ds_write_b32 at a stride of 8 dwords between
-  // lanes, is an 8-way bank conflict per instruction: measured slower than the r03 form.)
-  v2f32 hold[4];      // the columns of the pair's first row
-  // the first row of a pair is kept, the second goes to the strip with it
-  auto take = [&](bool pair, int rr, v2f32 (&c)[4]) {
-    if (!pair) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        hold[i] = c[i];
-      return;
-    }
-    v2f32 lo[4], hi[4]; // (row a, row b) of this lane's columns 2 i / 2 i + 1 (ES = 2: U / V of pixel i)
-    if ((rr & 1) == 0) { // the wave's last row is the first of a pair: the pair is the row twice
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        lo[i] = pk_dup<0>(c[i]);
-        hi[i] = pk_dup<1>(c[i]);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        lo[i] = pk_mov<0, 0>(hold[i], c[i]);
-        hi[i] = pk_mov<1, 1>(hold[i], c[i]);
-      }
-    }
-    // (lanes past the tile's last chunk repeat it -- j0 -- with the same data: no predicate)
-    {
-      if constexpr (ES == 3) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          strip[wpos[2 * i]] = lo[i];
-          strip[wpos[2 * i + 1]] = hi[i];
-        }
-      } else if (ragged) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if constexpr (ES == 2) { // pixel i: (U, V); pixels 0, 2 in the run of wpos[0], 1, 3 in that of wpos[1]
-            strip[wpos[i & 1] + (i >> 1)] = lo[i];
-            strip[SEG + wpos[i & 1] + (i >> 1)] = hi[i];
-          } else {                 // pixels 2 i (run of wpos[0]) and 2 i + 1 (run of wpos[1])
-            strip[wpos[0] + i] = lo[i];
-            strip[wpos[1] + i] = hi[i];
-          }
-        }
-      } else if constexpr (ES == 2) {
-        *reinterpret_cast<float4*>(strip + wpos[0]) = make_float4(lo[0].x, lo[0].y, lo[2].x, lo[2].y);
-        *reinterpret_cast<float4*>(strip + wpos[1]) = make_float4(lo[1].x, lo[1].y, lo[3].x, lo[3].y);
-        *reinterpret_cast<float4*>(strip + SEG + wpos[0]) = make_float4(hi[0].x, hi[0].y, hi[2].x, hi[2].y);
-        *reinterpret_cast<float4*>(strip + SEG + wpos[1]) = make_float4(hi[1].x, hi[1].y, hi[3].x, hi[3].y);
-      } else {
-        *reinterpret_cast<float4*>(strip + wpos[0]) = make_float4(lo[0].x, lo[0].y, lo[1].x, lo[1].y);
-        *reinterpret_cast<float4*>(strip + wpos[0] + 2) = make_float4(lo[2].x, lo[2].y, lo[3].x, lo[3].y);
-        *reinterpret_cast<float4*>(strip + wpos[1]) = make_float4(hi[0].x, hi[0].y, hi[1].x, hi[1].y);
-        *reinterpret_cast<float4*>(strip + wpos[1] + 2) = make_float4(hi[2].x, hi[2].y, hi[3].x, hi[3].y);
-      }
-    }
-    wave_lds_sync();
-    if (pad_left || pad_right) { // image edges: replicas of the first / last pixel of every channel segment
-      const int ch = lane >> 3, i = lane & 7;
-      if (pad_left && ch < ES && i < kColPadL)
-        strip[ch * SEG + col_slot<ES>(kColPadL - 1 - i)] = strip[ch * SEG + col_slot<ES>(kColPadL)];
-      if (pad_right && ch < ES && i < kColPadR)
-        strip[ch * SEG + col_slot<ES>(edge + 1 + i)] = strip[ch * SEG + col_slot<ES>(edge)];
-      wave_lds_sync();
-    }
-    // Two windows per LDS round trip, every slot with its own ds_read_b64: left to itself the compiler fuses two into a
-    // ds_read2_b64, which takes twice the LDS cycles per byte and banks modulo 32 dwords instead of 64
-    // (MI355X_MICROARCH.md, LDS).  Hence the assembly; the wait names every loaded register, so nothing reads one early.
-    // Two windows per block of assembly: their ds_read_b64s (every slot with its own: left to itself the compiler fuses
-    // two into a ds_read2_b64, four times the LDS time -- tools/exp/lds_patterns.hip), the wait for the first window
-    // only, its chains (specification order: e over the even taps, o over the odd ones, e + o; one half of a weight
-    // pair for both halves of the result by op_sel) while the second window's reads are still in flight.  One block: the
-    // compiler pads every boundary between assembly and its own code with an s_nop.
-#pragma unroll
-    for (int half = 0; half < 4; half += 2) {
-      v2f32 t0, t1, t2, t3, t4, t5, u0, u1, u2, u3, u4, u5;
-      if constexpr (TAPS == 6) {
-        asm volatile(
-            "ds_read_b64 %[t0], %[a0]\n\tds_read_b64 %[t1], %[a1]\n\tds_read_b64 %[t2], %[a0] offset:8\n\t"
-            "ds_read_b64 %[t3], %[a1] offset:8\n\tds_read_b64 %[t4], %[a0] offset:16\n\tds_read_b64 %[t5], %[a1] offset:16\n\t"
-            "ds_read_b64 %[u0], %[b0]\n\tds_read_b64 %[u1], %[b1]\n\tds_read_b64 %[u2], %[b0] offset:8\n\t"
-            "ds_read_b64 %[u3], %[b1] offset:8\n\tds_read_b64 %[u4], %[b0] offset:16\n\tds_read_b64 %[u5], %[b1] offset:16\n\t"
-            "s_waitcnt lgkmcnt(6)\n\t"
-            "v_pk_fma_f32 %[t0], %[w0], %[t0], 0 op_sel_hi:[0,1,0]\n\t"
-            "v_pk_fma_f32 %[t1], %[w0], %[t1], 0 op_sel:[1,0,0] op_sel_hi:[1,1,0]\n\t"
-            "v_pk_fma_f32 %[t0], %[w1], %[t2], %[t0] op_sel_hi:[0,1,1]\n\t"
-            "v_pk_fma_f32 %[t1], %[w1], %[t3], %[t1] op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
-            "v_pk_fma_f32 %[t0], %[w2], %[t4], %[t0] op_sel_hi:[0,1,1]\n\t"
-            "v_pk_fma_f32 %[t1], %[w2], %[t5], %[t1] op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
-            "s_waitcnt lgkmcnt(0)\n\t"
-            "v_pk_fma_f32 %[u0], %[x0], %[u0], 0 op_sel_hi:[0,1,0]\n\t"
-            "v_pk_fma_f32 %[u1], %[x0], %[u1], 0 op_sel:[1,0,0] op_sel_hi:[1,1,0]\n\t"
-            "v_pk_add_f32 %[t0], %[t0], %[t1]\n\t"
-            "v_pk_fma_f32 %[u0], %[x1], %[u2], %[u0] op_sel_hi:[0,1,1]\n\t"
-            "v_pk_fma_f32 %[u1], %[x1], %[u3], %[u1] op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
-            "v_pk_fma_f32 %[u0], %[x2], %[u4], %[u0] op_sel_hi:[0,1,1]\n\t"
-            "v_pk_fma_f32 %[u1], %[x2], %[u5], %[u1] op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
-            "s_nop 0\n\t"
-            "v_pk_add_f32 %[u0], %[u0], %[u1]"
-            : [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2),
-              [t3] "=&v"(t3), [t4] "=&v"(t4), [t5] "=&v"(t5), [u0] "=&v"(u0), [u1] "=&v"(u1), [u2] "=&v"(u2), [u3] "=&v"(u3),
-              [u4] "=&v"(u4), [u5] "=&v"(u5)
-            : [a0] "v"(ha[half][0]), [a1] "v"(ha[half][1]), [b0] "v"(ha[half + 1][0]), [b1] "v"(ha[half + 1][1]),
-              [w0] "v"(wq[half][0]), [w1] "v"(wq[half][1]), [w2] "v"(wq[half][TAPS / 2 - 1]), [x0] "v"(wq[half + 1][0]),
-              [x1] "v"(wq[half + 1][1]), [x2] "v"(wq[half + 1][TAPS / 2 - 1])
-            : "memory");
-      } else {
-        asm volatile(
-            "ds_read_b64 %[t0], %[a0]\n\tds_read_b64 %[t1], %[a1]\n\tds_read_b64 %[t2], %[a0] offset:8\n\t"
-            "ds_read_b64 %[t3], %[a1] offset:8\n\t"
-            "ds_read_b64 %[u0], %[b0]\n\tds_read_b64 %[u1], %[b1]\n\tds_read_b64 %[u2], %[b0] offset:8\n\t"
-            "ds_read_b64 %[u3], %[b1] offset:8\n\t"
-            "s_waitcnt lgkmcnt(4)\n\t"
-            "v_pk_fma_f32 %[t0], %[w0], %[t0], 0 op_sel_hi:[0,1,0]\n\t"
-            "v_pk_fma_f32 %[t1], %[w0], %[t1], 0 op_sel:[1,0,0] op_sel_hi:[1,1,0]\n\t"
-            "v_pk_fma_f32 %[t0], %[w1], %[t2], %[t0] op_sel_hi:[0,1,1]\n\t"
-            "v_pk_fma_f32 %[t1], %[w1], %[t3], %[t1] op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
-            "s_waitcnt lgkmcnt(0)\n\t"
-            "v_pk_fma_f32 %[u0], %[x0], %[u0], 0 op_sel_hi:[0,1,0]\n\t"
-            "v_pk_fma_f32 %[u1], %[x0], %[u1], 0 op_sel:[1,0,0] op_sel_hi:[1,1,0]\n\t"
-            "v_pk_add_f32 %[t0], %[t0], %[t1]\n\t"
-            "v_pk_fma_f32 %[u0], %[x1], %[u2], %[u0] op_sel_hi:[0,1,1]\n\t"
-            "v_pk_fma_f32 %[u1], %[x1], %[u3], %[u1] op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
-            "s_nop 0\n\t"
-            "v_pk_add_f32 %[u0], %[u0], %[u1]"
-            : [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2),
-              [t3] "=&v"(t3), [u0] "=&v"(u0), [u1] "=&v"(u1), [u2] "=&v"(u2), [u3] "=&v"(u3)
-            : [a0] "v"(ha[half][0]), [a1] "v"(ha[half][1]), [b0] "v"(ha[half + 1][0]), [b1] "v"(ha[half + 1][1]),
-              [w0] "v"(wq[half][0]), [w1] "v"(wq[half][1]), [x0] "v"(wq[half + 1][0]), [x1] "v"(wq[half + 1][1])
-            : "memory");
-      }
-      obuf[half * kWave + lane] = t0;       // (the chains accumulate in the registers of their first taps)
-      obuf[(half + 1) * kWave + lane] = u0;
-    }
-    wave_lds_sync();
-    if (n_out > 0) {
-      // (two ds_read_b128: the compiler reads the halves it uses as four ds_read2_b32 at a lane stride of 32 bytes --
-      // 8 LDS slots each instead of 2, tools/exp/lds_patterns.hip)
-      float4 v0, v1; // (a0, b0, a1, b1), (a2, b2, a3, b3)
-      asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16\n\ts_waitcnt lgkmcnt(0)"
-                   : "=&v"(v0), "=&v"(v1) : "v"(lds_base + 8u * (u32)kColStrip + 32u * (u32)lane) : "memory");
-      store_row(rr - (rr & 1), v0.x, v0.z, v1.x, v1.z); // (a last row on its own: twice)
-      store_row(rr, v0.y, v0.w, v1.y, v1.w);
-    }
-    wave_lds_sync();
-  };
-  cols_walk<T, TAPS, P, ND, D>(r, sp, spitch, sh, (u32)(j0 * EB), [](const u32 (&d)[ND], v2f32 (&f)[4]) { conv8<T>(d, f); }, take);
-}
-
 // ---- the general form on SPECIALISED waves (round 5) ----
-// The form above runs both passes in ONE wave: a wave that has completed a pair of dst rows stops walking -- strip write,
+// Round 4's form ran both passes in ONE wave: a wave that had completed a pair of dst rows stopped walking -- strip write,
 // tap reads, chains, transposition write, read, quantise, store: three LDS round trips behind each other -- while its loads
-// in flight land and wait; with 118-126 registers at most four such waves share a SIMD, and at any moment most of them wait
-// (profiles/r04_lanczos.md, section 6).  Here a workgroup is TWO waves with one tile: the PRODUCER walks the source rows
-// (loads, conversions, the scatter into the slots' accumulators -- cols_walk, unchanged) and writes every completed pair of
-// dst rows into one of two strips; the CONSUMER runs the pass along the rows on the other strip (the same reads, chains,
-// transposition and stores as above, bit for bit).  The producer never waits for an LDS result but its program entries, the
+// in flight landed and waited; with 118-126 registers at most four such waves shared a SIMD, and at any moment most of them
+// waited (profiles/r04_lanczos.md, section 6).  Here a workgroup is TWO waves with one tile: the PRODUCER walks the source
+// rows (loads, conversions, the scatter into the slots' accumulators -- cols_walk) and writes every completed pair of dst
+// rows into one of two strips; the CONSUMER runs the pass along the rows on the other strip (tap reads, chains,
+// transposition, stores).  The producer never waits for an LDS result but its program entries, the
 // consumer never for a global load; they meet at ONE s_barrier per pair:
 //   producer   [B] W(0) walk [B] W(1) walk ... [B] W(n-1) walk-out [B]        W(k): strip k % 2
 //   consumer   [B]      R(0) [B]      R(1) ...  [B]            R(n-1)
@@ -1468,28 +1195,8 @@ __device__ __forceinline__ void cols_tile_x32(const uint8_t* sp, int spitch, int
   }
 }
 
-// ESSET as in resize_taps.hip: 1 = one-channel planes, 12 = NV12 / P10 (Y + UV), 3 = packed RGB
-template <typename T, int ESSET, int TAPS, int P>
-__global__ void __launch_bounds__(kBlock) k_resize_cols(const ResizeArgs a) {
-  __shared__ __attribute__((aligned(16))) float lds[kWavesPerBlock][kColWave];
-  ResizeJob job;
-  u32 tx, ty, frame;
-  if (!plane_tile(a.job, a.njobs, a.map, job, tx, ty, frame))
-    return;
-  const PlaneView v = plane_view(a.d_src, a.d_dst, frame, job, a.sw, a.sh, a.dw, a.dh);
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  float* const strip = lds[wave];
-  if constexpr (ESSET == 3) {
-    cols_tile<T, 3, TAPS, P>(v.sp, v.spitch, v.sw, v.sh, v.dp, v.dpitch, v.dw, v.dh, tx, ty, a.cols_n, a.cols_rps, strip);
-  } else {
-    if (ESSET == 12 && job.channels == 2)
-      cols_tile<T, 2, TAPS, P>(v.sp, v.spitch, v.sw, v.sh, v.dp, v.dpitch, v.dw, v.dh, tx, ty, a.cols_n, a.cols_rps, strip);
-    else
-      cols_tile<T, 1, TAPS, P>(v.sp, v.spitch, v.sw, v.sh, v.dp, v.dpitch, v.dw, v.dh, tx, ty, a.cols_n, a.cols_rps, strip);
-  }
-}
-
-// waves per SIMD the register allocation aims at: the producer's accumulators are 8 P registers
+// ESSET as in resize_taps.hip: 1 = one-channel planes, 12 = NV12 / P10 (Y + UV), 3 = packed RGB.
+// Waves per SIMD the register allocation aims at: the producer's accumulators are 8 P registers
 template <int EB, int P> constexpr int kWsWaves = EB == 4 ? (P <= 3 ? 4 : 3) : P <= 3 ? (EB == 2 ? 5 : 6) : P <= 4 ? 5 : 4;
 template <typename T, int ESSET, int TAPS, int P, int NS>
 __global__ void __launch_bounds__(kWsBlock, (kWsWaves<(int)sizeof(T), NS == 4 ? P : P < 4 ? 4 : P>)) k_resize_cols_ws(const ResizeArgs a) {
@@ -1579,7 +1286,7 @@ __global__ void __launch_bounds__(kBlock) k_resize_cols_direct(const ResizeArgs 
 }
 
 template <typename T, int ESSET, int TAPS>
-static void launch_slots(const ResizeArgs& a, int slots, int xform, dim3 grid, hipStream_t stream) { // xform: 0 general, 2 / 3: the 2:1 / 3:2-along-x forms, 4: 3:2 both ways
+static void launch_slots(const ResizeArgs& a, int slots, int xform, dim3 grid, hipStream_t stream) { // xform: 2 / 3: the 2:1 / 3:2-along-x forms, 4: 3:2 both ways, 5: general
   constexpr int P0 = TAPS == 6 ? 3 : 2, P1 = TAPS == 6 ? 4 : 3, P2 = TAPS == 6 ? 6 : 4;
   if constexpr (sizeof(T) <= 2 && ESSET != 3) {
     if (xform == 2) {
@@ -1606,29 +1313,21 @@ static void launch_slots(const ResizeArgs& a, int slots, int xform, dim3 grid, h
       return;
     }
   }
-  if (xform == 5) { // the general form on specialised waves: a workgroup = producer + consumer of ONE tile
-    const int cap = tuning(VALI_TUNE_WAVES_PER_CU); // (measurements: workgroups per CU = cap / 2, by unused dynamic LDS)
-    constexpr int kLds = kWsLds<P0, sizeof(T) == 4> * 4;
-    const unsigned dyn = cap >= 2 && 160 * 1024 / (cap / 2) > kLds ? (unsigned)(160 * 1024 / (cap / 2) - kLds) & ~15u : 0u;
+  // the general form on specialised waves: a workgroup = producer + consumer of ONE tile
+  const int cap = tuning(VALI_TUNE_WAVES_PER_CU); // (measurements: workgroups per CU = cap / 2, by unused dynamic LDS)
+  constexpr int kLds = kWsLds<P0, sizeof(T) == 4> * 4;
+  const unsigned dyn = cap >= 2 && 160 * 1024 / (cap / 2) > kLds ? (unsigned)(160 * 1024 / (cap / 2) - kLds) & ~15u : 0u;
 #define VALI_WS_LAUNCH(P, NS) hipLaunchKernelGGL((k_resize_cols_ws<T, ESSET, TAPS, P, NS>), grid, dim3(kWsBlock), dyn, stream, a)
-    if (a.cols_n > 4 * kWave) { // wide tiles: five sets per consumer lane
-      if (slots <= P0) VALI_WS_LAUNCH(P0, 5);
-      else if (slots <= P1) VALI_WS_LAUNCH(P1, 5);
-      else VALI_WS_LAUNCH(P2, 5);
-    } else {
-      if (slots <= P0) VALI_WS_LAUNCH(P0, 4);
-      else if (slots <= P1) VALI_WS_LAUNCH(P1, 4);
-      else VALI_WS_LAUNCH(P2, 4);
-    }
-#undef VALI_WS_LAUNCH
-    return;
+  if (a.cols_n > 4 * kWave) { // wide tiles: five sets per consumer lane
+    if (slots <= P0) VALI_WS_LAUNCH(P0, 5);
+    else if (slots <= P1) VALI_WS_LAUNCH(P1, 5);
+    else VALI_WS_LAUNCH(P2, 5);
+  } else {
+    if (slots <= P0) VALI_WS_LAUNCH(P0, 4);
+    else if (slots <= P1) VALI_WS_LAUNCH(P1, 4);
+    else VALI_WS_LAUNCH(P2, 4);
   }
-  if (slots <= P0)
-    hipLaunchKernelGGL((k_resize_cols<T, ESSET, TAPS, P0>), grid, dim3(kBlock), 0, stream, a);
-  else if (slots <= P1)
-    hipLaunchKernelGGL((k_resize_cols<T, ESSET, TAPS, P1>), grid, dim3(kBlock), 0, stream, a);
-  else
-    hipLaunchKernelGGL((k_resize_cols<T, ESSET, TAPS, P2>), grid, dim3(kBlock), 0, stream, a);
+#undef VALI_WS_LAUNCH
 }
 
 // Every job of `base` shrinks (or keeps) its plane height.  Returns VALI_OK after launching.
@@ -1698,7 +1397,7 @@ int launch_resize_cols(const ResizeArgs& base, int elem, int taps, int src_w, in
   const int P = slots <= pmin ? pmin : slots <= pmid ? pmid : pmax;
   // rows per wave = P x rps <= 64 (a lane evaluates a row's taps) and few enough for the wave's program in LDS:
   // (rows - 1) scale_y + taps + 1 source rows, + the walk's rows in flight (<= 8), <= kProgRows<P>
-  const bool ws = !x2 && !x32 && tuning(VALI_TUNE_RESIZE_COLS) != 1;           // the general form: specialised waves
+  const bool ws = !x2 && !x32;                                                // the general form: specialised waves
   if (ws && tuning(VALI_TUNE_RESIZE_COLS) != 2) {                             // ... with their taps from tables (2: computed in the kernel)
     const int dev = stream_device(stream);
     for (int k = 0; k < a.njobs; ++k) {
@@ -1797,13 +1496,13 @@ int launch_resize_cols(const ResizeArgs& base, int elem, int taps, int src_w, in
 #define VALI_COLS_T(T)                                                               \
   do {                                                                               \
     if (taps == 6) {                                                                 \
-      if (esset == 1) launch_slots<T, 1, 6>(a, P, x2 ? 2 : srows ? 4 : x32 ? 3 : ws ? 5 : 0, grid, stream);                      \
-      else if (esset == 12) launch_slots<T, 12, 6>(a, P, x2 ? 2 : srows ? 4 : x32 ? 3 : ws ? 5 : 0, grid, stream);               \
-      else launch_slots<T, 3, 6>(a, P, x2 ? 2 : srows ? 4 : x32 ? 3 : ws ? 5 : 0, grid, stream);                                 \
+      if (esset == 1) launch_slots<T, 1, 6>(a, P, x2 ? 2 : srows ? 4 : x32 ? 3 : 5, grid, stream);                      \
+      else if (esset == 12) launch_slots<T, 12, 6>(a, P, x2 ? 2 : srows ? 4 : x32 ? 3 : 5, grid, stream);               \
+      else launch_slots<T, 3, 6>(a, P, x2 ? 2 : srows ? 4 : x32 ? 3 : 5, grid, stream);                                 \
     } else {                                                                         \
-      if (esset == 1) launch_slots<T, 1, 4>(a, P, x2 ? 2 : x32 ? 3 : ws ? 5 : 0, grid, stream);                      \
-      else if (esset == 12) launch_slots<T, 12, 4>(a, P, x2 ? 2 : x32 ? 3 : ws ? 5 : 0, grid, stream);               \
-      else launch_slots<T, 3, 4>(a, P, x2 ? 2 : x32 ? 3 : ws ? 5 : 0, grid, stream);                                 \
+      if (esset == 1) launch_slots<T, 1, 4>(a, P, x2 ? 2 : x32 ? 3 : 5, grid, stream);                      \
+      else if (esset == 12) launch_slots<T, 12, 4>(a, P, x2 ? 2 : x32 ? 3 : 5, grid, stream);               \
+      else launch_slots<T, 3, 4>(a, P, x2 ? 2 : x32 ? 3 : 5, grid, stream);                                 \
     }                                                                                \
   } while (0)
   if (elem == 1) VALI_COLS_T(uint8_t);

@@ -52,7 +52,6 @@ struct RotArgs {
   int njobs;
   float c, s;
   TileMap map;
-  int tile_order; // quarter-turn tiles: 0 = walk the source tiles row by row (default), 1 = column by column (A/B)
 };
 
 __device__ __forceinline__ bool rot_tile(const RotArgs& a, RotJob& job, u32& tx, u32& ty, u32& frame) {
@@ -563,14 +562,6 @@ __global__ void __launch_bounds__(kBlock) k_rotate_tile(const RotArgs a) {
   if (!rot_tile(a, job, tile_x, tile_y, frame))
     return;
   const PlaneView v = plane_view(a.d_src, a.d_dst, frame, job, a.sw, a.sh, a.dw, a.dh);
-  if (a.tile_order == 1) { // walk the source tiles column by column: consecutive workgroups write neighbouring dst
-                           // segments.  Measured both ways round: RGB 2160p 90 deg 10.8 -> 10.15 us and 1080p 270 deg
-                           // 2.80 -> 2.72 in one harness, 1080p 90 deg 2.40 -> 2.62 in BASELINE config 4's: not the default
-    const u32 th = P == 3 ? THR : kRotTile;
-    const u32 tiles_y = ((u32)v.sh + th - 1) / th, local = tile_y * job.tiles_x + tile_x;
-    tile_x = local / tiles_y;
-    tile_y = local - tile_x * tiles_y;
-  }
   if constexpr (P == 3) {
     rotate_tile_rgb8<QUARTER, THR>(v, tile_x, tile_y);
   } else {
@@ -896,7 +887,7 @@ static bool launch_affine_lds(RotArgs& a, int n, int sw, int sh, int dw, int dh,
 template <typename T> static bool launch_affine_lds_form(RotArgs& a, int form, int n, int sw, int sh, int dw, int dh, hipStream_t stream) {
   // tile shape: 64 x 64 destination pixels where the launch still has enough workgroups to fill the chip a few times over,
   // 32 x 32 for small launches and for float pixels (whose 64 x 64 box does not fit the LDS budget) -- profiles/r06_rotate.md
-  if (form == 0) {
+  if (form == 0 || form == 2) { // (2: a retired tile shape -- the automatic choice)
     long long tiles64 = 0;
     for (int k = 0; k < a.njobs; ++k)
       tiles64 += (long long)(((dw >> a.job[k].sub_x) + 63) / 64) * (((dh >> a.job[k].sub_y) + 63) / 64);
@@ -909,7 +900,6 @@ template <typename T> static bool launch_affine_lds_form(RotArgs& a, int form, i
   }
   if constexpr (sizeof(T) != 4) {
     switch (form) {
-    case 2: return launch_affine_lds<T, 32, 2>(a, n, sw, sh, dw, dh, stream);
     case 5: // 64 x 128: one-channel 8-bit planes only (a packed-RGB box of that tile does not fit the LDS budget)
       if (sizeof(T) == 1 && launch_affine_lds<uint8_t, 64, 8, 1>(a, n, sw, sh, dw, dh, stream)) return true;
       if (launch_affine_lds<T, 64, 4>(a, n, sw, sh, dw, dh, stream)) return true;
@@ -943,7 +933,6 @@ static int launch_rotate(RotArgs& a, int fmt, int sw, int sh, int dw, int dh, do
                    (q90 && shift_x == 0.0 && shift_y == (double)(sw - 1) && a.njobs == 1) ||
                    (q270 && shift_y == 0.0 && shift_x == (double)(sh - 1) && a.njobs == 1);
   const bool no_tile = tuning(VALI_TUNE_ROTATE_NO_TILE) == 1;
-  a.tile_order = tuning(VALI_TUNE_ROTATE_NO_TILE) == 2 ? 1 : 0;
   const bool tiled = canonical && (q90 || q270) && !no_tile;
   // half turn with each plane's own (W-1, H-1) shifts: a reversal
   const bool half = q180 && !no_tile && sw == dw && sh == dh &&

@@ -106,10 +106,7 @@ template <typename T> __device__ __forceinline__ u32 trunc_sat(float v) {
 constexpr int kUdRowBytes = kWave * 16;         // 1 KiB per staged row
 constexpr int kUdRowsPerWave = 8; // dst rows a wave walks with the same column taps
 constexpr int kUdTileH = kWavesPerBlock * kUdRowsPerWave;
-#ifndef VALI_UD_DEPTH
-#define VALI_UD_DEPTH 2
-#endif
-constexpr int kUdDepth = VALI_UD_DEPTH; // dst rows of prefetch in the staged general kernel
+constexpr int kUdDepth = 2; // dst rows of prefetch in the staged general kernel
 // CH = 16-byte chunks per lane per row: 1 for 8-bit sources, 2 for 16-bit ones (P10: the same
 // 2x downscale spans twice the bytes; with 1 KiB rows it fell to the gather path, 17.7 us)
 template <int CH> struct alignas(16) UdStage {
@@ -194,22 +191,7 @@ __device__ __forceinline__ void trunc_pack_px4(const float* c0, const float* c1,
 // store 4 pixels of one dst row; c0/c1/c2 = Y,U,V or R,G,B already multiplied by
 // UdScale<T,OUT>; n = valid pixels; y is wave-uniform
 // The vector stores of ud_store: neighbouring lanes write neighbouring pixels, so a wave instruction covers whole
-// 128-byte lines -> non-temporal (VALI_UD_NT_STORES=0 builds the plain forms for an A/B).  Packed RGB_32F stays
-// plain: its three 16-byte pieces per lane are 48 bytes apart.
-#ifndef VALI_UD_NT_STORES
-#define VALI_UD_NT_STORES 1
-#endif
-#if VALI_UD_NT_STORES
-#define UD_ST(T) gstore_nt<T>
-#define UD_ST8 store8_nt
-#define UD_ST16F store16f_nt
-#define UD_ST16 gstore16_nt
-#else
-#define UD_ST(T) gstore<T>
-#define UD_ST8 store8
-#define UD_ST16F store16f
-#define UD_ST16 gstore16
-#endif
+// 128-byte lines -> non-temporal.  Packed RGB_32F stays plain: its three 16-byte pieces per lane are 48 bytes apart.
 template <typename T, int OUT>
 __device__ __forceinline__ void ud_store(const SurfRef& d, int x0, int y, int n, const float (&c0)[4],
                                          const float (&c1)[4], const float (&c2)[4]) {
@@ -227,7 +209,7 @@ __device__ __forceinline__ void ud_store(const SurfRef& d, int x0, int y, int n,
       u32 w0, w1, w2;
       trunc_pack3x4(c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3], c2[0], c2[1], c2[2], c2[3], w0, w1, w2);
       if (fast) {
-        UD_ST(u32)(o0, w0); UD_ST(u32)(o1, w1); UD_ST(u32)(o2, w2);
+        gstore_nt<u32>(o0, w0); gstore_nt<u32>(o1, w1); gstore_nt<u32>(o2, w2);
       } else {
         for (int p = 0; p < n; ++p) {
           gstore<uint8_t>(o0 + p, (uint8_t)(w0 >> (8 * p))); gstore<uint8_t>(o1 + p, (uint8_t)(w1 >> (8 * p)));
@@ -241,9 +223,9 @@ __device__ __forceinline__ void ud_store(const SurfRef& d, int x0, int y, int n,
         q0[p] = trunc_sat<T>(c0[p]); q1[p] = trunc_sat<T>(c1[p]); q2[p] = trunc_sat<T>(c2[p]);
       }
       if (fast) {
-        UD_ST8(o0, make_uint2(q0[0] | (q0[1] << 16), q0[2] | (q0[3] << 16)));
-        UD_ST8(o1, make_uint2(q1[0] | (q1[1] << 16), q1[2] | (q1[3] << 16)));
-        UD_ST8(o2, make_uint2(q2[0] | (q2[1] << 16), q2[2] | (q2[3] << 16)));
+        store8_nt(o0, make_uint2(q0[0] | (q0[1] << 16), q0[2] | (q0[3] << 16)));
+        store8_nt(o1, make_uint2(q1[0] | (q1[1] << 16), q1[2] | (q1[3] << 16)));
+        store8_nt(o2, make_uint2(q2[0] | (q2[1] << 16), q2[2] | (q2[3] << 16)));
       } else {
         for (int p = 0; p < n; ++p) {
           gstore<T>(o0 + p * sizeof(T), (T)q0[p]); gstore<T>(o1 + p * sizeof(T), (T)q1[p]); gstore<T>(o2 + p * sizeof(T), (T)q2[p]);
@@ -257,7 +239,7 @@ __device__ __forceinline__ void ud_store(const SurfRef& d, int x0, int y, int n,
     uint8_t* o1 = pd1 + (u32)(y * dp0) + x0;
     uint8_t* o2 = pd2 + (u32)(y * dp0) + x0;
     if (n == 4 && ((((uintptr_t)o0) | ((uintptr_t)o1) | ((uintptr_t)o2)) & 3u) == 0) {
-      UD_ST(u32)(o0, wr); UD_ST(u32)(o1, wg); UD_ST(u32)(o2, wb);
+      gstore_nt<u32>(o0, wr); gstore_nt<u32>(o1, wg); gstore_nt<u32>(o2, wb);
     } else {
       for (int p = 0; p < n; ++p) {
         gstore<uint8_t>(o0 + p, (uint8_t)(wr >> (8 * p))); gstore<uint8_t>(o1 + p, (uint8_t)(wg >> (8 * p)));
@@ -272,7 +254,7 @@ __device__ __forceinline__ void ud_store(const SurfRef& d, int x0, int y, int n,
     if (n == 4 && (((uintptr_t)o) & 3u) == 0) {
       typedef unsigned v3u32 __attribute__((ext_vector_type(3)));
       const v3u32 w = {w0, w1, w2};
-      UD_ST(v3u32)(o, w); // global_store_dwordx3
+      gstore_nt<v3u32>(o, w); // global_store_dwordx3
     } else {
       const u32 ww[3] = {w0, w1, w2};
       for (int k = 0; k < 3 * n; ++k)
@@ -283,9 +265,9 @@ __device__ __forceinline__ void ud_store(const SurfRef& d, int x0, int y, int n,
     uint8_t* o1 = pd1 + (u32)(y * dp0) + (size_t)x0 * 4;
     uint8_t* o2 = pd2 + (u32)(y * dp0) + (size_t)x0 * 4;
     if (n == 4 && ((((uintptr_t)o0) | ((uintptr_t)o1) | ((uintptr_t)o2)) & 15u) == 0) {
-      UD_ST16F(o0, make_float4(c0[0], c0[1], c0[2], c0[3]));
-      UD_ST16F(o1, make_float4(c1[0], c1[1], c1[2], c1[3]));
-      UD_ST16F(o2, make_float4(c2[0], c2[1], c2[2], c2[3]));
+      store16f_nt(o0, make_float4(c0[0], c0[1], c0[2], c0[3]));
+      store16f_nt(o1, make_float4(c1[0], c1[1], c1[2], c1[3]));
+      store16f_nt(o2, make_float4(c2[0], c2[1], c2[2], c2[3]));
     } else {
       for (int p = 0; p < n; ++p) { gstore<float>(o0 + 4 * p, c0[p]); gstore<float>(o1 + 4 * p, c1[p]); gstore<float>(o2 + 4 * p, c2[p]); }
     }
@@ -1101,7 +1083,7 @@ __global__ void __launch_bounds__(kBlock) k_ud_half(const UdArgs a) {
         if (b + 16 <= nbytes) {
           const uint4 v = *reinterpret_cast<const uint4*>(st + b);
           if (dst16)
-            UD_ST16(orow + b, v);
+            gstore16_nt(orow + b, v);
           else
             gstore_u_nt<v4u32>(orow + b, (v4u32){v.x, v.y, v.z, v.w});
         } else if (b < nbytes) {
@@ -1119,7 +1101,7 @@ __global__ void __launch_bounds__(kBlock) k_ud_half(const UdArgs a) {
       for (int k = 0; k < 3; ++k) {
         uint8_t* o = d.p[k] + (u32)(y * pp[k]) + (u32)x0;
         if ((((uintptr_t)d.p[k] | (uintptr_t)pp[k]) & 7u) == 0) // wave-uniform
-          UD_ST8(o, make_uint2(pw[2 * k], pw[2 * k + 1]));
+          store8_nt(o, make_uint2(pw[2 * k], pw[2 * k + 1]));
         else
           gstore_u_nt<v2u32>(o, (v2u32){pw[2 * k], pw[2 * k + 1]});
       }
@@ -1292,7 +1274,7 @@ __global__ void __launch_bounds__(kBlock) k_ud_lean(const UdArgs a) {
         if (b + 16 <= nbytes) {
           const uint4 v = *reinterpret_cast<const uint4*>(st + b);
           if (dst16)
-            UD_ST16(orow + b, v);
+            gstore16_nt(orow + b, v);
           else
             gstore_u_nt<v4u32>(orow + b, (v4u32){v.x, v.y, v.z, v.w});
         } else if (b < nbytes) {
@@ -1310,7 +1292,7 @@ __global__ void __launch_bounds__(kBlock) k_ud_lean(const UdArgs a) {
       for (int k = 0; k < 3; ++k) {
         uint8_t* o = d.p[k] + (u32)(y * pp[k]) + (u32)xl;
         if (!slid && (((uintptr_t)d.p[k] | (uintptr_t)pp[k]) & 7u) == 0) // (wave-uniform but for the slid lane)
-          UD_ST8(o, make_uint2(pw[2 * k], pw[2 * k + 1]));
+          store8_nt(o, make_uint2(pw[2 * k], pw[2 * k + 1]));
         else
           gstore_u_nt<v2u32>(o, (v2u32){pw[2 * k], pw[2 * k + 1]});
       }
@@ -1491,7 +1473,7 @@ __global__ void __launch_bounds__(kBlock) k_ud_32(const UdArgs a) {
         if (b + 16 <= nbytes) {
           const uint4 v = *reinterpret_cast<const uint4*>(st + b);
           if (dst16)
-            UD_ST16(orow + b, v);
+            gstore16_nt(orow + b, v);
           else
             gstore_u_nt<v4u32>(orow + b, (v4u32){v.x, v.y, v.z, v.w});
         } else if (b < nbytes) {
@@ -1509,7 +1491,7 @@ __global__ void __launch_bounds__(kBlock) k_ud_32(const UdArgs a) {
       for (int k = 0; k < 3; ++k) {
         uint8_t* o = d.p[k] + (u32)(y * pp[k]) + (u32)x0;
         if ((((uintptr_t)d.p[k] | (uintptr_t)pp[k]) & 7u) == 0) // wave-uniform
-          UD_ST8(o, make_uint2(pw[2 * k], pw[2 * k + 1]));
+          store8_nt(o, make_uint2(pw[2 * k], pw[2 * k + 1]));
         else
           gstore_u_nt<v2u32>(o, (v2u32){pw[2 * k], pw[2 * k + 1]});
       }
@@ -1531,17 +1513,16 @@ __global__ void __launch_bounds__(kBlock) k_ud_32(const UdArgs a) {
 
 // ---- the same lean form with the output written turned by 90 / 270 degrees: BASELINE config 4 as ONE pass ----
 // k_ud_down2_t collects 256 x 32 tiles, so a destination row receives 32 pixels = 96 bytes per tile: three quarters of a
-// line, 1.13x the written bytes at the memory (profiles/r02_secondary_traffic.md).  Here a workgroup owns 64 columns x 128
-// (or 64: the default, see the launch) rows of the (virtual) un-rotated output: a destination row then gets 128 pixels =
-// 384 bytes = three whole lines per tile (64: 192 bytes, completed by the next tile of the same XCD).  Compute phase: 8 lanes x 8 pixels cover a row of the tile (one 128-byte line of luma per source row), 8 rows per
-// wave instruction, each wave walks 32 (16) rows in 4 (2) steps; pixels go to LDS as one dword each (row stride 65 dwords: the
-// 8 x 8 lanes of a step and the 16 x 4 lanes of a store hit all banks twice at most).  Store phase: 16 lanes x 4 pixels
-// (12 bytes, one dwordx3) walk half a destination segment for 4 neighbouring destination rows.
-template <int ROT, int TH>
+// line, 1.13x the written bytes at the memory (profiles/r02_secondary_traffic.md).  Here a workgroup owns 64 columns x 64
+// rows of the (virtual) un-rotated output: a destination row then gets 64 pixels = 192 bytes per tile, completed by the next
+// tile of the same XCD (see the launch).  Compute phase: 8 lanes x 8 pixels cover a row of the tile (one 128-byte line of luma
+// per source row), 8 rows per wave instruction, each wave walks 16 rows in 2 steps; pixels go to LDS as one dword each (row
+// stride 65 dwords: the 8 x 8 lanes of a step and the 16 x 4 lanes of a store hit all banks twice at most).  Store phase:
+// 16 lanes x 4 pixels (12 bytes, one dwordx3) walk the tile's destination segment for 4 neighbouring destination rows.
+template <int ROT>
 __global__ void __launch_bounds__(kBlock) k_ud_half_t(const UdArgs a) {
   static_assert(ROT == 1 || ROT == 3, "quarter turns only");
-  constexpr int TW = 64, SD = TW + 1, RW = TH / kWavesPerBlock, STEPS = RW / 8; // rows per wave, 8-row steps per wave
-  static_assert(TH == 64 || TH == 128, "tile rows");
+  constexpr int TW = 64, TH = 64, SD = TW + 1, RW = TH / kWavesPerBlock, STEPS = RW / 8; // rows per wave, 8-row steps per wave
   __shared__ u32 tile[TH * SD];
   u32 tile_x, tile_y, frame;
   {
@@ -1625,13 +1606,11 @@ __global__ void __launch_bounds__(kBlock) k_ud_half_t(const UdArgs a) {
   // transposed store: destination row <-> tile column.  ROT 1: dst(y, uw-1-x) = ud(x, y), pixels in rising y;
   // ROT 3: dst(uh-1-y, x) = ud(x, y), pixels in falling y (ud_rot_store)
   const int t = threadIdx.x, qd = t & 15, cc = (t >> 4) & 3, grp = t >> 6; // row quad, column in the group of 4, wave
-  constexpr int HALVES = TH / 64;                                           // 16 row quads per store instruction
 #pragma unroll 1
-  for (int pass = 0; pass < 4 * HALVES; ++pass) {
-    const int half = pass % HALVES, lc = ((pass / HALVES) * 4 + grp) * 4 + cc; // 16 groups of 4 columns x the halves of the rows
+  for (int pass = 0; pass < 4; ++pass) {
+    const int lc = (pass * 4 + grp) * 4 + cc;                              // 16 groups of 4 columns
     const int x = xw + lc;
-    const int quad = half * 16 + qd;                                       // rows 4 quad .. 4 quad + 3 of the tile
-    const int r0 = ROT == 1 ? 4 * quad : TH - 4 - 4 * quad;                // lowest tile row of the quad
+    const int r0 = ROT == 1 ? 4 * qd : TH - 4 - 4 * qd;                    // lowest tile row of the quad (rows 4 qd .. 4 qd + 3)
     if (x >= dw || yb + r0 >= dh || yb + r0 < 0)                           // (dh % 4 == 0: a quad is whole or absent)
       continue;
     u32 pxl[4];
@@ -1953,19 +1932,13 @@ static int launch_ud(UdArgs& a, int src_fmt, int src_w, int src_h, int dst_w, in
   }
   if (down2_mode == 1 && !force_gather && src_fmt == VALI_FMT_NV12 && src_w == 2 * dst_w && src_h == 2 * dst_h && (rot & 1) &&
       dst_w % kD2LanePx == 0 && dst_h % 4 == 0) { // exactly 2:1 both ways: 64 x 128 tiles, whole-line destination segments
-    // 64-row tiles (17 KB of LDS, 9 workgroups per CU) beat 128-row ones (33 KB, 4 per CU) although their destination segments
-    // are 192 bytes instead of three whole lines -- the neighbouring tile follows on the same XCD and the L2 merges the halves:
-    // 2160p -> 1080p 90 deg 3.67 vs 3.75 us, 270 deg 3.71 vs 4.15, 1080p -> 540p 0.87 vs 0.93 (VALI_TUNE_ROTATE_NO_TILE = 3: the tall form)
-    const bool tall = tuning(VALI_TUNE_ROTATE_NO_TILE) == 3;
-    a.map = make_tile_map((dst_w + 63) / 64, tall ? (dst_h + 127) / 128 : (dst_h + 63) / 64, (u32)n);
+    // 64-row tiles (17 KB of LDS, 9 workgroups per CU) measured faster than 128-row ones (33 KB, 4 per CU) although their
+    // destination segments are 192 bytes instead of three whole lines -- the neighbouring tile follows on the same XCD and the
+    // L2 merges the halves: 2160p -> 1080p 90 deg 3.67 vs 3.75 us, 270 deg 3.71 vs 4.15, 1080p -> 540p 0.87 vs 0.93
+    a.map = make_tile_map((dst_w + 63) / 64, (dst_h + 63) / 64, (u32)n);
     const dim3 gt = tile_grid(a.map);
-    if (tall) {
-      if (rot == 1) hipLaunchKernelGGL((k_ud_half_t<1, 128>), gt, block, 0, stream, a);
-      else hipLaunchKernelGGL((k_ud_half_t<3, 128>), gt, block, 0, stream, a);
-    } else {
-      if (rot == 1) hipLaunchKernelGGL((k_ud_half_t<1, 64>), gt, block, 0, stream, a);
-      else hipLaunchKernelGGL((k_ud_half_t<3, 64>), gt, block, 0, stream, a);
-    }
+    if (rot == 1) hipLaunchKernelGGL((k_ud_half_t<1>), gt, block, 0, stream, a);
+    else hipLaunchKernelGGL((k_ud_half_t<3>), gt, block, 0, stream, a);
     VALI_LAUNCH_CHECK();
     return VALI_OK;
   }
