@@ -269,6 +269,47 @@ VALI_API int vali_nv12_preproc_batch(const vali_surface* d_src, const vali_surfa
                                      int dst_format, const vali_preproc_params* params,
                                      vali_stream_t stream);
 
+/*
+ * Regions: crop, letterbox, mosaic.  Item i takes the rectangle `src_*` of its NV12 source
+ * (luma pixels) and places it at the rectangle `dst_*` of its destination (destination pixels).
+ * Inside the placement the result is bit-identical to vali_nv12_preproc on the two views
+ *   view(src, crop)  = plane[0] + src_y * pitch[0] + src_x, plane[1] + (src_y / 2) * pitch[1] + src_x,
+ *                      src_w x src_h
+ *   view(dst, place) = every plane + dst_y * pitch + dst_x * (bytes per pixel of dst->format),
+ *                      dst_w x dst_h
+ * so sampling never reads outside the crop.  Outside the placement, with pad != 0 every pixel is
+ * the colour pad_rgb = (R, G, B) in u8 taken through the same definition: out_c =
+ * ((pad_rgb[c] / 255.0f) / div - mean[c]) / std_[c] for float destinations, the bytes themselves
+ * (in the format's memory order) for 8-bit ones.  With pad == 0 those pixels are not written
+ * (a mosaic).  pad_rgb is read at call time (it may be NULL when pad == 0).
+ * All eight values are even (4:2:0 chroma); both rectangles are at least 2 x 2 and lie inside
+ * their surfaces.  dst->format / dst_format and the normalisation as for vali_nv12_preproc.
+ */
+typedef struct vali_roi {
+  int32_t src_x, src_y, src_w, src_h; /* crop, source luma pixels, even */
+  int32_t dst_x, dst_y, dst_w, dst_h; /* placement, destination pixels, even */
+} vali_roi;                           /* 32 bytes; arrays of it are read by the kernel */
+
+/* roi is in host memory and checked strictly (VALI_ERR_INVALID_ARG); it travels in the kernel arguments */
+VALI_API int vali_nv12_preproc_roi(const vali_surface* src, const vali_surface* dst, const vali_roi* roi,
+                                   const vali_preproc_params* params, int pad, const uint8_t pad_rgb[3],
+                                   vali_stream_t stream);
+/*
+ * Batched form: d_src, d_dst and d_roi are DEVICE arrays of n (0..65535) entries.  The sources
+ * may differ in size (each item reads its own descriptor) and may repeat; the destinations share
+ * dst_width x dst_height and dst_format.  The rectangles cannot be checked on the host, so the
+ * kernel sanitises each one against its own surface (W x H):
+ *   x = clamp(x, 0, W) rounded down to even;  w = clamp(w, 0, W - x) rounded down to even
+ *   (y / h likewise against H; the placement against the destination's size)
+ * An item whose crop or placement is then narrower or shorter than 2 is empty: its destination
+ * is all pad (pad != 0) or untouched (pad == 0).  Whatever the rectangles hold, an item reads only
+ * inside src[i] and writes only inside dst[i]; a valid rectangle is left as it is.
+ */
+VALI_API int vali_nv12_preproc_roi_batch(const vali_surface* d_src, const vali_surface* d_dst,
+                                         const vali_roi* d_roi, int n, int dst_width, int dst_height,
+                                         int dst_format, const vali_preproc_params* params, int pad,
+                                         const uint8_t pad_rgb[3], vali_stream_t stream);
+
 /* ---- UD: chroma upsample + resize (+ YUV->RGB) in one pass ---------------------- */
 
 /*

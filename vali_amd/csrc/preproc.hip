@@ -317,6 +317,349 @@ static int launch_preproc(PreprocArgs& a, int src_w, int src_h, int dst_w, int d
   return VALI_OK;
 }
 
+// ---- regions: crop -> place inside a canvas, the rest padded or left alone -------------------
+// Item i: crop (sx, sy, sw, sh) of src[i] onto place (dx, dy, dw, dh) of dst[i].  Inside the
+// placement every pixel is k_nv12_preproc's on view(src, crop) -> view(dst, place): the same
+// make_lerp grid on scales (float)sw / (float)dw, the same one-load two-tap fetch, quantisation
+// and table.  Equal crop and placement sizes take the same path: the scale is exactly 1, every
+// tap weight 0, and the lerp returns the texel itself.  Outside it: the pad colour, or nothing.
+// The rectangles are workgroup-uniform: loaded with scalar loads and sanitised in SGPRs, so a
+// device-supplied record can never move an access outside the item's own surfaces.
+// Tiles: 4 px x 2 rows per lane as in k_nv12_preproc.  WIDE: the 4 waves side by side (1024 px);
+// TALL (canvases of at most 256 px, the classifier inputs): each wave spans the canvas and the
+// 4 waves take consecutive row pairs -- a 224-wide canvas keeps 7 of 8 lanes busy instead of 1 of 5.
+struct RoiArgs {
+  const vali_surface* d_src;
+  const vali_surface* d_dst;
+  const vali_roi* d_roi;
+  vali_surface src, dst;
+  vali_roi roi;
+  vali_preproc_params prm;
+  TileMap map;
+  int row_pairs; // row pairs a wave walks
+  int pad;       // 0: pixels outside the placement are not written
+  u32 pad_rgb;   // R | G << 8 | B << 16
+};
+
+// step 3 of the definition for (channel c, u8 value q): the operations of k_nv12_preproc's table
+__device__ __forceinline__ float preproc_step3(int q, int c, const vali_preproc_params& prm) {
+  const float f = (float)q / 255.0f;
+  const float g = f / prm.div;
+  return (g - prm.mean[c]) / prm.std_[c];
+}
+
+// Item-uniform records of the batch form (descriptor, rectangle) read through the constant address space: the index is
+// uniform, so they are scalar loads into SGPRs (through generic pointers they would be flat vector loads)
+#define VALI_CONST __attribute__((address_space(4)))
+template <typename T> __device__ __forceinline__ T load_uniform(const T* arr, const T& one, u32 index) {
+  static_assert(sizeof(T) % 4 == 0, "records of whole dwords");
+  if (!arr)
+    return one;
+  const VALI_CONST u32* q = (const VALI_CONST u32*)(arr + index);
+  u32 w[sizeof(T) / 4];
+#pragma unroll
+  for (unsigned i = 0; i < sizeof(T) / 4; ++i)
+    w[i] = q[i];
+  T v;
+  __builtin_memcpy(&v, w, sizeof(T));
+  return v;
+}
+
+__device__ __forceinline__ SurfRef surf_ref(const vali_surface& v) {
+  SurfRef r;
+  r.p[0] = (uint8_t*)v.plane[0]; r.p[1] = (uint8_t*)v.plane[1]; r.p[2] = (uint8_t*)v.plane[2];
+  r.pitch[0] = v.pitch[0]; r.pitch[1] = v.pitch[1]; r.pitch[2] = v.pitch[2];
+  r.width = v.width; r.height = v.height;
+  return r;
+}
+
+// clamp (x, w) into [0, size], both even (the batch form's sanitising rule)
+__device__ __forceinline__ void roi_clamp(int& x, int& w, int size) {
+  size = max(size, 0);
+  x = min(max(x, 0), size) & ~1;
+  w = min(max(w, 0), size - x) & ~1;
+}
+
+template <int OUT, bool TALL>
+__global__ void __launch_bounds__(kBlock) k_nv12_preproc_roi(const RoiArgs a) {
+  constexpr bool kFloat = OUT == PP_F32_PLANAR || OUT == PP_F32_PACKED;
+  constexpr int kTileW = TALL ? kWave * 4 : kPpTileW;
+  __shared__ float lut[kFloat ? 3 : 1][256];
+  u32 tile_x, tile_y, frame;
+  if (!tile_of_block(a.map, tile_x, tile_y, frame))
+    return;
+  const SurfRef s = surf_ref(load_uniform(a.d_src, a.src, frame));
+  const SurfRef d = surf_ref(load_uniform(a.d_dst, a.dst, frame));
+  const vali_roi r = load_uniform(a.d_roi, a.roi, frame);
+  int sx = r.src_x, sy = r.src_y, sw = r.src_w, sh = r.src_h;
+  int dx = r.dst_x, dy = r.dst_y, dw = r.dst_w, dh = r.dst_h;
+  roi_clamp(sx, sw, s.width);
+  roi_clamp(sy, sh, s.height);
+  const int cw = max(d.width, 0) & ~1, ch = max(d.height, 0) & ~1; // the canvas
+  roi_clamp(dx, dw, cw);
+  roi_clamp(dy, dh, ch);
+  const bool empty = sw < 2 || sh < 2 || dw < 2 || dh < 2;
+
+  // does this workgroup's tile meet the placement?  (block-uniform)
+  const int tx0 = tile_x * kTileW;
+  const int ty0 = tile_y * a.row_pairs * (TALL ? 8 : 2);
+  const int th = a.row_pairs * (TALL ? 8 : 2);
+  const bool hits = !empty && tx0 < dx + dw && tx0 + kTileW > dx && ty0 < dy + dh && ty0 + th > dy;
+  if (!hits && !a.pad)
+    return;
+  if constexpr (kFloat) {
+    if (hits) {
+      for (int e = threadIdx.x; e < 3 * 256; e += kBlock)
+        lut[e >> 8][e & 255] = preproc_step3(e & 255, e >> 8, a.prm);
+      __syncthreads();
+    }
+  }
+
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int x0 = tx0 + (TALL ? 0 : wave * kWave * 4) + lane * 4;
+  if (x0 >= cw)
+    return;
+  const int n = min(4, cw - x0); // cw is even: n is 2 or 4
+  // the lane's two pixel pairs (x0, x0 + 1) and (x0 + 2, x0 + 3): dx, dw and x0 are even, so each
+  // pair is wholly inside or wholly outside the placement
+  const bool in0 = hits && x0 >= dx && x0 < dx + dw;
+  const bool in1 = hits && x0 + 2 >= dx && x0 + 2 < dx + dw;
+  float pv[3]; // the pad colour: the normalised value (float outputs) or the byte (8-bit outputs)
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int q = (a.pad_rgb >> (8 * c)) & 255u;
+    const float v = kFloat ? preproc_step3(q, c, a.prm) : (float)q;
+    pv[c] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); // uniform: SGPRs
+  }
+
+  // the view of the crop, and the resize geometry of view -> view (k_nv12_preproc's expressions)
+  const int sp_y = s.pitch[0], sp_uv = s.pitch[1], dp = d.pitch[0];
+  const uint8_t* py = s.p[0] + (size_t)sy * sp_y + sx;
+  const uint8_t* puv = s.p[1] + (size_t)(sy >> 1) * sp_uv + sx;
+  const vali_csc k = a.prm.csc;
+  const float lsx = (float)sw / (float)dw, lsy = (float)sh / (float)dh;
+  const float csx = (float)(sw >> 1) / (float)(dw >> 1), csy = (float)(sh >> 1) / (float)(dh >> 1);
+  const int vx0 = x0 - dx; // the lane's first pixel in view coordinates (even; clamped below for pad lanes)
+  const bool same = sw == dw && sh == dh; // item-uniform
+  Lerp lx[4], cxl[2];
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+    lx[p] = make_lerp(min(max(vx0 + p, 0), dw - 1), lsx, sw);
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+    cxl[j] = make_lerp(min(max((vx0 >> 1) + j, 0), (dw >> 1) - 1), csx, sw >> 1);
+
+#pragma unroll 1
+  for (int it = 0; it < a.row_pairs; ++it) {
+    const int y0 = TALL ? ty0 + (it * kWavesPerBlock + wave) * 2 : ty0 + it * 2; // wave-uniform
+    if (y0 >= ch)
+      break;
+    const bool row_in = y0 >= dy && y0 < dy + dh; // both rows of the pair (dy, dh even)
+    const bool c0 = row_in && in0, c1 = row_in && in1;
+    if (!a.pad && !c0 && !c1)
+      continue;
+    // which of the 4 pixels this lane stores, and is that all of them
+    const bool w01 = c0 || a.pad, w23 = c1 || a.pad;
+    const bool full = n == 4 && w01 && w23;
+    float yv[2][4], uu[2], vv[2];
+    if (same && c0 && c1) {
+      // ---- equal sizes, all 4 pixels inside: the taps are the texels themselves (scale 1, weights 0), so the
+      // lane streams them as k_nv12_preproc<true, *> does -- one dword per row and one of chroma (any alignment:
+      // the crop and the placement may each sit at 2 mod 4) ----
+      const int vy0 = y0 - dy;
+      const u32 w0 = gload_u<u32>(py + (size_t)vy0 * sp_y + vx0);
+      const u32 w1 = gload_u<u32>(py + (size_t)(vy0 + 1) * sp_y + vx0);
+      const u32 wc = gload_u<u32>(puv + (size_t)(vy0 >> 1) * sp_uv + vx0);
+      yv[0][0] = ubyte_f32<0>(w0); yv[0][1] = ubyte_f32<1>(w0); yv[0][2] = ubyte_f32<2>(w0); yv[0][3] = ubyte_f32<3>(w0);
+      yv[1][0] = ubyte_f32<0>(w1); yv[1][1] = ubyte_f32<1>(w1); yv[1][2] = ubyte_f32<2>(w1); yv[1][3] = ubyte_f32<3>(w1);
+      uu[0] = ubyte_f32<0>(wc); vv[0] = ubyte_f32<1>(wc); uu[1] = ubyte_f32<2>(wc); vv[1] = ubyte_f32<3>(wc);
+    } else if (c0 || c1) {
+      // ---- bilinear taps of k_nv12_preproc<false, *> on the view ----
+      typedef uint16_t u16_unaligned __attribute__((aligned(1)));
+      typedef u32 u32_unaligned __attribute__((aligned(1)));
+      auto lerp3 = [](float t00, float t10, float t01, float t11, float ax, float ay) {
+        const float t0 = __builtin_fmaf(ax, t10 - t00, t00);
+        const float t1 = __builtin_fmaf(ax, t11 - t01, t01);
+        return (float)quantize_u8(__builtin_fmaf(ay, t1 - t0, t0));
+      };
+      const int vy0 = y0 - dy;
+#pragma unroll
+      for (int rr = 0; rr < 2; ++rr) {
+        const Lerp ly = make_lerp(min(vy0 + rr, dh - 1), lsy, sh);
+        const uint8_t* r0 = py + (size_t)ly.i0 * sp_y;
+        const uint8_t* r1 = py + (size_t)ly.i1 * sp_y;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          const int base = min(lx[p].i0, sw - 2);
+          const bool edge = lx[p].i0 != base;
+          const u32 w0 = *(const VALI_GLOBAL u16_unaligned*)(r0 + base);
+          const u32 w1 = *(const VALI_GLOBAL u16_unaligned*)(r1 + base);
+          const float t10 = (float)(w0 >> 8), t11 = (float)(w1 >> 8);
+          const float t00 = edge ? t10 : (float)(w0 & 0xffu), t01 = edge ? t11 : (float)(w1 & 0xffu);
+          yv[rr][p] = lerp3(t00, t10, t01, t11, lx[p].a, ly.a);
+        }
+      }
+      const Lerp cy = make_lerp(vy0 >> 1, csy, sh >> 1);
+      const uint8_t* q0 = puv + (size_t)cy.i0 * sp_uv;
+      const uint8_t* q1 = puv + (size_t)cy.i1 * sp_uv;
+      if (sw >= 4) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int base = min(cxl[j].i0, (sw >> 1) - 2);
+          const bool edge = cxl[j].i0 != base;
+          const u32 w0 = *(const VALI_GLOBAL u32_unaligned*)(q0 + 2 * base); // U V U' V'
+          const u32 w1 = *(const VALI_GLOBAL u32_unaligned*)(q1 + 2 * base);
+          const float u10 = ubyte_f32<2>(w0), v10 = ubyte_f32<3>(w0), u11 = ubyte_f32<2>(w1), v11 = ubyte_f32<3>(w1);
+          const float u00 = edge ? u10 : ubyte_f32<0>(w0), v00 = edge ? v10 : ubyte_f32<1>(w0);
+          const float u01 = edge ? u11 : ubyte_f32<0>(w1), v01 = edge ? v11 : ubyte_f32<1>(w1);
+          uu[j] = lerp3(u00, u10, u01, u11, cxl[j].a, cy.a);
+          vv[j] = lerp3(v00, v10, v01, v11, cxl[j].a, cy.a);
+        }
+      } else { // a 2-pixel-wide crop has ONE chroma pair per row
+        const float u0 = (float)gload<uint8_t>(q0), v0 = (float)gload<uint8_t>(q0 + 1);
+        const float u1 = (float)gload<uint8_t>(q1), v1 = (float)gload<uint8_t>(q1 + 1);
+        uu[0] = uu[1] = lerp3(u0, u0, u1, u1, 0.0f, cy.a);
+        vv[0] = vv[1] = lerp3(v0, v0, v1, v1, 0.0f, cy.a);
+      }
+    } else {
+#pragma unroll
+      for (int rr = 0; rr < 2; ++rr)
+#pragma unroll
+        for (int p = 0; p < 4; ++p) yv[rr][p] = 0.0f;
+      uu[0] = uu[1] = vv[0] = vv[1] = 128.0f;
+    }
+    // ---- step 2 + 3, the pad colour where the pixel lies outside the placement ----
+    const ChromaTerm ct[2] = {chroma_term(uu[0], vv[0], k), chroma_term(uu[1], vv[1], k)};
+    // (the two rows stay a rolled loop: unrolled, the packed float form holds both rows' 24 values at once)
+#pragma unroll 1
+    for (int rr = 0; rr < 2; ++rr) {
+      const int y = y0 + rr;
+      float o[3][4]; // [channel][pixel]: float outputs the final value, 8-bit outputs the pre-quantised one
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const bool inside = p < 2 ? c0 : c1;
+        const float yf = luma_term(rr ? yv[1][p] : yv[0][p], k);
+        const ChromaTerm& c = ct[p >> 1];
+        if constexpr (kFloat) {
+          o[0][p] = inside ? lut[0][quantize_u8(yf + c.rv)] : pv[0];
+          o[1][p] = inside ? lut[1][quantize_u8(yf + c.guv)] : pv[1];
+          o[2][p] = inside ? lut[2][quantize_u8(yf + c.bu)] : pv[2];
+        } else {
+          o[0][p] = inside ? yf + c.rv : pv[0];
+          o[1][p] = inside ? yf + c.guv : pv[1];
+          o[2][p] = inside ? yf + c.bu : pv[2];
+        }
+      }
+      auto writes = [&](int p) { return p < n && (p < 2 ? w01 : w23); };
+      if constexpr (OUT == PP_F32_PLANAR) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          uint8_t* q = d.p[c] + (u32)(y * dp) + (size_t)x0 * 4;
+          if (full && (((uintptr_t)q) & 15u) == 0)
+            store16f_nt(q, make_float4(o[c][0], o[c][1], o[c][2], o[c][3]));
+          else
+            for (int p = 0; p < 4; ++p)
+              if (writes(p)) gstore<float>(q + 4 * p, o[c][p]);
+        }
+      } else if constexpr (OUT == PP_F32_PACKED) {
+        uint8_t* q = d.p[0] + (u32)(y * dp) + (size_t)x0 * 12;
+        if (full && (((uintptr_t)q) & 15u) == 0) {
+          store16f(q + 0, make_float4(o[0][0], o[1][0], o[2][0], o[0][1]));
+          store16f(q + 16, make_float4(o[1][1], o[2][1], o[0][2], o[1][2]));
+          store16f(q + 32, make_float4(o[2][2], o[0][3], o[1][3], o[2][3]));
+        } else { // per pixel pair (the unit that is inside or outside): 24 bytes each
+          if (writes(0)) {
+            gstore<float>(q + 0, o[0][0]); gstore<float>(q + 4, o[1][0]); gstore<float>(q + 8, o[2][0]);
+            gstore<float>(q + 12, o[0][1]); gstore<float>(q + 16, o[1][1]); gstore<float>(q + 20, o[2][1]);
+          }
+          if (writes(2)) {
+            gstore<float>(q + 24, o[0][2]); gstore<float>(q + 28, o[1][2]); gstore<float>(q + 32, o[2][2]);
+            gstore<float>(q + 36, o[0][3]); gstore<float>(q + 40, o[1][3]); gstore<float>(q + 44, o[2][3]);
+          }
+        }
+      } else if constexpr (OUT == PP_U8_PLANAR) {
+        u32 w[3] = {0u, 0u, 0u};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          w[c] = pack_u8<0>(o[c][0], w[c]); w[c] = pack_u8<1>(o[c][1], w[c]);
+          w[c] = pack_u8<2>(o[c][2], w[c]); w[c] = pack_u8<3>(o[c][3], w[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          uint8_t* q = d.p[c] + (u32)(y * dp) + x0;
+          if (full && (((uintptr_t)q) & 3u) == 0)
+            gstore<u32>(q, w[c]);
+          else
+            for (int p = 0; p < 4; ++p)
+              if (writes(p)) gstore<uint8_t>(q + p, (uint8_t)(w[c] >> (8 * p)));
+        }
+      } else {
+        // memory order f g l per pixel: f = R (RGB) or B (BGR), l the other one
+        const float (&cf)[4] = OUT == PP_U8_RGB ? o[0] : o[2];
+        const float (&cg)[4] = o[1];
+        const float (&cl)[4] = OUT == PP_U8_RGB ? o[2] : o[0];
+        u32 d0 = 0u, d1 = 0u, d2 = 0u;
+        d0 = pack_u8<0>(cf[0], d0); d0 = pack_u8<1>(cg[0], d0); d0 = pack_u8<2>(cl[0], d0); d0 = pack_u8<3>(cf[1], d0);
+        d1 = pack_u8<0>(cg[1], d1); d1 = pack_u8<1>(cl[1], d1); d1 = pack_u8<2>(cf[2], d1); d1 = pack_u8<3>(cg[2], d1);
+        d2 = pack_u8<0>(cl[2], d2); d2 = pack_u8<1>(cf[3], d2); d2 = pack_u8<2>(cg[3], d2); d2 = pack_u8<3>(cl[3], d2);
+        uint8_t* q = d.p[0] + (u32)(y * dp) + (size_t)x0 * 3;
+        if (full && (((uintptr_t)q) & 3u) == 0) {
+          typedef unsigned v3u32 __attribute__((ext_vector_type(3)));
+          const v3u32 wv = {d0, d1, d2};
+          *(VALI_GLOBAL v3u32*)q = wv;
+        } else {
+          const u32 ww[3] = {d0, d1, d2};
+          for (int b = 0; b < 12; ++b)
+            if (writes(b / 3)) gstore<uint8_t>(q + b, (uint8_t)(ww[b >> 2] >> (8 * (b & 3))));
+        }
+      }
+    }
+  }
+}
+
+static int launch_preproc_roi(RoiArgs& a, int canvas_w, int canvas_h, int dst_fmt, int n, hipStream_t stream) {
+  int out;
+  switch (dst_fmt) {
+  case VALI_FMT_RGB_32F_PLANAR: out = PP_F32_PLANAR; break;
+  case VALI_FMT_RGB_32F: out = PP_F32_PACKED; break;
+  case VALI_FMT_RGB: out = PP_U8_RGB; break;
+  case VALI_FMT_BGR: out = PP_U8_BGR; break;
+  case VALI_FMT_RGB_PLANAR: out = PP_U8_PLANAR; break;
+  default:
+    return fail(VALI_ERR_UNSUPPORTED,
+                "nv12_preproc_roi: destination must be RGB_32F[_PLANAR], RGB, BGR or RGB_PLANAR (got %d)", dst_fmt);
+  }
+  // the tile shape follows the canvas width: narrow canvases stack the waves (see RoiArgs)
+  const bool tall = canvas_w <= kWave * 4;
+  const int tile_w = tall ? kWave * 4 : kPpTileW, rows_per_pair_step = tall ? 2 * kWavesPerBlock : 2;
+  const long long tiles_x = (canvas_w + tile_w - 1) / tile_w;
+  // row pairs per wave: 4, or 2 / 1 while that would leave SIMDs without a wave (launch_preproc's rule)
+  a.row_pairs = kPpRowPairsPerWave;
+  auto tiles_y = [&](int rp) { return (canvas_h + rows_per_pair_step * rp - 1) / (rows_per_pair_step * rp); };
+  while (a.row_pairs > 1 && tiles_x * tiles_y(a.row_pairs) * n * kWavesPerBlock < 2048)
+    a.row_pairs /= 2;
+  a.map = make_tile_map((u32)tiles_x, (u32)tiles_y(a.row_pairs), (u32)n);
+  const dim3 grid = tile_grid(a.map), block(kBlock);
+#define VALI_PPR_CASE(O)                                                                     \
+  case O:                                                                                   \
+    if (tall)                                                                               \
+      hipLaunchKernelGGL((k_nv12_preproc_roi<O, true>), grid, block, 0, stream, a);         \
+    else                                                                                    \
+      hipLaunchKernelGGL((k_nv12_preproc_roi<O, false>), grid, block, 0, stream, a);        \
+    break;
+  switch (out) {
+    VALI_PPR_CASE(PP_F32_PLANAR)
+    VALI_PPR_CASE(PP_F32_PACKED)
+    VALI_PPR_CASE(PP_U8_RGB)
+    VALI_PPR_CASE(PP_U8_BGR)
+    VALI_PPR_CASE(PP_U8_PLANAR)
+  }
+#undef VALI_PPR_CASE
+  VALI_LAUNCH_CHECK();
+  return VALI_OK;
+}
+
 } // namespace vali
 
 using namespace vali;
@@ -359,6 +702,61 @@ int vali_nv12_preproc_batch(const vali_surface* d_src, const vali_surface* d_dst
   hipStream_t s = as_stream(stream);
   VALI_ENTRY(s);
   return launch_preproc(a, src_width, src_height, dst_width, dst_height, dst_format, n, s);
+}
+
+static bool roi_axis_ok(int x, int w, int size) {
+  return x >= 0 && w >= 2 && ((x | w) & 1) == 0 && x <= size - w;
+}
+
+int vali_nv12_preproc_roi(const vali_surface* src, const vali_surface* dst, const vali_roi* roi,
+                          const vali_preproc_params* params, int pad, const uint8_t pad_rgb[3],
+                          vali_stream_t stream) {
+  VALI_REQUIRE(src && dst && roi && params, "null argument");
+  VALI_REQUIRE(!pad || pad_rgb, "null pad colour");
+  VALI_REQUIRE(src->format == VALI_FMT_NV12, "source must be NV12");
+  VALI_REQUIRE(src->width >= 2 && src->height >= 2 && dst->width >= 2 && dst->height >= 2, "empty surface");
+  VALI_REQUIRE(((src->width | src->height | dst->width | dst->height) & 1) == 0, "4:2:0 needs even sizes");
+  VALI_REQUIRE(src->plane[0] && src->plane[1] && dst->plane[0], "null plane");
+  VALI_REQUIRE(planes_fit_32bit(*src) && planes_fit_32bit(*dst), "plane of 4 GiB or more");
+  if (dst->format == VALI_FMT_RGB_32F_PLANAR || dst->format == VALI_FMT_RGB_PLANAR)
+    VALI_REQUIRE(dst->plane[1] && dst->plane[2], "null dst plane");
+  VALI_REQUIRE(roi_axis_ok(roi->src_x, roi->src_w, src->width) && roi_axis_ok(roi->src_y, roi->src_h, src->height),
+               "crop must be even, at least 2 x 2 and inside the source");
+  VALI_REQUIRE(roi_axis_ok(roi->dst_x, roi->dst_w, dst->width) && roi_axis_ok(roi->dst_y, roi->dst_h, dst->height),
+               "placement must be even, at least 2 x 2 and inside the destination");
+  RoiArgs a = {};
+  a.src = *src;
+  a.dst = *dst;
+  a.roi = *roi;
+  a.prm = *params;
+  a.pad = pad != 0;
+  if (pad)
+    a.pad_rgb = (u32)pad_rgb[0] | (u32)pad_rgb[1] << 8 | (u32)pad_rgb[2] << 16;
+  hipStream_t s = as_stream(stream);
+  VALI_ENTRY(s);
+  return launch_preproc_roi(a, dst->width, dst->height, dst->format, 1, s);
+}
+
+int vali_nv12_preproc_roi_batch(const vali_surface* d_src, const vali_surface* d_dst, const vali_roi* d_roi, int n,
+                                int dst_width, int dst_height, int dst_format, const vali_preproc_params* params,
+                                int pad, const uint8_t pad_rgb[3], vali_stream_t stream) {
+  VALI_REQUIRE(d_src && d_dst && d_roi && params, "null argument");
+  VALI_REQUIRE(!pad || pad_rgb, "null pad colour");
+  VALI_REQUIRE(dst_width >= 2 && dst_height >= 2 && ((dst_width | dst_height) & 1) == 0, "bad geometry");
+  VALI_REQUIRE(n >= 0 && n <= 65535, "batch size out of range (0..65535)");
+  if (n == 0)
+    return VALI_OK;
+  RoiArgs a = {};
+  a.d_src = d_src;
+  a.d_dst = d_dst;
+  a.d_roi = d_roi;
+  a.prm = *params;
+  a.pad = pad != 0;
+  if (pad)
+    a.pad_rgb = (u32)pad_rgb[0] | (u32)pad_rgb[1] << 8 | (u32)pad_rgb[2] << 16;
+  hipStream_t s = as_stream(stream);
+  VALI_ENTRY(s);
+  return launch_preproc_roi(a, dst_width, dst_height, dst_format, n, s);
 }
 
 } // extern "C"

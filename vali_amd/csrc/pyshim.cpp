@@ -9,6 +9,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <array>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -47,6 +48,13 @@ struct CvtParams {
 struct PreprocParams {
   vali_preproc_params p;
 };
+
+vali_roi to_roi(const std::array<int32_t, 8>& v) {
+  vali_roi r;
+  r.src_x = v[0]; r.src_y = v[1]; r.src_w = v[2]; r.src_h = v[3];
+  r.dst_x = v[4]; r.dst_y = v[5]; r.dst_w = v[6]; r.dst_h = v[7];
+  return r;
+}
 
 // ---- DLPack ------------------------------------------------------------------
 
@@ -171,6 +179,7 @@ PYBIND11_MODULE(_vali_shim, m) {
   m.attr("ERR_RUNTIME") = VALI_ERR_RUNTIME;
   m.attr("ERR_NO_DEVICE") = VALI_ERR_NO_DEVICE;
   m.attr("SURFACE_DESC_SIZE") = sizeof(vali_surface);
+  m.attr("ROI_SIZE") = sizeof(vali_roi);
 
   py::class_<SurfaceDesc>(m, "SurfaceDesc")
       .def(py::init([](std::vector<uintptr_t> planes, std::vector<int> pitches, int width,
@@ -389,6 +398,26 @@ PYBIND11_MODULE(_vali_shim, m) {
     return (uintptr_t)d;
   });
 
+  // the same for rectangle records: a list of (src_x, src_y, src_w, src_h, dst_x, dst_y, dst_w, dst_h)
+  m.def("rois_upload", [](int device, const std::vector<std::array<int32_t, 8>>& rois, uintptr_t stream) {
+    if (rois.empty())
+      throw py::value_error("rois_upload: empty list");
+    std::vector<vali_roi> host(rois.size());
+    for (size_t i = 0; i < rois.size(); ++i)
+      host[i] = to_roi(rois[i]);
+    const size_t bytes = host.size() * sizeof(vali_roi);
+    void* d = nullptr;
+    check(vali_mem_alloc(device, bytes, &d), "vali_mem_alloc");
+    int rc = vali_memcpy2d_async(device, d, bytes, host.data(), bytes, bytes, 1, 0, P(stream));
+    if (rc == VALI_OK)
+      rc = vali_stream_sync(device, P(stream));
+    if (rc != VALI_OK) {
+      vali_mem_free(device, d);
+      check(rc, "rois_upload");
+    }
+    return (uintptr_t)d;
+  });
+
   // ---- operators: return the C status code; Python maps it to TaskExecInfo ----
   m.def("nv12_to_rgb",
         [](const SurfaceDesc& src, const SurfaceDesc& dst, const Csc& csc, uintptr_t stream) {
@@ -453,6 +482,22 @@ PYBIND11_MODULE(_vali_shim, m) {
           return vali_nv12_preproc_batch((const vali_surface*)P(d_src), (const vali_surface*)P(d_dst), n,
                                          src_width, src_height, dst_width, dst_height, dst_format, &p.p,
                                          P(stream));
+        },
+        py::call_guard<py::gil_scoped_release>());
+
+  m.def("nv12_preproc_roi",
+        [](const SurfaceDesc& src, const SurfaceDesc& dst, const std::array<int32_t, 8>& roi, const PreprocParams& p,
+           bool pad, const std::array<uint8_t, 3>& pad_rgb, uintptr_t stream) {
+          const vali_roi r = to_roi(roi);
+          return vali_nv12_preproc_roi(&src.s, &dst.s, &r, &p.p, pad ? 1 : 0, pad_rgb.data(), P(stream));
+        },
+        py::call_guard<py::gil_scoped_release>());
+  m.def("nv12_preproc_roi_batch",
+        [](uintptr_t d_src, uintptr_t d_dst, uintptr_t d_roi, int n, int dst_width, int dst_height, int dst_format,
+           const PreprocParams& p, bool pad, const std::array<uint8_t, 3>& pad_rgb, uintptr_t stream) {
+          return vali_nv12_preproc_roi_batch((const vali_surface*)P(d_src), (const vali_surface*)P(d_dst),
+                                             (const vali_roi*)P(d_roi), n, dst_width, dst_height, dst_format, &p.p,
+                                             pad ? 1 : 0, pad_rgb.data(), P(stream));
         },
         py::call_guard<py::gil_scoped_release>());
 

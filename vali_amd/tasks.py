@@ -7,10 +7,11 @@ per-pixel work is one C-ABI call into libvali_hip.so per Run
 """
 from __future__ import annotations
 
+import operator
 from typing import List, Optional, Sequence, Tuple
 
 from ._native import shim
-from .enums import (ColorRange, ColorSpace, ColorspaceConversionContext, Interpolation, PixelFormat,
+from .enums import (ColorRange, ColorSpace, ColorspaceConversionContext, DLDeviceType, Interpolation, PixelFormat,
                     TaskExecDetails, TaskExecInfo)
 from .runtime import CudaStreamEvent, HipResMgr, is_capturing
 from .surface import Surface
@@ -700,6 +701,200 @@ class PySurfacePreprocessor(_SurfaceTask):
         r = self.RunBatchAsync(batch, dsts, cc_ctx)
         self._sync()
         return r
+
+    # ---- regions: crop / letterbox / mosaic (vali_nv12_preproc_roi[_batch]) ----
+    # src_rect = (x, y, w, h) in source luma pixels, dst_rect in destination pixels, all even; None = the whole
+    # surface.  Inside dst_rect the result is exactly Run(view of src_rect, view of dst_rect); outside it the pad
+    # colour (R, G, B) in u8 through the same normalisation, or -- pad=None -- nothing is written.
+    def RunRoiAsync(self, src: Surface, dst: Surface, src_rect=None, dst_rect=None, pad=None,
+                    cc_ctx=None) -> Tuple[bool, TaskExecInfo]:
+        if src is None or dst is None or src.IsEmpty or dst.IsEmpty:
+            return False, TaskExecInfo.INVALID_INPUT
+        bad = self._check(src.Format, dst.Format, src.Width, src.Height, dst.Width, dst.Height)
+        if bad:
+            return bad.success, bad.info
+        if self._u8_needs_identity(dst.Format):
+            return False, TaskExecInfo.NOT_SUPPORTED
+        try:
+            roi = _roi_record(src_rect, dst_rect, (src.Width, src.Height), (dst.Width, dst.Height))
+            on, rgb = _pad_colour(pad)
+        except ValueError:
+            return False, TaskExecInfo.INVALID_INPUT
+        p = self._params(cc_ctx)
+        if p is None:
+            return False, TaskExecInfo.UNSUPPORTED_FMT_CONV_PARAMS
+        d = _status(shim.nv12_preproc_roi(src.desc(), dst.desc(), roi, p, on, rgb, self._stream))
+        return d.success, d.info
+
+    def RunRoi(self, src: Surface, dst: Surface, src_rect=None, dst_rect=None, pad=None,
+               cc_ctx=None) -> Tuple[bool, TaskExecInfo]:
+        r = self.RunRoiAsync(src, dst, src_rect, dst_rect, pad, cc_ctx)
+        self._sync()
+        return r
+
+    def PrepareRoiBatch(self, srcs: Sequence[Surface], dsts: Sequence[Surface], src_rects=None,
+                        dst_rects=None) -> "RoiBatch":
+        return RoiBatch(self._gpu_id, self._stream, srcs, dsts, src_rects, dst_rects)
+
+    def RunRoiBatchAsync(self, batch: "RoiBatch", pad=None, cc_ctx=None, rects=None) -> Tuple[bool, TaskExecInfo]:
+        """One launch over the items of `batch`.  `rects`: a contiguous device int32 tensor of shape (n, 8) on the
+        batch's GPU (__cuda_array_interface__ or DLPack) that replaces the batch's rectangles for this call -- read
+        by the kernel, never by the host (detector output: no synchronisation).  Such rectangles are sanitised on the
+        device (include/vali_hip.h); the tensor must stay alive until the launch has run."""
+        if not isinstance(batch, RoiBatch):
+            raise ValueError("RunRoiBatch: pass a RoiBatch (PrepareRoiBatch)")
+        if any(f != F.NV12 for f in batch.src_formats) or batch.dst_format not in (
+                F.RGB_32F, F.RGB_32F_PLANAR, F.RGB, F.BGR, F.RGB_PLANAR):
+            return False, TaskExecInfo.NOT_SUPPORTED
+        if self._u8_needs_identity(batch.dst_format):
+            return False, TaskExecInfo.NOT_SUPPORTED
+        try:
+            on, rgb = _pad_colour(pad)
+        except ValueError:
+            return False, TaskExecInfo.INVALID_INPUT
+        p = self._params(cc_ctx)
+        if p is None:
+            return False, TaskExecInfo.UNSUPPORTED_FMT_CONV_PARAMS
+        d_roi, _hold = (batch.d_roi, None) if rects is None else _device_rects(rects, batch.n, batch.gpu_id)
+        d = _status(shim.nv12_preproc_roi_batch(batch.d_src, batch.d_dst, d_roi, batch.n, batch.dst_size[0],
+                                                batch.dst_size[1], int(batch.dst_format), p, on, rgb, self._stream))
+        return d.success, d.info
+
+    def RunRoiBatch(self, batch: "RoiBatch", pad=None, cc_ctx=None, rects=None) -> Tuple[bool, TaskExecInfo]:
+        r = self.RunRoiBatchAsync(batch, pad, cc_ctx, rects)
+        self._sync()
+        return r
+
+
+def letterbox_rect(src_w: int, src_h: int, dst_w: int, dst_h: int) -> Tuple[int, int, int, int]:
+    """The centred, aspect-preserving, even placement (x, y, w, h) of a src_w x src_h picture inside a
+    dst_w x dst_h canvas: s = min(dst_w / src_w, dst_h / src_h); w = min(dst_w, 2 * round(src_w * s / 2)) (h likewise);
+    x = ((dst_w - w) // 4) * 2 (y likewise).  1920 x 1080 -> 640 x 640 gives (0, 140, 640, 360)."""
+    src_w, src_h, dst_w, dst_h = (int(v) for v in (src_w, src_h, dst_w, dst_h))
+    if min(src_w, src_h, dst_w, dst_h) <= 0:
+        raise ValueError("letterbox_rect: sizes must be positive")
+    s = min(dst_w / src_w, dst_h / src_h)
+    w = min(dst_w, 2 * round(src_w * s / 2))
+    h = min(dst_h, 2 * round(src_h * s / 2))
+    return ((dst_w - w) // 4) * 2, ((dst_h - h) // 4) * 2, w, h
+
+
+def _rect(r, size, what):
+    """A host rectangle (x, y, w, h): even, at least 2 x 2, inside `size`; None = the whole surface."""
+    if r is None:
+        return (0, 0, size[0], size[1])
+    try:
+        x, y, w, h = (operator.index(v) for v in r)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: a rectangle is four integers (x, y, w, h)") from None
+    if (x | y | w | h) & 1 or w < 2 or h < 2 or x < 0 or y < 0 or x + w > size[0] or y + h > size[1]:
+        raise ValueError(f"{what}: {(x, y, w, h)} must be even, at least 2 x 2 and inside {size[0]} x {size[1]}")
+    return (x, y, w, h)
+
+
+def _roi_record(src_rect, dst_rect, src_size, dst_size):
+    return _rect(src_rect, src_size, "src_rect") + _rect(dst_rect, dst_size, "dst_rect")
+
+
+def _pad_colour(pad):
+    """pad=None: pixels outside the placement are left alone; (r, g, b) in 0..255: they take that colour"""
+    if pad is None:
+        return False, (0, 0, 0)
+    try:
+        rgb = tuple(operator.index(v) for v in pad)
+    except (TypeError, ValueError):
+        raise ValueError("pad: None or (r, g, b)") from None
+    if len(rgb) != 3 or any(not 0 <= v <= 255 for v in rgb):
+        raise ValueError("pad: None or (r, g, b) in 0..255")
+    return True, rgb
+
+
+def _device_rects(rects, n, gpu_id):
+    """(device pointer, holder) of an int32 (n, 8) contiguous device tensor; shape, dtype, device and contiguity are
+    all the host checks -- the values are the kernel's to sanitise."""
+    if hasattr(rects, "__cuda_array_interface__"):
+        cai = rects.__cuda_array_interface__
+        shape = tuple(int(v) for v in cai["shape"])
+        strides = cai.get("strides")
+        if cai["typestr"] not in ("<i4", "|i4") or shape != (n, 8):
+            raise ValueError(f"rects: need an int32 tensor of shape ({n}, 8), got {cai['typestr']} {shape}")
+        if strides is not None and (int(strides[1]) != 4 or (n > 1 and int(strides[0]) != 32)):
+            raise ValueError("rects: the tensor must be contiguous")
+        ptr, holder = int(cai["data"][0]), rects
+        dev = getattr(rects, "device", None)
+        device = dev.index if getattr(dev, "type", None) == "cuda" and dev.index is not None else shim.ptr_device(ptr)
+    elif hasattr(rects, "__dlpack__"):
+        info, holder = shim.dlpack_import(rects.__dlpack__())
+        shape, strides = tuple(info["shape"]), tuple(info["strides"])
+        if info["code"] != 0 or info["bits"] != 32 or info["lanes"] != 1 or shape != (n, 8):
+            raise ValueError(f"rects: need an int32 tensor of shape ({n}, 8)")
+        if strides[1] != 1 or (n > 1 and strides[0] != 8):
+            raise ValueError("rects: the tensor must be contiguous")
+        if info["device_type"] not in (int(DLDeviceType.kDLROCM), int(DLDeviceType.kDLCUDA)):
+            raise ValueError("rects: the tensor must live on the GPU")
+        ptr, device = int(info["ptr"]), int(info["device_id"])
+    else:
+        raise ValueError("rects: a device tensor with __cuda_array_interface__ or __dlpack__")
+    if device != gpu_id:
+        raise ValueError(f"rects: the tensor is on device {device}, the batch on {gpu_id}")
+    return ptr, holder
+
+
+class RoiBatch:
+    """Device-resident arrays for n region items: source descriptors (any NV12 sizes, repeats allowed), destination
+    descriptors (one format and size) and rectangle records, uploaded once (PySurfacePreprocessor.PrepareRoiBatch)."""
+
+    def __init__(self, gpu_id: int, stream: int, srcs: Sequence[Surface], dsts: Sequence[Surface], src_rects=None,
+                 dst_rects=None):
+        srcs, dsts = list(srcs), list(dsts)
+        n = len(srcs)
+        if not n or len(dsts) != n:
+            raise ValueError("RoiBatch: need equally long, non-empty src and dst lists")
+        if n > 65535:
+            raise ValueError("RoiBatch: at most 65535 items")
+        src_rects = [None] * n if src_rects is None else list(src_rects)
+        dst_rects = [None] * n if dst_rects is None else list(dst_rects)
+        if len(src_rects) != n or len(dst_rects) != n:
+            raise ValueError("RoiBatch: src_rects / dst_rects need one entry per item")
+        for s in srcs:
+            if s is None or s.IsEmpty or (s.Width | s.Height) & 1:
+                raise ValueError("RoiBatch: sources must be non-empty surfaces of even size")
+        f0, s0 = dsts[0].Format, (dsts[0].Width, dsts[0].Height)
+        for d in dsts:
+            if d is None or d.IsEmpty or d.Format != f0 or (d.Width, d.Height) != s0 or (d.Width | d.Height) & 1:
+                raise ValueError("RoiBatch: destinations must share format and (even) size")
+        self.rects = [_roi_record(sr, dr, (s.Width, s.Height), s0)
+                      for s, sr, dr in zip(srcs, src_rects, dst_rects)]
+        if is_capturing(gpu_id, stream):
+            raise RuntimeError("RoiBatch: cannot be created while the stream is capturing -- PrepareRoiBatch() "
+                               "before the StreamCapture block and Keep() the batch with the capture")
+        self.gpu_id = gpu_id
+        self._stream = stream
+        self.n = n
+        self.src_formats = tuple(s.Format for s in srcs)
+        self.dst_format, self.dst_size = f0, s0
+        self._keep = (srcs, dsts)
+        self.d_src = shim.descs_upload(gpu_id, [s.desc() for s in srcs], stream)
+        self.d_dst = shim.descs_upload(gpu_id, [d.desc() for d in dsts], stream)
+        self.d_roi = shim.rois_upload(gpu_id, self.rects, stream)
+
+    def __len__(self):
+        return self.n
+
+    def __del__(self):
+        if getattr(self, "d_src", 0) or getattr(self, "d_dst", 0) or getattr(self, "d_roi", 0):
+            try:    # a launch issued on the batch's stream may still be reading the arrays
+                shim.stream_sync(self.gpu_id, self._stream)
+            except Exception:
+                pass
+        for name in ("d_src", "d_dst", "d_roi"):
+            p = getattr(self, name, 0)
+            if p:
+                try:
+                    shim.mem_free(self.gpu_id, p)
+                except Exception:
+                    pass
+                setattr(self, name, 0)
 
 
 # ---- PySurfaceRotator --------------------------------------------------------------------
