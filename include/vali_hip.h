@@ -310,6 +310,52 @@ VALI_API int vali_nv12_preproc_roi_batch(const vali_surface* d_src, const vali_s
                                          int dst_format, const vali_preproc_params* params, int pad,
                                          const uint8_t pad_rgb[3], vali_stream_t stream);
 
+/* ---- JPEG: baseline sequential JFIF encoder ------------------------------------------------
+ *
+ * The reference's PyNvJpegEncoder (src/TC/src/TaskNvJpegEncode.cpp) on nvJPEG.  Definition (tests/jpeg_model.py
+ * restates it; with no restart markers its entropy data is byte-identical to libjpeg's for the same pixels):
+ *   - RGB, BGR, RGB_PLANAR: libjpeg's fixed-point rgb_ycc, coded 4:4:4.  YUV444, YUV422, YUV420: the planes as
+ *     they are (no colour conversion), coded with their own sampling.  Other formats: VALI_ERR_UNSUPPORTED.
+ *   - the last column and row of every component are replicated out to its block edge; the dummy blocks of a
+ *     partial MCU have zero AC and the DC of the block to their left (a dummy row: of the previous block of the
+ *     same component in that MCU), as libjpeg's jccoefct;
+ *   - level shift by 128, accurate integer FDCT (libjpeg "islow"), each coefficient / (8 q) rounded half away from
+ *     zero; q from the Annex K tables scaled as jpeg_set_quality(quality, force_baseline = TRUE);
+ *   - Huffman coding with the Annex K tables, a restart marker every restart_interval MCUs (DRI).
+ * A file is vali_jpeg_header + the entropy data of vali_jpeg_encode_batch + EOI (FF D9).
+ */
+typedef struct vali_jpeg_params {
+  int32_t quality;          /* 1..100 (clamped by vali_jpeg_params_init)                           */
+  int32_t format;           /* enum vali_pixel_format of the source surfaces                       */
+  int32_t h_samp, v_samp;   /* luma sampling factors: 1x1 (4:4:4), 2x1 (4:2:2), 2x2 (4:2:0)        */
+  int32_t restart_interval; /* MCUs per restart segment: 1 .. 64 / blocks per MCU                  */
+  int32_t reserved[3];
+  uint8_t qtable[2][64];    /* quantisation tables in natural order: 0 luma, 1 both chroma, 1..255 */
+} vali_jpeg_params;         /* 160 bytes */
+
+/* host only: the parameters of `quality` (clamped to 1..100) for surfaces of `format`; restart_interval is the
+ * largest that keeps a segment within 64 blocks (21 MCUs at 4:4:4, 16 at 4:2:2, 10 at 4:2:0) */
+VALI_API int vali_jpeg_params_init(int quality, int format, vali_jpeg_params* out);
+/* host only: SOI, APP0 (JFIF), DQT, SOF0, DHT, DRI, SOS of a width x height image (1..65535) into out[0..cap),
+ * its length in *len.  out == NULL asks for the length only; cap < length is VALI_ERR_INVALID_ARG (*len still set) */
+VALI_API int vali_jpeg_header(int width, int height, const vali_jpeg_params* params, uint8_t* out, size_t cap,
+                              size_t* len);
+/* worst-case sizes: the device workspace of a batch of n images, and one image's output slot (no input can
+ * overflow either: every segment is sized for its worst case of bits and byte stuffing) */
+VALI_API int vali_jpeg_workspace_size(int n, int width, int height, const vali_jpeg_params* params, size_t* bytes);
+VALI_API int vali_jpeg_stream_capacity(int width, int height, const vali_jpeg_params* params, size_t* bytes);
+/*
+ * Entropy-codes n (0..65535) images: d_src is a DEVICE array of n descriptors of `format` and width x height
+ * (sizes as everywhere: 4:2:0 even width and height, YUV422 even width).  Image i's entropy data, restart markers
+ * included, header and EOI not, goes to d_out + i * out_stride (out_stride >= vali_jpeg_stream_capacity), its
+ * length in bytes to d_sizes[i] (device memory).  workspace: ws_bytes >= vali_jpeg_workspace_size, device memory,
+ * 256-byte aligned.  Four launches in stream order; nothing is allocated and nothing synchronises, so the call
+ * can be captured into a graph.
+ */
+VALI_API int vali_jpeg_encode_batch(const vali_surface* d_src, int n, int width, int height, int format,
+                                    const vali_jpeg_params* params, void* workspace, size_t ws_bytes, uint8_t* d_out,
+                                    size_t out_stride, uint32_t* d_sizes, vali_stream_t stream);
+
 /* ---- UD: chroma upsample + resize (+ YUV->RGB) in one pass ---------------------- */
 
 /*

@@ -1,0 +1,88 @@
+"""Images per second of PyNvJpegEncoder, backend "hip" (vali_jpeg_encode_batch) against "cpu" (Pillow), whole Run
+calls: launches, sizes, the exact D2H copies and the headers included.  1080p and 2160p, RGB and YUV420, q = 90,
+batch 1 / 16 / 64.  Prints one JSON line per configuration and a markdown table (profiles/jpeg.md).
+
+  python tools/bench_jpeg.py [--gpu 0] [--quick]     (--quick: 1080p RGB batch 16, hip only: the profiling run)
+"""
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+import vali_amd as vali  # noqa: E402
+
+
+def frames(fmt, w, h, k, gpu):
+    """k distinct smooth-plus-noise pictures (a realistic bit rate), uploaded"""
+    rng = np.random.default_rng(1)
+    yy, xx = np.mgrid[0:h, 0:w]
+    out = []
+    for i in range(k):
+        rgb = np.stack([(xx + 7 * i) % 256, (yy + xx // 3) % 256, (2 * yy + 11 * i) % 256], -1).astype(np.int16)
+        rgb = np.clip(rgb + rng.integers(-6, 7, rgb.shape), 0, 255).astype(np.uint8)
+        s = vali.Surface.Make(vali.RGB, w, h, gpu)
+        assert vali.PyFrameUploader(gpu).Run(rgb.reshape(-1), s)[0]
+        if fmt != vali.RGB:
+            d = vali.Surface.Make(fmt, w, h, gpu)
+            assert vali.PySurfaceConverter(gpu).Run(s, d)[0]
+            s = d
+        out.append(s)
+    return out
+
+
+def run(enc, ctx, surfs, reps):
+    enc.Run(ctx, surfs)                                       # warm-up (buffers grow, headers cached)
+    best = float("inf")
+    nbytes = 0
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        out, info = enc.Run(ctx, surfs)
+        best = min(best, time.perf_counter() - t0)
+        assert info == vali.TaskExecInfo.SUCCESS
+        nbytes = sum(b.size for b in out)
+    return best, nbytes
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpu", type=int, default=0)
+    ap.add_argument("--quick", action="store_true")
+    a = ap.parse_args()
+    sizes = [(1920, 1080)] if a.quick else [(1920, 1080), (3840, 2160)]
+    fmts = [vali.RGB] if a.quick else [vali.RGB, vali.YUV420]
+    batches = [16] if a.quick else [1, 16, 64]
+    backends = ["hip"] if a.quick else ["hip", "cpu"]
+    rows = []
+    for w, h in sizes:
+        for fmt in fmts:
+            pool = frames(fmt, w, h, 4, a.gpu)
+            for n in batches:
+                surfs = [pool[i % len(pool)] for i in range(n)]
+                for backend in backends:
+                    enc = vali.PyNvJpegEncoder(a.gpu, backend=backend)
+                    ctx = enc.Context(90, fmt)
+                    reps = 10 if backend == "hip" else (3 if n == 1 else 1)
+                    t, nbytes = run(enc, ctx, surfs, reps)
+                    r = {"size": f"{w}x{h}", "format": fmt.name, "batch": n, "backend": backend,
+                         "ms_per_call": round(t * 1e3, 3), "images_per_s": round(n / t, 1),
+                         "mean_file_kib": round(nbytes / n / 1024, 1)}
+                    rows.append(r)
+                    print(json.dumps(r), flush=True)
+    print("\n| size | format | batch | hip img/s | cpu img/s | hip / cpu | file KiB |")
+    print("|---|---|---|---|---|---|---|")
+    for r in rows:
+        if r["backend"] != "hip":
+            continue
+        c = next((x for x in rows if x["backend"] == "cpu" and all(x[k] == r[k] for k in ("size", "format", "batch"))),
+                 None)
+        cpu = c["images_per_s"] if c else float("nan")
+        print(f"| {r['size']} | {r['format']} | {r['batch']} | {r['images_per_s']} | {cpu} | "
+              f"{r['images_per_s'] / cpu:.0f}x | {r['mean_file_kib']} |")
+
+
+if __name__ == "__main__":
+    main()

@@ -16,8 +16,8 @@ offline.  What IS provided so pipelines written against python_vali keep running
 * PyFrameConverter -- the reference's CPU (libswscale) converter API
                  (src/python_vali/src/PyFrameConverter.cpp:21-129) served by the HIP converter:
                  ndarray -> upload -> kernel -> download.  It is NOT a CPU code path.
-* PyNvJpegEncoder -- the reference's JPEG encoder API on the CPU (download + Pillow) so that pipelines keep their
-                 output side.
+* PyNvJpegEncoder -- the reference's JPEG encoder API: backend="cpu" (default) downloads and compresses with Pillow;
+                 backend="hip" encodes baseline JPEG on the GPU (vali_jpeg_encode_batch).
 * PyNvEncoder  -- the reference's video encoder API (src/python_vali/src/PyNvEncoder.cpp:388-630) as "download + CPU
                  FFmpeg": the surface is downloaded on the encoder's stream and handed to a libavcodec encoder through
                  PyAV (libx264 / libx265 by default); raises RuntimeError only when PyAV is not importable.
@@ -31,8 +31,9 @@ from typing import Optional, Tuple
 import numpy as np
 
 from .enums import ColorRange, ColorSpace, DecodeMode, FfmpegLogLevel, PixelFormat, TaskExecInfo
+from ._native import shim
 from .runtime import HipResMgr
-from .surface import FORMATS, Surface
+from .surface import FORMATS, Surface, _DeviceMem
 from .tasks import PySurfaceConverter
 from .transfer import PyFrameUploader, PySurfaceDownloader
 
@@ -743,21 +744,41 @@ class NvJpegEncodeContext:
 
 
 class PyNvJpegEncoder:
-    """JPEG encoder with the reference's call surface (src/python_vali/src/PyNvJpegEncoder.cpp:21-160), served on the
-    CPU: the reference uses the nvJPEG ASIC / CUDA library, this backend downloads the surface on the encoder's stream
-    and compresses with Pillow (libjpeg) when it is importable -- the output side of pipelines written against
-    python_vali keeps working (north_star: decode / encode classes are CPU stubs around the surface path).
-    `Run(context, surfaces)` -> (list of uint8 arrays, TaskExecInfo): all surfaces or none (:36-75)."""
+    """JPEG encoder with the reference's call surface (src/python_vali/src/PyNvJpegEncoder.cpp:21-160).
+    `Run(context, surfaces)` -> (list of uint8 arrays, TaskExecInfo): all surfaces or none (:36-75).
 
-    def __init__(self, gpu_id: int):
-        try:
-            from PIL import Image  # noqa: F401
-        except Exception as exc:  # pragma: no cover - depends on the environment
-            raise RuntimeError("PyNvJpegEncoder: no JPEG ASIC on this backend and Pillow (PIL) is not importable for the "
-                               f"CPU fallback ({exc})") from exc
+    Two backends:
+    * "cpu" (the default): the surface is downloaded on the encoder's stream and compressed with Pillow (libjpeg).
+    * "hip": baseline JPEG on the GPU (vali_jpeg_encode_batch, include/vali_hip.h): colour conversion, FDCT,
+      quantisation and Huffman coding run in HIP; only the finished entropy data of each image comes back over PCIe.
+      Every surface of one size goes into one launch; the header (cached per size, format and quality) and EOI are
+      added on the host.  The files decode to what the "cpu" backend's files decode to (the encoder definition is
+      libjpeg's); they differ in bytes only by the restart markers the GPU coder needs (DRI)."""
+
+    BACKENDS = ("cpu", "hip")
+
+    def __init__(self, gpu_id: int, backend: str = "cpu"):
+        if backend not in self.BACKENDS:
+            raise ValueError(f"PyNvJpegEncoder: backend must be one of {self.BACKENDS}, not {backend!r}")
+        if backend == "cpu":
+            try:
+                from PIL import Image  # noqa: F401
+            except Exception as exc:  # pragma: no cover - depends on the environment
+                raise RuntimeError("PyNvJpegEncoder: no JPEG ASIC on this backend and Pillow (PIL) is not importable "
+                                   f"for the CPU fallback ({exc})") from exc
+        self._backend = backend
         self._gpu_id = int(gpu_id)
         self._stream = HipResMgr.Instance().GetStream(self._gpu_id)
         self._down = PySurfaceDownloader(self._gpu_id, self._stream)
+        # hip backend: device buffers owned by the encoder, grown on demand; parameters and headers cached
+        self._ws = self._out = self._sizes = None
+        self._ws_bytes = self._out_bytes = self._sizes_bytes = 0
+        self._params = {}
+        self._headers = {}
+
+    @property
+    def Backend(self) -> str:
+        return self._backend
 
     def Context(self, compression: int, pixel_format: PixelFormat) -> NvJpegEncodeContext:
         return NvJpegEncodeContext(compression, pixel_format)
@@ -783,6 +804,8 @@ class PyNvJpegEncoder:
         return Image.fromarray(np.ascontiguousarray(np.stack([y, u, v], -1)), "YCbCr")
 
     def Run(self, context: NvJpegEncodeContext, surfaces) -> Tuple[list, TaskExecInfo]:
+        if self._backend == "hip":
+            return self._run_hip(context, list(surfaces))
         import io
 
         buffers = []
@@ -798,4 +821,71 @@ class PyNvJpegEncoder:
             self._image(surf.Format, surf.Width, surf.Height, host).save(
                 out, format="JPEG", quality=q, subsampling=NvJpegEncodeContext._SUBSAMPLING[surf.Format])
             buffers.append(np.frombuffer(out.getvalue(), np.uint8).copy())
+        return buffers, TaskExecInfo.SUCCESS
+
+    # ---- hip backend ----------------------------------------------------------------------------------------------------
+    def _jpeg_params(self, quality: int, fmt: PixelFormat):
+        key = (quality, int(fmt))
+        if key not in self._params:
+            self._params[key] = shim.jpeg_params_init(quality, int(fmt))
+        return self._params[key]
+
+    def _header(self, w: int, h: int, fmt: PixelFormat, quality: int) -> np.ndarray:
+        key = (w, h, int(fmt), quality)
+        if key not in self._headers:
+            self._headers[key] = np.frombuffer(shim.jpeg_header(w, h, self._jpeg_params(quality, fmt)), np.uint8)
+        return self._headers[key]
+
+    def _grow(self, name: str, need: int) -> int:
+        """device pointer of the encoder's buffer `name`, grown to `need` bytes (the old one is freed first: nothing is
+        in flight between calls, Run synchronises)"""
+        mem, have = getattr(self, "_" + name), getattr(self, "_" + name + "_bytes")
+        if mem is None or have < need:
+            setattr(self, "_" + name, None)
+            mem = _DeviceMem(shim.mem_alloc(self._gpu_id, need), self._gpu_id)
+            setattr(self, "_" + name, mem)
+            setattr(self, "_" + name + "_bytes", need)
+        return mem.ptr
+
+    def _run_hip(self, context: NvJpegEncodeContext, surfaces: list) -> Tuple[list, TaskExecInfo]:
+        fmt = context.Format()
+        for surf in surfaces:                       # all or nothing: validate everything before any launch
+            if surf is None or surf.IsEmpty or surf.Format != fmt:
+                return [], TaskExecInfo.FAIL
+            w, h = surf.Width, surf.Height
+            if not (1 <= w <= 65535 and 1 <= h <= 65535):
+                return [], TaskExecInfo.FAIL
+            if (fmt == F.YUV420 and (w | h) & 1) or (fmt == F.YUV422 and w & 1):
+                return [], TaskExecInfo.FAIL
+        q = max(1, min(100, context.Compression()))
+        params = self._jpeg_params(q, fmt)
+        groups = {}
+        for i, surf in enumerate(surfaces):
+            groups.setdefault((surf.Width, surf.Height), []).append(i)
+        buffers = [None] * len(surfaces)
+        g, s = self._gpu_id, self._stream
+        for (w, h), idx in groups.items():
+            n = len(idx)
+            ws_bytes = shim.jpeg_workspace_size(n, w, h, params)
+            cap = shim.jpeg_stream_capacity(w, h, params)
+            ws, out, d_sizes = self._grow("ws", ws_bytes), self._grow("out", n * cap), self._grow("sizes", 4 * n)
+            d_src = shim.descs_upload(g, [surfaces[i].desc() for i in idx], s)
+            try:
+                rc = shim.jpeg_encode_batch(d_src, n, w, h, int(fmt), params, ws, self._ws_bytes, out, cap, d_sizes, s)
+                if rc != 0:
+                    return [], TaskExecInfo.FAIL
+                sizes = np.zeros(n, np.uint32)
+                shim.memcpy2d_async(g, sizes.ctypes.data, 4 * n, d_sizes, 4 * n, 4 * n, 1, 1, s)
+                shim.stream_sync(g, s)
+            finally:
+                shim.mem_free(g, d_src)
+            hdr = self._header(w, h, fmt, q)
+            for k, i in enumerate(idx):             # one exact D2H copy per image, between its header and EOI
+                size = int(sizes[k])
+                buf = np.empty(hdr.size + size + 2, np.uint8)
+                buf[:hdr.size] = hdr
+                buf[-2:] = (0xFF, 0xD9)
+                shim.memcpy2d_async(g, buf.ctypes.data + hdr.size, size, out + k * cap, size, size, 1, 1, s)
+                buffers[i] = buf
+            shim.stream_sync(g, s)
         return buffers, TaskExecInfo.SUCCESS

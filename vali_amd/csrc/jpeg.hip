@@ -1,0 +1,758 @@
+// Baseline sequential JFIF encoder: the reference's PyNvJpegEncoder (src/TC/src/TaskNvJpegEncode.cpp, nvJPEG).
+//
+// DEFINITION = libjpeg's encoder with the Annex K Huffman tables (include/vali_hip.h, "JPEG"); tests/jpeg_model.py
+// restates it and tests/test_jpeg_host.py pins the restatement to Pillow's libjpeg byte for byte.
+//
+// Four launches in stream order; none hands data to another workgroup of the same launch:
+//   k_jpeg_fdct      lane = one 8x8 block of one component, in MCU-interleaved scan order: load (edge replication,
+//                    rgb_ycc for RGB sources), islow FDCT, quantise, zigzag -> 128 B of int16 in the workspace.
+//                    A dummy block of a partial MCU computes the block whose DC it copies and keeps only that DC.
+//   k_jpeg_huff      wave = one restart segment (<= 64 blocks), lane = one block: count the bits of each block,
+//                    prefix-sum them into bit offsets, OR the codes into an LDS bit buffer (ds_or_b32), pad with
+//                    1-bits, then stuff a 0x00 after every 0xFF (per-chunk counts + prefix sum) into the segment's
+//                    worst-case slot; its length goes to the length array.
+//   k_jpeg_offsets   workgroup = one image: exclusive scan of (segment length + 2 bytes of RST) -> offsets, size.
+//   k_jpeg_assemble  workgroup = one segment: copy it and its RST marker to the image's output slot.
+#include <cstring>
+
+#include "common.hpp"
+
+namespace vali {
+namespace {
+
+typedef uint32_t u32;
+typedef uint8_t u8;
+
+// ---- Annex K (ITU T.81): the one copy of the tables, for the header writer and the kernels ---------------------------
+constexpr u8 kLumaQ[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57,
+                           69, 56, 14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64,
+                           81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+constexpr u8 kChromaQ[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99,
+                             99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+                             99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+// natural index of zigzag position k
+constexpr int kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+struct HuffSpec {
+  u8 bits[16];   // BITS: number of codes of length 1..16
+  u8 vals[162];  // HUFFVAL
+  int nvals;
+};
+
+// DHT order: DC luma, AC luma, DC chroma, AC chroma (table class << 4 | id = 0x00, 0x10, 0x01, 0x11)
+constexpr HuffSpec kHuff[4] = {
+    {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}, 12},
+    {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d},
+     {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71,
+      0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72,
+      0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37,
+      0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59,
+      0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83,
+      0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3,
+      0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+      0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2,
+      0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa},
+     162},
+    {{0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}, 12},
+    {{0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77},
+     {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22,
+      0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1,
+      0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36,
+      0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58,
+      0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a,
+      0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a,
+      0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+      0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda,
+      0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa},
+     162}};
+
+// symbol -> (code << 8) | length (Annex C); length 0 = no such symbol
+struct CodeTable {
+  u32 e[256];
+};
+
+constexpr CodeTable build_codes(const HuffSpec& s) {
+  CodeTable t{};
+  u32 code = 0;
+  int k = 0;
+  for (int len = 1; len <= 16; ++len) {
+    for (int i = 0; i < s.bits[len - 1]; ++i)
+      t.e[s.vals[k++]] = (code++ << 8) | (u32)len;
+    code <<= 1;
+  }
+  return t;
+}
+
+// device copy, built at compile time from kHuff: DC luma, AC luma, DC chroma, AC chroma
+__constant__ CodeTable d_codes[4] = {build_codes(kHuff[0]), build_codes(kHuff[1]), build_codes(kHuff[2]),
+                                     build_codes(kHuff[3])};
+
+// Worst case of one block: DC 11 + 11 bits (chroma), 63 AC of 16 + 10 bits: 1660 bits < 208 bytes.  A segment's
+// stuffed bytes at most double that.
+constexpr int kBlockBytes = 208;
+constexpr int kSegBlocks = 64;
+constexpr int kHuffWords = kSegBlocks * kBlockBytes / 4 + 2;  // LDS bit buffer (+ padding word, + spill word)
+
+// ---- geometry ------------------------------------------------------------------------------------------------------------
+struct JpegGeom {
+  int H, V, bpm, R, bps;          // luma sampling, blocks per MCU, MCUs / blocks per segment
+  int mcux, mcuy, nblocks, nseg;  // per image
+  int cw[3], ch[3], bw[3], bh[3]; // component size in samples / real blocks
+  size_t slot;                    // bytes of one segment slot
+  size_t coef_bytes, len_at, off_at, slot_at;  // workspace layout of a batch
+};
+
+int jpeg_sampling(int format, int* H, int* V) {
+  switch (format) {
+  case VALI_FMT_RGB: case VALI_FMT_BGR: case VALI_FMT_RGB_PLANAR: case VALI_FMT_YUV444:
+    *H = 1, *V = 1;
+    return 1;
+  case VALI_FMT_YUV422:
+    *H = 2, *V = 1;
+    return 1;
+  case VALI_FMT_YUV420:
+    *H = 2, *V = 2;
+    return 1;
+  default:
+    return 0;
+  }
+}
+
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// checks params and sizes; fills g (workspace layout for a batch of n)
+int jpeg_geom(const char* fn, int n, int w, int h, const vali_jpeg_params* p, JpegGeom* g) {
+  if (!p)
+    return fail(VALI_ERR_INVALID_ARG, "%s: null params", fn);
+  if (w < 1 || h < 1 || w > 65535 || h > 65535)
+    return fail(VALI_ERR_INVALID_ARG, "%s: size %d x %d outside 1..65535", fn, w, h);
+  int H, V;
+  if (!jpeg_sampling(p->format, &H, &V))
+    return fail(VALI_ERR_UNSUPPORTED, "%s: format %d cannot be encoded", fn, p->format);
+  if (p->h_samp != H || p->v_samp != V)
+    return fail(VALI_ERR_INVALID_ARG, "%s: sampling %dx%d does not match format %d", fn, p->h_samp, p->v_samp,
+                p->format);
+  if (!subsampled_sizes_ok(p->format, w, h))
+    return fail(VALI_ERR_INVALID_ARG, "%s: %d x %d: 4:2:0 needs an even width and height, 4:2:2 an even width", fn,
+                w, h);
+  const int bpm = H * V + 2;
+  if (p->restart_interval < 1 || p->restart_interval * bpm > kSegBlocks)
+    return fail(VALI_ERR_INVALID_ARG, "%s: restart interval %d outside 1..%d", fn, p->restart_interval,
+                kSegBlocks / bpm);
+  for (int t = 0; t < 2; ++t)
+    for (int k = 0; k < 64; ++k)
+      if (p->qtable[t][k] == 0)
+        return fail(VALI_ERR_INVALID_ARG, "%s: quantisation table %d holds 0", fn, t);
+  if (n < 0 || n > 65535)
+    return fail(VALI_ERR_INVALID_ARG, "%s: batch size out of range (0..65535)", fn);
+  g->H = H, g->V = V, g->bpm = bpm, g->R = p->restart_interval, g->bps = g->R * bpm;
+  g->mcux = (w + 8 * H - 1) / (8 * H);
+  g->mcuy = (h + 8 * V - 1) / (8 * V);
+  const long long nmcu = (long long)g->mcux * g->mcuy;
+  g->nblocks = (int)(nmcu * bpm);
+  g->nseg = (int)((nmcu + g->R - 1) / g->R);
+  for (int c = 0; c < 3; ++c) {
+    const int hs = c ? 1 : H, vs = c ? 1 : V;
+    g->cw[c] = (w * hs + H - 1) / H;
+    g->ch[c] = (h * vs + V - 1) / V;
+    g->bw[c] = (g->cw[c] + 7) / 8;
+    g->bh[c] = (g->ch[c] + 7) / 8;
+  }
+  g->slot = (size_t)2 * g->bps * kBlockBytes;
+  // one image's output slot must stay addressable with 32-bit offsets
+  if ((size_t)g->nseg * (g->slot + 2) > 0xFFFFFFFFull)
+    return fail(VALI_ERR_INVALID_ARG, "%s: %d x %d is too large for one output slot", fn, w, h);
+  const size_t nn = (size_t)(n > 0 ? n : 1);
+  g->coef_bytes = align256(nn * g->nblocks * 128);
+  g->len_at = g->coef_bytes;
+  g->off_at = g->len_at + align256(nn * g->nseg * 4);
+  g->slot_at = g->off_at + align256(nn * g->nseg * 4);
+  return VALI_OK;
+}
+
+size_t jpeg_ws_bytes(const JpegGeom& g, int n) { return g.slot_at + (size_t)(n > 0 ? n : 1) * g.nseg * g.slot; }
+
+// ---- k_jpeg_fdct -----------------------------------------------------------------------------------------------------
+struct FdctArgs {
+  const vali_surface* d_src;
+  int16_t* coef;  // image i: coef + i * nblocks * 64
+  int H, V, HV, bpm, mcux, nblocks;
+  int cw[3], ch[3], bw[3], bh[3];
+  u32 recip[2][64];       // jcdctmgr reciprocal of 8 q (natural order)
+  u32 corr_shift[2][64];  // correction | shift << 16
+};
+
+enum { SRC_YUV = 0, SRC_RGB = 1, SRC_BGR = 2, SRC_RGB_PLANAR = 3 };
+
+constexpr int fix16(double x) { return (int)(x * 65536 + 0.5); }
+
+// 8 samples of one row, columns x0.. clamped to the last column cw - 1
+__device__ __forceinline__ void load_row_u8(const u8* row, int x0, int cw, int v[8]) {
+  const u8* p = row + x0;
+  if (x0 + 8 <= cw && (((uintptr_t)p) & 3) == 0) {
+    const u32 a = *(const u32*)p, b = *(const u32*)(p + 4);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      v[i] = (a >> (8 * i)) & 0xFF;
+      v[4 + i] = (b >> (8 * i)) & 0xFF;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      v[i] = row[min(x0 + i, cw - 1)];
+  }
+}
+
+__device__ __forceinline__ void load_row_rgb(const u8* row, int x0, int cw, int r[8], int g[8], int b[8]) {
+  const u8* p = row + 3 * x0;
+  if (x0 + 8 <= cw && (((uintptr_t)p) & 3) == 0) {
+    u32 w[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+      w[i] = ((const u32*)p)[i];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int k = 3 * i;
+      r[i] = (w[k / 4] >> (8 * (k % 4))) & 0xFF;
+      g[i] = (w[(k + 1) / 4] >> (8 * ((k + 1) % 4))) & 0xFF;
+      b[i] = (w[(k + 2) / 4] >> (8 * ((k + 2) % 4))) & 0xFF;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const u8* q = row + 3 * min(x0 + i, cw - 1);
+      r[i] = q[0], g[i] = q[1], b[i] = q[2];
+    }
+  }
+}
+
+__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+
+// one pass of libjpeg's jfdctint over d[0], d[S], ..., d[7 S]; ROWS = pass 1 (keeps PASS1_BITS = 2 extra bits)
+template <bool ROWS, int S>
+__device__ __forceinline__ void fdct_pass(int* d) {
+  constexpr int sh = ROWS ? 13 - 2 : 13 + 2;
+  const int tmp0 = d[0] + d[7 * S], tmp7 = d[0] - d[7 * S];
+  const int tmp1 = d[S] + d[6 * S], tmp6 = d[S] - d[6 * S];
+  const int tmp2 = d[2 * S] + d[5 * S], tmp5 = d[2 * S] - d[5 * S];
+  const int tmp3 = d[3 * S] + d[4 * S], tmp4 = d[3 * S] - d[4 * S];
+  const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+  if (ROWS) {
+    d[0] = (tmp10 + tmp11) * 4;
+    d[4 * S] = (tmp10 - tmp11) * 4;
+  } else {
+    d[0] = descale(tmp10 + tmp11, 2);
+    d[4 * S] = descale(tmp10 - tmp11, 2);
+  }
+  int z1 = (tmp12 + tmp13) * 4433;
+  d[2 * S] = descale(z1 + tmp13 * 6270, sh);
+  d[6 * S] = descale(z1 - tmp12 * 15137, sh);
+  z1 = tmp4 + tmp7;
+  int z2 = tmp5 + tmp6, z3 = tmp4 + tmp6, z4 = tmp5 + tmp7;
+  const int z5 = (z3 + z4) * 9633;
+  const int t4 = tmp4 * 2446, t5 = tmp5 * 16819, t6 = tmp6 * 25172, t7 = tmp7 * 12299;
+  z1 *= -7373;
+  z2 *= -20995;
+  z3 = z3 * -16069 + z5;
+  z4 = z4 * -3196 + z5;
+  d[7 * S] = descale(t4 + z1 + z3, sh);
+  d[5 * S] = descale(t5 + z2 + z4, sh);
+  d[3 * S] = descale(t6 + z2 + z3, sh);
+  d[S] = descale(t7 + z1 + z4, sh);
+}
+
+template <int SRC>
+__global__ void __launch_bounds__(256) k_jpeg_fdct(const FdctArgs a) {
+  const int gb = blockIdx.x * 256 + threadIdx.x;
+  if (gb >= a.nblocks)
+    return;
+  const vali_surface s = a.d_src[blockIdx.y];
+  const int mcu = gb / a.bpm, p = gb - mcu * a.bpm;
+  const int mx = mcu % a.mcux, my = mcu / a.mcux;
+  const int c = p < a.HV ? 0 : p - a.HV + 1;
+  int bx = c ? mx : mx * a.H + p % a.H;
+  int by = c ? my : my * a.V + p / a.H;
+  const int bw = c ? a.bw[1] : a.bw[0], bh = c ? a.bh[1] : a.bh[0];
+  const int cw = c ? a.cw[1] : a.cw[0], ch = c ? a.ch[1] : a.ch[0];
+  // a dummy block of a partial MCU computes the block whose DC it copies (jccoefct): the block to its left, for a
+  // dummy row the last block of the row above in this MCU -- always a real block after clamping
+  const bool dummy = bx >= bw || by >= bh;
+  if (by >= bh) {
+    bx = c ? mx : mx * a.H + a.H - 1;
+    by = bh - 1;
+  }
+  bx = min(bx, bw - 1);
+
+  int d[64];
+  const int x0 = bx * 8;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const int y = min(by * 8 + r, ch - 1);
+    int* v = d + 8 * r;
+    if (SRC == SRC_YUV) {
+      const u8* plane = (const u8*)(c == 0 ? s.plane[0] : c == 1 ? s.plane[1] : s.plane[2]);
+      const int pitch = c == 0 ? s.pitch[0] : c == 1 ? s.pitch[1] : s.pitch[2];
+      load_row_u8(plane + (size_t)y * pitch, x0, cw, v);
+    } else {
+      int R[8], G[8], B[8];
+      if (SRC == SRC_RGB_PLANAR) {
+        load_row_u8((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, cw, R);
+        load_row_u8((const u8*)s.plane[1] + (size_t)y * s.pitch[1], x0, cw, G);
+        load_row_u8((const u8*)s.plane[2] + (size_t)y * s.pitch[2], x0, cw, B);
+      } else if (SRC == SRC_RGB) {
+        load_row_rgb((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, cw, R, G, B);
+      } else {
+        load_row_rgb((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, cw, B, G, R);
+      }
+      // jccolor rgb_ycc_convert: this lane's component only
+      const int kr = c == 0 ? fix16(0.299) : c == 1 ? -fix16(0.16874) : fix16(0.5);
+      const int kg = c == 0 ? fix16(0.587) : c == 1 ? -fix16(0.33126) : -fix16(0.41869);
+      const int kb = c == 0 ? fix16(0.114) : c == 1 ? fix16(0.5) : -fix16(0.08131);
+      const int off = c == 0 ? (1 << 15) : (128 << 16) + (1 << 15) - 1;
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        v[i] = (kr * R[i] + kg * G[i] + kb * B[i] + off) >> 16;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      v[i] -= 128;
+  }
+#pragma unroll
+  for (int r = 0; r < 8; ++r)
+    fdct_pass<true, 1>(d + 8 * r);
+#pragma unroll
+  for (int col = 0; col < 8; ++col)
+    fdct_pass<false, 8>(d + col);
+
+  // quantise: (|x| + corr) * recip >> shift == round_half_away(|x| / 8q) for every |x| < 2^15 (test_jpeg_host)
+  const int t = c ? 1 : 0;
+  u32 out[32];
+#pragma unroll
+  for (int k = 0; k < 64; ++k) {
+    const int x = d[kZigzag[k]];
+    const u32 recip = t ? a.recip[1][kZigzag[k]] : a.recip[0][kZigzag[k]];
+    const u32 cs = t ? a.corr_shift[1][kZigzag[k]] : a.corr_shift[0][kZigzag[k]];
+    const u32 m = (u32)abs(x);
+    const int q = (int)(((m + (cs & 0xFFFF)) * recip) >> (cs >> 16));
+    int v = x < 0 ? -q : q;
+    if (dummy && k)
+      v = 0;
+    if (k & 1)
+      out[k / 2] |= (u32)(v & 0xFFFF) << 16;
+    else
+      out[k / 2] = (u32)(v & 0xFFFF);
+  }
+  uint4* dst = (uint4*)(a.coef + ((size_t)blockIdx.y * a.nblocks + gb) * 64);
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+    dst[i] = make_uint4(out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]);
+}
+
+// ---- k_jpeg_huff -----------------------------------------------------------------------------------------------------
+struct HuffArgs {
+  const int16_t* coef;
+  u32* seglen;  // image i, segment s: [i * nseg + s]
+  u8* slots;    // slot bytes per segment, same order
+  int nblocks, nseg, bpm, HV, bps;
+  u32 slot;
+};
+
+__device__ __forceinline__ int nbits(int v) { return v ? 32 - __clz(abs(v)) : 0; }
+
+// OR `len` (1..32) bits of `code` into the big-endian bit stream at bit `pos`: one or two ds_or_b32
+__device__ __forceinline__ void put_bits(u32* buf, u32 pos, u32 code, int len) {
+  const u32 w = pos >> 5, off = pos & 31;
+  const uint64_t x = (uint64_t)code << (64 - off - len);
+  atomicOr(&buf[w], (u32)(x >> 32));
+  if ((u32)x)
+    atomicOr(&buf[w + 1], (u32)x);
+}
+
+__device__ __forceinline__ u32 wave_incl_scan(u32 v, int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const u32 o = __shfl_up(v, d, 64);
+    if (lane >= d)
+      v += o;
+  }
+  return v;
+}
+
+// EMIT = false: returns the bits of the block; true: writes them at bit `pos`
+template <bool EMIT>
+__device__ __forceinline__ u32 code_block(const int* z, int diff, const u32* dc, const u32* ac, u32* buf, u32 pos) {
+  u32 n = 0;
+  {
+    const int s = nbits(diff);
+    const u32 e = dc[s];
+    const int len = (int)(e & 0xFF) + s;
+    if (EMIT)
+      put_bits(buf, pos, ((e >> 8) << s) | ((u32)(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1)), len);
+    n += len;
+  }
+  int last = 0;
+#pragma unroll
+  for (int k = 1; k < 64; ++k) {
+    const int v = z[k];
+    if (v) {
+      int run = k - last - 1;
+      for (; run > 15; run -= 16) {
+        const u32 e = ac[0xF0];
+        if (EMIT)
+          put_bits(buf, pos + n, e >> 8, (int)(e & 0xFF));
+        n += e & 0xFF;
+      }
+      const int s = nbits(v);
+      const u32 e = ac[(run << 4) | s];
+      const int len = (int)(e & 0xFF) + s;
+      if (EMIT)
+        put_bits(buf, pos + n, ((e >> 8) << s) | ((u32)(v < 0 ? v - 1 : v) & ((1u << s) - 1)), len);
+      n += len;
+      last = k;
+    }
+  }
+  if (last < 63) {
+    const u32 e = ac[0];
+    if (EMIT)
+      put_bits(buf, pos + n, e >> 8, (int)(e & 0xFF));
+    n += e & 0xFF;
+  }
+  return n;
+}
+
+__global__ void __launch_bounds__(64) k_jpeg_huff(const HuffArgs a) {
+  __shared__ u32 s_codes[4][256];
+  __shared__ u32 s_bits[kHuffWords];
+  const int lane = threadIdx.x;
+  const int seg = blockIdx.x;
+  const size_t img = blockIdx.y;
+  for (int i = lane; i < 4 * 256; i += 64)
+    s_codes[i >> 8][i & 255] = d_codes[i >> 8].e[i & 255];
+
+  const int base = seg * a.bps;
+  const int nb = min(a.bps, a.nblocks - base);
+  const bool act = lane < nb;
+  int z[64];
+  if (act) {
+    const uint4* src = (const uint4*)(a.coef + (img * a.nblocks + base + lane) * 64);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const uint4 q = src[i];
+      const u32 w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        z[8 * i + 2 * j] = (int)(int16_t)(w[j] & 0xFFFF);
+        z[8 * i + 2 * j + 1] = (int)(int16_t)(w[j] >> 16);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 64; ++k)
+      z[k] = 0;
+  }
+  // DC prediction from the previous block of the same component; it restarts with the segment
+  const int p = lane % a.bpm;  // segments start on an MCU
+  const bool chroma = p >= a.HV;
+  const int prev = lane - (chroma ? a.bpm : p > 0 ? 1 : a.bpm - a.HV + 1);
+  const int pdc = __shfl(z[0], prev < 0 ? lane : prev, 64);
+  const int diff = z[0] - (prev < 0 ? 0 : pdc);
+  __syncthreads();  // code tables
+
+  const u32* dc = s_codes[chroma ? 2 : 0];
+  const u32* ac = s_codes[chroma ? 3 : 1];
+  const u32 mine = act ? code_block<false>(z, diff, dc, ac, nullptr, 0) : 0;
+  const u32 incl = wave_incl_scan(mine, lane);
+  const u32 total = __shfl(incl, 63, 64);
+  const int nwords = (int)((total + 7) >> 5) + 2;
+  for (int i = lane; i < nwords; i += 64)
+    s_bits[i] = 0;
+  __syncthreads();
+  if (act)
+    code_block<true>(z, diff, dc, ac, s_bits, incl - mine);
+  const u32 pad = (8 - (total & 7)) & 7;
+  if (lane == 0 && pad)
+    put_bits(s_bits, total, (1u << pad) - 1, (int)pad);
+  __syncthreads();
+
+  // byte stuffing: 4 bytes per lane per step, 0xFF counts prefix-summed across the wave
+  const u32 nbytes = (total + pad) >> 3;
+  u8* out = a.slots + (img * a.nseg + seg) * a.slot;
+  u32 opos = 0;
+  for (u32 b0 = 0; b0 < nbytes; b0 += 256) {
+    const u32 bi = b0 + 4 * lane;
+    const u32 word = bi < nbytes ? s_bits[bi >> 2] : 0u;
+    const int nv = bi < nbytes ? (int)min(4u, nbytes - bi) : 0;
+    u32 ff = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      ff += (k < nv && ((word >> (24 - 8 * k)) & 0xFF) == 0xFF) ? 1u : 0u;
+    const u32 fincl = wave_incl_scan(ff, lane);
+    const u32 ftot = __shfl(fincl, 63, 64);
+    u8* o = out + opos + 4 * lane + (fincl - ff);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (k < nv) {
+        const u32 byte = (word >> (24 - 8 * k)) & 0xFF;
+        *o++ = (u8)byte;
+        if (byte == 0xFF)
+          *o++ = 0;
+      }
+    }
+    opos += min(256u, nbytes - b0) + ftot;
+  }
+  if (lane == 0)
+    a.seglen[img * a.nseg + seg] = opos;
+}
+
+// ---- k_jpeg_offsets ----------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_jpeg_offsets(const u32* seglen, u32* segoff, u32* sizes, int nseg) {
+  __shared__ u32 s_wave[4];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const size_t img = blockIdx.x;
+  u32 carry = 0;
+  for (int s0 = 0; s0 < nseg; s0 += 256) {
+    const int s = s0 + tid;
+    const u32 v = s < nseg ? seglen[img * nseg + s] + 2u : 0u;  // + RST marker
+    const u32 incl = wave_incl_scan(v, lane);
+    if (lane == 63)
+      s_wave[wid] = incl;
+    __syncthreads();
+    u32 before = 0, chunk = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      before += w < wid ? s_wave[w] : 0u;
+      chunk += s_wave[w];
+    }
+    if (s < nseg)
+      segoff[img * nseg + s] = carry + before + incl - v;
+    carry += chunk;
+    __syncthreads();
+  }
+  if (tid == 0)
+    sizes[img] = carry - 2u;  // no marker after the last segment
+}
+
+// ---- k_jpeg_assemble ---------------------------------------------------------------------------------------------------
+struct AsmArgs {
+  const u32* seglen;
+  const u32* segoff;
+  const u8* slots;
+  u8* out;
+  size_t out_stride;
+  int nseg;
+  u32 slot;
+};
+
+__global__ void __launch_bounds__(256) k_jpeg_assemble(const AsmArgs a) {
+  const int seg = blockIdx.x;
+  const size_t img = blockIdx.y;
+  const size_t k = img * a.nseg + seg;
+  const u32 len = a.seglen[k];
+  const u8* src = a.slots + k * a.slot;
+  u8* dst = a.out + img * a.out_stride + a.segoff[k];
+  for (u32 i = 4 * threadIdx.x; i < len; i += 4 * 256) {
+    const u32 v = *(const u32*)(src + i);  // slots are 16-byte aligned and a multiple of 16 long
+    const u32 n = min(4u, len - i);
+#pragma unroll
+    for (u32 j = 0; j < 4; ++j)
+      if (j < n)
+        dst[i + j] = (u8)(v >> (8 * j));
+  }
+  if (threadIdx.x == 0 && seg + 1 < a.nseg) {
+    dst[len] = 0xFF;
+    dst[len + 1] = (u8)(0xD0 + (seg & 7));
+  }
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------------
+void put16(u8* p, int v) {
+  p[0] = (u8)(v >> 8);
+  p[1] = (u8)v;
+}
+
+size_t write_header(int w, int h, const vali_jpeg_params* p, u8* o) {
+  size_t n = 0;
+  auto seg = [&](int marker, int payload) {
+    o[n] = 0xFF, o[n + 1] = (u8)marker;
+    put16(o + n + 2, payload + 2);
+    n += 4;
+  };
+  o[n++] = 0xFF, o[n++] = 0xD8;
+  static const u8 jfif[14] = {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+  seg(0xE0, 14);
+  memcpy(o + n, jfif, 14), n += 14;
+  seg(0xDB, 2 * 65);
+  for (int t = 0; t < 2; ++t) {
+    o[n++] = (u8)t;
+    for (int k = 0; k < 64; ++k)
+      o[n++] = p->qtable[t][kZigzag[k]];
+  }
+  seg(0xC0, 15);
+  o[n++] = 8;
+  put16(o + n, h), n += 2;
+  put16(o + n, w), n += 2;
+  const u8 comps[10] = {3, 1, (u8)((p->h_samp << 4) | p->v_samp), 0, 2, 0x11, 1, 3, 0x11, 1};
+  memcpy(o + n, comps, 10), n += 10;
+  int dht = 0;
+  for (int t = 0; t < 4; ++t)
+    dht += 17 + kHuff[t].nvals;
+  seg(0xC4, dht);
+  static const u8 cls_id[4] = {0x00, 0x10, 0x01, 0x11};
+  for (int t = 0; t < 4; ++t) {
+    o[n++] = cls_id[t];
+    memcpy(o + n, kHuff[t].bits, 16), n += 16;
+    memcpy(o + n, kHuff[t].vals, kHuff[t].nvals), n += kHuff[t].nvals;
+  }
+  seg(0xDD, 2);
+  put16(o + n, p->restart_interval), n += 2;
+  seg(0xDA, 10);
+  const u8 sos[10] = {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
+  memcpy(o + n, sos, 10), n += 10;
+  return n;
+}
+
+constexpr size_t kHeaderMax = 1024;
+
+// jcdctmgr compute_reciprocal of the divisor 8 q
+void reciprocal(int q, u32* recip, u32* corr_shift) {
+  const u32 d = 8u * (u32)q;
+  int b = 31 - __builtin_clz(d);
+  int r = 16 + b;
+  u32 fq = (u32)((1ull << r) / d), fr = (u32)((1ull << r) % d), c = d / 2;
+  if (fr == 0) {
+    fq >>= 1;
+    --r;
+  } else if (fr <= d / 2) {
+    ++c;
+  } else {
+    ++fq;
+  }
+  *recip = fq;
+  *corr_shift = c | ((u32)r << 16);
+}
+
+} // namespace
+} // namespace vali
+
+using namespace vali;
+
+extern "C" {
+
+int vali_jpeg_params_init(int quality, int format, vali_jpeg_params* out) {
+  VALI_REQUIRE(out, "null output");
+  int H, V;
+  if (!jpeg_sampling(format, &H, &V))
+    return fail(VALI_ERR_UNSUPPORTED, "%s: format %d cannot be encoded", __func__, format);
+  memset(out, 0, sizeof(*out));
+  const int q = quality < 1 ? 1 : quality > 100 ? 100 : quality;
+  const int scale = q < 50 ? 5000 / q : 200 - 2 * q;  // jpeg_quality_scaling
+  for (int k = 0; k < 64; ++k) {
+    const int l = (kLumaQ[k] * scale + 50) / 100, c = (kChromaQ[k] * scale + 50) / 100;
+    out->qtable[0][k] = (uint8_t)(l < 1 ? 1 : l > 255 ? 255 : l);  // force_baseline
+    out->qtable[1][k] = (uint8_t)(c < 1 ? 1 : c > 255 ? 255 : c);
+  }
+  out->quality = q;
+  out->format = format;
+  out->h_samp = H;
+  out->v_samp = V;
+  out->restart_interval = kSegBlocks / (H * V + 2);
+  return VALI_OK;
+}
+
+int vali_jpeg_header(int width, int height, const vali_jpeg_params* params, uint8_t* out, size_t cap, size_t* len) {
+  VALI_REQUIRE(len, "null length");
+  JpegGeom g;
+  const int rc = jpeg_geom(__func__, 1, width, height, params, &g);
+  if (rc != VALI_OK)
+    return rc;
+  u8 buf[kHeaderMax];
+  const size_t n = write_header(width, height, params, buf);
+  *len = n;
+  if (!out)
+    return VALI_OK;
+  VALI_REQUIRE(cap >= n, "capacity below the header length");
+  memcpy(out, buf, n);
+  return VALI_OK;
+}
+
+int vali_jpeg_workspace_size(int n, int width, int height, const vali_jpeg_params* params, size_t* bytes) {
+  VALI_REQUIRE(bytes, "null output");
+  JpegGeom g;
+  const int rc = jpeg_geom(__func__, n, width, height, params, &g);
+  if (rc != VALI_OK)
+    return rc;
+  *bytes = jpeg_ws_bytes(g, n);
+  return VALI_OK;
+}
+
+int vali_jpeg_stream_capacity(int width, int height, const vali_jpeg_params* params, size_t* bytes) {
+  VALI_REQUIRE(bytes, "null output");
+  JpegGeom g;
+  const int rc = jpeg_geom(__func__, 1, width, height, params, &g);
+  if (rc != VALI_OK)
+    return rc;
+  *bytes = (size_t)g.nseg * (g.slot + 2);
+  return VALI_OK;
+}
+
+int vali_jpeg_encode_batch(const vali_surface* d_src, int n, int width, int height, int format,
+                           const vali_jpeg_params* params, void* workspace, size_t ws_bytes, uint8_t* d_out,
+                           size_t out_stride, uint32_t* d_sizes, vali_stream_t stream) {
+  VALI_REQUIRE(d_src && params && workspace && d_out && d_sizes, "null argument");
+  VALI_REQUIRE(params->format == format, "params were made for another format");
+  JpegGeom g;
+  int rc = jpeg_geom(__func__, n, width, height, params, &g);
+  if (rc != VALI_OK)
+    return rc;
+  VALI_REQUIRE((((uintptr_t)workspace) & 255) == 0, "workspace not 256-byte aligned");
+  VALI_REQUIRE(ws_bytes >= jpeg_ws_bytes(g, n), "workspace below vali_jpeg_workspace_size");
+  VALI_REQUIRE(out_stride >= (size_t)g.nseg * (g.slot + 2), "out_stride below vali_jpeg_stream_capacity");
+  if (n == 0)
+    return VALI_OK;
+
+  u8* ws = (u8*)workspace;
+  FdctArgs f = {};
+  f.d_src = d_src;
+  f.coef = (int16_t*)ws;
+  f.H = g.H, f.V = g.V, f.HV = g.H * g.V, f.bpm = g.bpm, f.mcux = g.mcux, f.nblocks = g.nblocks;
+  for (int c = 0; c < 3; ++c)
+    f.cw[c] = g.cw[c], f.ch[c] = g.ch[c], f.bw[c] = g.bw[c], f.bh[c] = g.bh[c];
+  for (int t = 0; t < 2; ++t)
+    for (int k = 0; k < 64; ++k)
+      reciprocal(params->qtable[t][k], &f.recip[t][k], &f.corr_shift[t][k]);
+  HuffArgs hf = {(const int16_t*)ws, (u32*)(ws + g.len_at), ws + g.slot_at, g.nblocks, g.nseg, g.bpm, g.H * g.V,
+                 g.bps, (u32)g.slot};
+  AsmArgs as = {(const u32*)(ws + g.len_at), (const u32*)(ws + g.off_at), ws + g.slot_at, d_out, out_stride, g.nseg,
+                (u32)g.slot};
+
+  hipStream_t s = as_stream(stream);
+  VALI_ENTRY(s);
+  const dim3 fgrid((g.nblocks + 255) / 256, n);
+  switch (format) {
+  case VALI_FMT_RGB:
+    hipLaunchKernelGGL(k_jpeg_fdct<SRC_RGB>, fgrid, dim3(256), 0, s, f);
+    break;
+  case VALI_FMT_BGR:
+    hipLaunchKernelGGL(k_jpeg_fdct<SRC_BGR>, fgrid, dim3(256), 0, s, f);
+    break;
+  case VALI_FMT_RGB_PLANAR:
+    hipLaunchKernelGGL(k_jpeg_fdct<SRC_RGB_PLANAR>, fgrid, dim3(256), 0, s, f);
+    break;
+  default:
+    hipLaunchKernelGGL(k_jpeg_fdct<SRC_YUV>, fgrid, dim3(256), 0, s, f);
+    break;
+  }
+  VALI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_jpeg_huff, dim3(g.nseg, n), dim3(64), 0, s, hf);
+  VALI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_jpeg_offsets, dim3(n), dim3(256), 0, s, (const u32*)(ws + g.len_at), (u32*)(ws + g.off_at),
+                     (u32*)d_sizes, g.nseg);
+  VALI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_jpeg_assemble, dim3(g.nseg, n), dim3(256), 0, s, as);
+  VALI_LAUNCH_CHECK();
+  return VALI_OK;
+}
+
+} // extern "C"

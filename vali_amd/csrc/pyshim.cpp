@@ -49,6 +49,10 @@ struct PreprocParams {
   vali_preproc_params p;
 };
 
+struct JpegParams {
+  vali_jpeg_params p;
+};
+
 vali_roi to_roi(const std::array<int32_t, 8>& v) {
   vali_roi r;
   r.src_x = v[0]; r.src_y = v[1]; r.src_w = v[2]; r.src_h = v[3];
@@ -498,6 +502,51 @@ PYBIND11_MODULE(_vali_shim, m) {
           return vali_nv12_preproc_roi_batch((const vali_surface*)P(d_src), (const vali_surface*)P(d_dst),
                                              (const vali_roi*)P(d_roi), n, dst_width, dst_height, dst_format, &p.p,
                                              pad ? 1 : 0, pad_rgb.data(), P(stream));
+        },
+        py::call_guard<py::gil_scoped_release>());
+
+  // ---- JPEG: host-side parameters / header / sizes, then the batched encoder -----------------------------------
+  py::class_<JpegParams>(m, "JpegParams")
+      .def_property_readonly("quality", [](const JpegParams& j) { return j.p.quality; })
+      .def_property_readonly("format", [](const JpegParams& j) { return j.p.format; })
+      .def_property_readonly("h_samp", [](const JpegParams& j) { return j.p.h_samp; })
+      .def_property_readonly("v_samp", [](const JpegParams& j) { return j.p.v_samp; })
+      .def_property("restart_interval", [](const JpegParams& j) { return j.p.restart_interval; },
+                    [](JpegParams& j, int r) { j.p.restart_interval = r; })
+      .def_property_readonly("qtable", [](const JpegParams& j) {
+        std::vector<std::vector<int>> t(2, std::vector<int>(64));
+        for (int i = 0; i < 2; ++i)
+          for (int k = 0; k < 64; ++k)
+            t[i][k] = j.p.qtable[i][k];
+        return t;
+      });
+  m.def("jpeg_params_init", [](int quality, int format) {
+    JpegParams j;
+    check(vali_jpeg_params_init(quality, format, &j.p), "vali_jpeg_params_init");
+    return j;
+  });
+  m.def("jpeg_header", [](int width, int height, const JpegParams& j) {
+    size_t len = 0;
+    check(vali_jpeg_header(width, height, &j.p, nullptr, 0, &len), "vali_jpeg_header");
+    std::string out(len, '\0');
+    check(vali_jpeg_header(width, height, &j.p, (uint8_t*)&out[0], out.size(), &len), "vali_jpeg_header");
+    return py::bytes(out);
+  });
+  m.def("jpeg_workspace_size", [](int n, int width, int height, const JpegParams& j) {
+    size_t bytes = 0;
+    check(vali_jpeg_workspace_size(n, width, height, &j.p, &bytes), "vali_jpeg_workspace_size");
+    return bytes;
+  });
+  m.def("jpeg_stream_capacity", [](int width, int height, const JpegParams& j) {
+    size_t bytes = 0;
+    check(vali_jpeg_stream_capacity(width, height, &j.p, &bytes), "vali_jpeg_stream_capacity");
+    return bytes;
+  });
+  m.def("jpeg_encode_batch",
+        [](uintptr_t d_src, int n, int width, int height, int format, const JpegParams& j, uintptr_t workspace,
+           size_t ws_bytes, uintptr_t d_out, size_t out_stride, uintptr_t d_sizes, uintptr_t stream) {
+          return vali_jpeg_encode_batch((const vali_surface*)P(d_src), n, width, height, format, &j.p, P(workspace),
+                                        ws_bytes, (uint8_t*)P(d_out), out_stride, (uint32_t*)P(d_sizes), P(stream));
         },
         py::call_guard<py::gil_scoped_release>());
 
