@@ -356,6 +356,71 @@ VALI_API int vali_jpeg_encode_batch(const vali_surface* d_src, int n, int width,
                                     const vali_jpeg_params* params, void* workspace, size_t ws_bytes, uint8_t* d_out,
                                     size_t out_stride, uint32_t* d_sizes, vali_stream_t stream);
 
+/* ---- JPEG: baseline sequential decoder ----------------------------------------------------
+ *
+ * Definition: libjpeg-turbo's default decompression, bit for bit (tests/jpeg_decode_model.py restates it):
+ *   - Huffman decoding; a DC prediction per component that restarts with every restart segment;
+ *   - dequantisation, accurate integer IDCT (jidctint "islow"), the post-IDCT range-limit table of jdmaster
+ *     including its wrap of out-of-range values (index & 1023);
+ *   - RGB outputs: fancy upsampling of chroma (h2v1 / h2v2 triangle filters when the chroma width exceeds 2,
+ *     replication otherwise; h1v2 triangle filter), rows replicated at the top and bottom of the image, then
+ *     jdcolor's fixed-point ycc_rgb_convert.  Grayscale files give R = G = B = Y.
+ * Supported input: SOF0, or SOF1 with 8-bit samples; Huffman coding; one interleaved scan of 1 or 3 components;
+ * luma sampling (H, V) in {(1,1), (2,1), (1,2), (2,2)} with chroma 1x1; any restart interval; 8- or 16-bit DQT.
+ * Everything else is VALI_ERR_UNSUPPORTED from vali_jpeg_parse, with the reason in vali_last_error().
+ *
+ * Corrupt entropy data fails the image (status != 0); it never makes a kernel read or write outside the call's
+ * buffers.  Corrupt means: an invalid Huffman code, a run past coefficient 63, a code word that runs past the end
+ * of its restart segment, a segment that ends before its last MCU, a byte 0xFF followed by anything but 0x00 or
+ * the expected RSTn, or a number of RSTn markers other than (segments - 1).
+ */
+/* Huffman decode table of one component and class: a 9-bit lookahead plus maxcode / valoff for longer codes */
+typedef struct vali_jpeg_huff {
+  uint16_t look[512];  /* next 9 bits -> (code length << 8) | symbol; 0 = the code is longer than 9 bits        */
+  int32_t maxcode[18]; /* largest code of length l (1..16), -1 when there is none; [0] and [17] unused          */
+  int32_t valoff[18];  /* symbol index of code c of length l = c + valoff[l]                                   */
+  uint8_t vals[256];   /* HUFFVAL                                                                              */
+} vali_jpeg_huff;      /* 1424 bytes */
+
+typedef struct vali_jpeg_info {
+  int32_t width, height;
+  int32_t components;       /* 1 (grayscale) or 3 (YCbCr)                                                   */
+  int32_t h_samp, v_samp;   /* luma sampling factors (chroma is 1x1); 1x1 for grayscale                     */
+  int32_t restart_interval; /* MCUs per restart segment from DRI; 0 = none                                  */
+  int32_t mcux, mcuy;       /* MCUs per row / per column                                                    */
+  int32_t blocks_per_mcu;   /* h_samp * v_samp + 2, or 1 for grayscale                                      */
+  int32_t segments;         /* restart segments of the scan (1 without restart markers)                     */
+  uint64_t data_offset;     /* first byte of the entropy-coded data: in the file (vali_jpeg_parse), in the
+                               batch's data buffer (vali_jpeg_decode_batch -- the caller sets it)             */
+  uint64_t data_len;        /* its length in bytes, restart markers included, up to the next other marker    */
+  uint16_t qtable[3][64];   /* quantisation table of each component, natural order                         */
+  vali_jpeg_huff dc[3], ac[3];
+} vali_jpeg_info;           /* 8984 bytes */
+
+/* host only: walks the markers of a whole file, checks them (an oversubscribed DHT and the all-ones code are
+ * refused) and fills *out.  VALI_ERR_UNSUPPORTED for what the decoder does not cover, VALI_ERR_INVALID_ARG for a
+ * malformed header; the reason is in vali_last_error() */
+VALI_API int vali_jpeg_parse(const uint8_t* data, size_t len, vali_jpeg_info* out);
+/* device workspace of a call on these n files, for every content of their entropy data */
+VALI_API int vali_jpeg_decode_workspace_size(const vali_jpeg_info* infos, int n, size_t* bytes);
+/*
+ * Decodes n (0..65535) files of any sizes and samplings in one call.  infos: the files' infos in host memory;
+ * d_infos: the same array in device memory.  d_data: device buffer holding every file's entropy-coded data at
+ * its data_offset.  d_dst: DEVICE array of n destination descriptors of `format` and of each file's size:
+ *   VALI_FMT_RGB, VALI_FMT_BGR, VALI_FMT_RGB_PLANAR   any file;
+ *   VALI_FMT_Y                                          any file: the luma component;
+ *   VALI_FMT_YUV444 / YUV422 / YUV420 / NV12            files of exactly that sampling (4:2:x: even sizes): the
+ *                                                       component planes cropped to the image, no resampling.
+ * d_status[i] (device int32) = 0 when file i decoded, nonzero when its entropy data is corrupt or its descriptor
+ * does not match its info; then nothing of it is written.  Only the image area of each destination is written.
+ * workspace: ws_bytes >= vali_jpeg_decode_workspace_size, device memory, 256-byte aligned.  A fixed number of
+ * launches per format, whatever n and the data; nothing is allocated and nothing synchronises, so the call can be
+ * captured into a graph and replayed on new data of the same layout.
+ */
+VALI_API int vali_jpeg_decode_batch(const vali_jpeg_info* infos, const vali_jpeg_info* d_infos, int n,
+                                    const uint8_t* d_data, int format, const vali_surface* d_dst, void* workspace,
+                                    size_t ws_bytes, int32_t* d_status, vali_stream_t stream);
+
 /* ---- UD: chroma upsample + resize (+ YUV->RGB) in one pass ---------------------- */
 
 /*

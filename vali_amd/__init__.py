@@ -11,8 +11,8 @@ import sys as _sys
 _BUILDING = "vali_amd.build" in getattr(_sys, "orig_argv", [])
 if not _BUILDING:
     from ._native import shim as _shim  # noqa: F401  (fails loudly if the HIP library is absent)
-    from .codecs import (NvJpegEncodeContext, PacketData, PyDecoder, PyFrameConverter, PyNvEncoder, PyNvJpegEncoder,
-                         SeekContext, SetFFMpegLogLevel, StreamParams)
+    from .codecs import (JpegInfo, NvJpegEncodeContext, PacketData, PyDecoder, PyFrameConverter, PyNvEncoder,
+                         PyNvJpegDecoder, PyNvJpegEncoder, SeekContext, SetFFMpegLogLevel, StreamParams)
     from .enums import (ColorRange, ColorSpace, ColorspaceConversionContext, DecodeMode, DLDeviceType, FfmpegLogLevel,
                         Interpolation, PixelFormat, TaskExecDetails, TaskExecInfo, TaskExecStatus, export_values)
     from .runtime import CudaStreamEvent, GetNumGpus, HipResMgr, StreamCapture

@@ -18,6 +18,8 @@ offline.  What IS provided so pipelines written against python_vali keep running
                  ndarray -> upload -> kernel -> download.  It is NOT a CPU code path.
 * PyNvJpegEncoder -- the reference's JPEG encoder API: backend="cpu" (default) downloads and compresses with Pillow;
                  backend="hip" encodes baseline JPEG on the GPU (vali_jpeg_encode_batch).
+* PyNvJpegDecoder -- baseline JPEG decoded on the GPU into Surfaces (vali_jpeg_decode_batch): RGB / BGR / RGB_PLANAR / Y
+                 from any supported file, YUV444 / YUV422 / YUV420 / NV12 from files of that sampling.
 * PyNvEncoder  -- the reference's video encoder API (src/python_vali/src/PyNvEncoder.cpp:388-630) as "download + CPU
                  FFmpeg": the surface is downloaded on the encoder's stream and handed to a libavcodec encoder through
                  PyAV (libx264 / libx265 by default); raises RuntimeError only when PyAV is not importable.
@@ -889,3 +891,223 @@ class PyNvJpegEncoder:
                 buffers[i] = buf
             shim.stream_sync(g, s)
         return buffers, TaskExecInfo.SUCCESS
+
+
+class JpegInfo:
+    """What PyNvJpegDecoder.Info reports about a file: size, components, sampling ("444", "422", "420", "440" or
+    "gray") and restart interval (0 = no restart markers)."""
+
+    __slots__ = ("width", "height", "components", "sampling", "restart_interval")
+
+    def __init__(self, width, height, components, sampling, restart_interval):
+        self.width, self.height, self.components = int(width), int(height), int(components)
+        self.sampling, self.restart_interval = sampling, int(restart_interval)
+
+    def __repr__(self) -> str:
+        return "JpegInfo(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.__slots__) + ")"
+
+
+_SAMPLING_NAMES = {(1, 1): "444", (2, 1): "422", (2, 2): "420", (1, 2): "440"}
+# formats a file of each sampling decodes to without resampling
+_RAW_FORMATS = {F.YUV444: "444", F.YUV422: "422", F.YUV420: "420", F.NV12: "420"}
+_DECODE_FORMATS = (F.RGB, F.BGR, F.RGB_PLANAR, F.Y, F.YUV444, F.YUV422, F.YUV420, F.NV12)
+
+
+def _as_u8(buf) -> np.ndarray:
+    if isinstance(buf, np.ndarray):
+        if buf.dtype != np.uint8:
+            raise TypeError("PyNvJpegDecoder: numpy inputs must be uint8")
+        return np.ascontiguousarray(buf).reshape(-1)
+    if isinstance(buf, (bytes, bytearray, memoryview)):
+        return np.frombuffer(buf, np.uint8)
+    raise TypeError("PyNvJpegDecoder: inputs are bytes, bytearray or uint8 numpy arrays")
+
+
+def _sos_end(a: np.ndarray) -> int:
+    """byte offset just past the SOS segment (the end of the header), or -1 when the markers do not get there"""
+    i, n = 2, a.size
+    while i + 4 <= n:
+        if a[i] != 0xFF:
+            return -1
+        while i < n and a[i] == 0xFF:
+            i += 1
+        if i + 3 > n:
+            return -1
+        marker, length = int(a[i]), (int(a[i + 1]) << 8) | int(a[i + 2])
+        i += 1 + length
+        if marker == 0xDA:
+            return i if i <= n else -1
+        if marker in (0xD8, 0xD9) or 0xD0 <= marker <= 0xD7:
+            return -1
+    return -1
+
+
+def _entropy_len(a: np.ndarray, start: int) -> int:
+    """vali_jpeg_parse's rule: the entropy data runs up to the first FF that starts no stuffed byte and no RSTn"""
+    body = a[start:]
+    ff = np.flatnonzero(body[:-1] == 0xFF)
+    nxt = body[ff + 1]
+    stop = ff[(nxt != 0) & ((nxt < 0xD0) | (nxt > 0xD7))]
+    return int(stop[0]) if stop.size else body.size
+
+
+class PyNvJpegDecoder:
+    """Baseline JPEG decode on the GPU into Surfaces (vali_jpeg_decode_batch, include/vali_hip.h).  The output is
+    libjpeg-turbo's default decompression bit for bit: RGB / BGR / RGB_PLANAR through fancy upsampling and jdcolor's
+    YCbCr -> RGB, Y as the luma component, and YUV444 / YUV422 / YUV420 / NV12 as the component planes of a file of
+    exactly that sampling.  Files of different sizes and samplings go through one call.
+
+    Inputs are bytes, bytearray or uint8 numpy arrays.  Headers are parsed on the host and cached by their bytes
+    (repeated MJPEG-style frames with one header are parsed once); every call makes one host-to-device copy of
+    the infos, the destination descriptors and the concatenated entropy data through a pinned staging buffer."""
+
+    def __init__(self, gpu_id: int, stream=None):
+        self._gpu_id = int(gpu_id)
+        self._stream = int(stream) if stream is not None else HipResMgr.Instance().GetStream(self._gpu_id)
+        self._headers = {}          # header bytes -> shim.JpegInfo of its file
+        self._dev = {}              # name -> (_DeviceMem, bytes)
+        self._pin = None            # (pointer, bytes) of the pinned staging buffer
+        self.last_status = []       # per-file status of the last Run / RunInto (0 = decoded)
+
+    Stream = property(lambda self: self._stream)
+
+    def __del__(self):
+        pin = getattr(self, "_pin", None)
+        if pin is not None:
+            try:
+                shim.host_free(self._gpu_id, pin[0])
+            except Exception:
+                pass
+
+    # ---- host side ---------------------------------------------------------------------------------------------------
+    def _parse(self, a: np.ndarray):
+        """shim.JpegInfo of one file, from the cache when its header was seen before; ValueError when unsupported"""
+        end = _sos_end(a)
+        key = a[:end].tobytes() if end > 0 else None
+        cached = self._headers.get(key) if key is not None else None
+        if cached is None:
+            info = shim.jpeg_parse(a)
+            if key is not None:
+                if len(self._headers) >= 256:
+                    self._headers.clear()
+                self._headers[key] = info.copy()
+            return info
+        info = cached.copy()
+        info.data_len = _entropy_len(a, end)
+        if end + info.data_len < a.size:                 # what follows must be EOI, as vali_jpeg_parse checks
+            j = end + info.data_len
+            while j < a.size and a[j] == 0xFF:
+                j += 1
+            if j < a.size and a[j] != 0xD9:
+                return shim.jpeg_parse(a)                # raises with the parser's reason
+        return info
+
+    @staticmethod
+    def _public(info) -> JpegInfo:
+        samp = "gray" if info.components == 1 else _SAMPLING_NAMES[(info.h_samp, info.v_samp)]
+        return JpegInfo(info.width, info.height, info.components, samp, info.restart_interval)
+
+    def Info(self, data) -> JpegInfo:
+        """host only: the file's size, components, sampling and restart interval; ValueError (with the parser's
+        reason) for a file the decoder does not support"""
+        return self._public(self._parse(_as_u8(data)))
+
+    # ---- device buffers ------------------------------------------------------------------------------------------------
+    def _grow(self, name: str, need: int) -> int:
+        mem = self._dev.get(name)
+        if mem is None or mem[1] < need:
+            self._dev.pop(name, None)
+            mem = (_DeviceMem(shim.mem_alloc(self._gpu_id, need), self._gpu_id), need)
+            self._dev[name] = mem
+        return mem[0].ptr
+
+    def _staging(self, need: int) -> np.ndarray:
+        import ctypes
+
+        if self._pin is None or self._pin[1] < need:
+            if self._pin is not None:
+                shim.host_free(self._gpu_id, self._pin[0])
+                self._pin = None
+            size = max(need, 1 << 20)
+            self._pin = (shim.host_alloc(self._gpu_id, size), size)
+        return np.ctypeslib.as_array((ctypes.c_uint8 * self._pin[1]).from_address(self._pin[0]))
+
+    # ---- decode ----------------------------------------------------------------------------------------------------------
+    def Run(self, buffers, pixel_format: PixelFormat = F.RGB) -> Tuple[list, TaskExecInfo]:
+        """decodes every buffer into a new Surface of `pixel_format`: (surfaces, SUCCESS), or ([], FAIL) when any
+        file is unsupported, does not fit the format or is corrupt (all or nothing)"""
+        fmt = PixelFormat(pixel_format)
+        arrays = [_as_u8(b) for b in buffers]
+        try:
+            infos = [self._parse(a) for a in arrays]
+        except ValueError:
+            return [], TaskExecInfo.FAIL
+        surfaces = [Surface.Make(fmt, i.width, i.height, self._gpu_id) for i in infos]
+        ok, info = self._run(arrays, infos, surfaces)
+        return (surfaces, info) if ok else ([], info)
+
+    def RunInto(self, buffers, surfaces) -> Tuple[bool, TaskExecInfo]:
+        """decodes into surfaces the caller holds (one per buffer, of the file's size, all of one format)"""
+        arrays = [_as_u8(b) for b in buffers]
+        surfaces = list(surfaces)
+        if len(surfaces) != len(arrays):
+            return False, TaskExecInfo.INVALID_INPUT
+        try:
+            infos = [self._parse(a) for a in arrays]
+        except ValueError:
+            return False, TaskExecInfo.FAIL
+        return self._run(arrays, infos, surfaces)
+
+    def _run(self, arrays, infos, surfaces) -> Tuple[bool, TaskExecInfo]:
+        self.last_status = []
+        n = len(arrays)
+        if n == 0:
+            return True, TaskExecInfo.SUCCESS
+        fmt = surfaces[0].Format if surfaces[0] is not None else None
+        if fmt not in _DECODE_FORMATS:
+            return False, TaskExecInfo.INVALID_INPUT
+        for s, i in zip(surfaces, infos):
+            if s is None or s.IsEmpty or s.Format != fmt or (s.Width, s.Height) != (i.width, i.height):
+                return False, TaskExecInfo.INVALID_INPUT
+            if fmt in _RAW_FORMATS and self._public(i).sampling != _RAW_FORMATS[fmt]:
+                return False, TaskExecInfo.INVALID_INPUT
+            if fmt in (F.YUV420, F.NV12) and (i.width | i.height) & 1 or fmt == F.YUV422 and i.width & 1:
+                return False, TaskExecInfo.INVALID_INPUT
+        # staging: [infos | descriptors | entropy data], one H2D copy
+        isz, dsz = shim.JPEG_INFO_SIZE, shim.SURFACE_DESC_SIZE
+        data_at = -(-(n * (isz + dsz)) // 256) * 256
+        offsets, o = [], data_at
+        for a, i in zip(arrays, infos):
+            offsets.append(o)
+            o += -(-int(i.data_len) // 16) * 16
+        total = max(o, data_at + 16)
+        stage = self._staging(total)
+        for k, (a, i) in enumerate(zip(arrays, infos)):
+            start, ln = int(i.data_offset), int(i.data_len)
+            stage[offsets[k]:offsets[k] + ln] = a[start:start + ln]
+        dev_infos = []
+        for k, i in enumerate(infos):
+            d = i.copy()
+            d.data_offset = offsets[k] - data_at
+            dev_infos.append(d)
+            stage[k * isz:(k + 1) * isz] = np.frombuffer(d.tobytes(), np.uint8)
+        for k, s in enumerate(surfaces):
+            stage[n * isz + k * dsz:n * isz + (k + 1) * dsz] = np.frombuffer(s.desc().tobytes(), np.uint8)
+        g, st = self._gpu_id, self._stream
+        ws_bytes = shim.jpeg_decode_workspace_size(dev_infos)
+        ws = self._grow("ws", ws_bytes)
+        buf = self._grow("buf", total)
+        d_status = self._grow("status", 4 * n)
+        shim.memcpy2d_async(g, buf, total, self._pin[0], total, total, 1, 0, st)
+        rc = shim.jpeg_decode_batch(dev_infos, buf, buf + data_at, int(fmt), buf + n * isz, ws, self._dev["ws"][1],
+                                    d_status, st)
+        if rc != 0:
+            shim.stream_sync(g, st)
+            return False, TaskExecInfo.FAIL
+        status = np.zeros(n, np.int32)
+        shim.memcpy2d_async(g, status.ctypes.data, 4 * n, d_status, 4 * n, 4 * n, 1, 1, st)
+        shim.stream_sync(g, st)
+        self.last_status = [int(v) for v in status]
+        if status.any():
+            return False, TaskExecInfo.FAIL
+        return True, TaskExecInfo.SUCCESS

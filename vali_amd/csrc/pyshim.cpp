@@ -53,6 +53,10 @@ struct JpegParams {
   vali_jpeg_params p;
 };
 
+struct JpegInfo {
+  vali_jpeg_info f;
+};
+
 vali_roi to_roi(const std::array<int32_t, 8>& v) {
   vali_roi r;
   r.src_x = v[0]; r.src_y = v[1]; r.src_w = v[2]; r.src_h = v[3];
@@ -549,6 +553,65 @@ PYBIND11_MODULE(_vali_shim, m) {
                                         ws_bytes, (uint8_t*)P(d_out), out_stride, (uint32_t*)P(d_sizes), P(stream));
         },
         py::call_guard<py::gil_scoped_release>());
+
+  // ---- JPEG decoder: host-side parser and sizes, then the batched decoder --------------------------------------
+  py::class_<JpegInfo>(m, "JpegInfo")
+      .def_property_readonly("width", [](const JpegInfo& j) { return j.f.width; })
+      .def_property_readonly("height", [](const JpegInfo& j) { return j.f.height; })
+      .def_property_readonly("components", [](const JpegInfo& j) { return j.f.components; })
+      .def_property_readonly("h_samp", [](const JpegInfo& j) { return j.f.h_samp; })
+      .def_property_readonly("v_samp", [](const JpegInfo& j) { return j.f.v_samp; })
+      .def_property_readonly("restart_interval", [](const JpegInfo& j) { return j.f.restart_interval; })
+      .def_property_readonly("segments", [](const JpegInfo& j) { return j.f.segments; })
+      .def_property_readonly("mcux", [](const JpegInfo& j) { return j.f.mcux; })
+      .def_property_readonly("mcuy", [](const JpegInfo& j) { return j.f.mcuy; })
+      .def_property("data_offset", [](const JpegInfo& j) { return j.f.data_offset; },
+                    [](JpegInfo& j, uint64_t v) { j.f.data_offset = v; })
+      .def_property("data_len", [](const JpegInfo& j) { return j.f.data_len; },
+                    [](JpegInfo& j, uint64_t v) { j.f.data_len = v; })
+      .def_property_readonly("qtable", [](const JpegInfo& j) {
+        std::vector<std::vector<int>> t(3, std::vector<int>(64));
+        for (int c = 0; c < 3; ++c)
+          for (int k = 0; k < 64; ++k)
+            t[c][k] = j.f.qtable[c][k];
+        return t;
+      })
+      .def("copy", [](const JpegInfo& j) { return j; })
+      .def("tobytes", [](const JpegInfo& j) { return py::bytes((const char*)&j.f, sizeof(j.f)); });
+  m.attr("JPEG_INFO_SIZE") = (int)sizeof(vali_jpeg_info);
+  m.def("jpeg_parse", [](py::buffer b) {
+    py::buffer_info info = b.request();
+    JpegInfo j;
+    check(vali_jpeg_parse((const uint8_t*)info.ptr, (size_t)(info.size * info.itemsize), &j.f), "vali_jpeg_parse");
+    return j;
+  });
+  // the status code itself (no exception): for tests that feed arbitrary headers
+  m.def("jpeg_parse_rc", [](py::buffer b) {
+    py::buffer_info info = b.request();
+    JpegInfo j;
+    std::memset(&j.f, 0, sizeof(j.f));
+    const int rc = vali_jpeg_parse((const uint8_t*)info.ptr, (size_t)(info.size * info.itemsize), &j.f);
+    return py::make_tuple(rc, j);
+  });
+  m.def("jpeg_decode_workspace_size", [](const std::vector<JpegInfo>& infos) {
+    std::vector<vali_jpeg_info> h(infos.size());
+    for (size_t i = 0; i < infos.size(); ++i)
+      h[i] = infos[i].f;
+    size_t bytes = 0;
+    check(vali_jpeg_decode_workspace_size(h.data(), (int)h.size(), &bytes), "vali_jpeg_decode_workspace_size");
+    return bytes;
+  });
+  m.def("jpeg_decode_batch",
+        [](const std::vector<JpegInfo>& infos, uintptr_t d_infos, uintptr_t d_data, int format, uintptr_t d_dst,
+           uintptr_t workspace, size_t ws_bytes, uintptr_t d_status, uintptr_t stream) {
+          std::vector<vali_jpeg_info> h(infos.size());
+          for (size_t i = 0; i < infos.size(); ++i)
+            h[i] = infos[i].f;
+          py::gil_scoped_release rel;
+          return vali_jpeg_decode_batch(h.data(), (const vali_jpeg_info*)P(d_infos), (int)h.size(),
+                                        (const uint8_t*)P(d_data), format, (const vali_surface*)P(d_dst),
+                                        P(workspace), ws_bytes, (int32_t*)P(d_status), P(stream));
+        });
 
   m.def("ud_nv12",
         [](const SurfaceDesc& src, const SurfaceDesc& dst, uintptr_t stream) {
