@@ -310,6 +310,43 @@ VALI_API int vali_nv12_preproc_roi_batch(const vali_surface* d_src, const vali_s
                                          int dst_format, const vali_preproc_params* params, int pad,
                                          const uint8_t pad_rgb[3], vali_stream_t stream);
 
+/*
+ * Regions of RGB-family sources: what a decoder gives for files that are not 4:2:0 of even size.
+ * Source VALI_FMT_RGB, VALI_FMT_BGR or VALI_FMT_RGB_PLANAR (8 bit); destination VALI_FMT_RGB_32F_PLANAR,
+ * VALI_FMT_RGB_32F, VALI_FMT_RGB, VALI_FMT_BGR or VALI_FMT_RGB_PLANAR, as for NV12.  For a crop (src_x, src_y,
+ * src_w, src_h) of the source placed at (dst_x, dst_y, dst_w, dst_h) of the destination, inside the placement:
+ *   1. q = the bilinear resize of the crop VIEW to dst_w x dst_h, channel by channel, exactly as
+ *      vali_resize(..., VALI_INTERP_LINEAR) does it for that format: scales (float)src_w / (float)dst_w and
+ *      (float)src_h / (float)dst_h, grid src = dst * scale, t0 / t1 / v by fma, round-half-even to u8; the taps
+ *      never leave the crop.  Equal sizes: q is the texel.
+ *   2. the channels are named by colour, not by position: q_R, q_G, q_B whatever the source's memory order.
+ *   3. float destinations: out_c = ((q_c / 255.0f) / div - mean[c]) / std_[c], c = R, G, B, IEEE float32 (step 3 of
+ *      vali_nv12_preproc).  8-bit destinations: the bytes q_c in the destination's memory order; div / mean / std_
+ *      are ignored.
+ * Outside the placement: the pad colour through step 3, or nothing written (pad == 0) -- the NV12 rule.
+ * There is NO colour matrix: params->csc is ignored.
+ * There is NO evenness rule: sizes, crops and placements are any integers; a rectangle is at least 1 x 1 and lies
+ * inside its surface.  The result is bit-identical to vali_resize on the views, vali_convert to the destination's
+ * layout, then step 3.
+ * roi is in host memory and checked strictly (VALI_ERR_INVALID_ARG); NULL = the whole source onto the whole
+ * destination.  Formats outside the lists: VALI_ERR_UNSUPPORTED.  Both are decided before any device is touched.
+ */
+VALI_API int vali_rgb_preproc_roi(const vali_surface* src, const vali_surface* dst, const vali_roi* roi,
+                                  const vali_preproc_params* params, int pad, const uint8_t pad_rgb[3],
+                                  vali_stream_t stream);
+/*
+ * Batched form: device arrays of n (0..65535) entries; all sources have the format src_format (their sizes may
+ * differ, they may repeat), the destinations share dst_width x dst_height and dst_format.  d_roi == NULL: every
+ * item is its whole source onto its whole destination.  Device rectangles are sanitised by clamping only:
+ *   x = clamp(x, 0, W);  w = clamp(w, 0, W - x)      (y / h likewise; the placement against the destination)
+ * An item whose crop or placement is then narrower or shorter than 1 is empty: all pad, or untouched.  Whatever
+ * the records hold, an item reads only inside src[i] and writes only inside dst[i].
+ */
+VALI_API int vali_rgb_preproc_roi_batch(const vali_surface* d_src, const vali_surface* d_dst, const vali_roi* d_roi,
+                                        int n, int src_format, int dst_width, int dst_height, int dst_format,
+                                        const vali_preproc_params* params, int pad, const uint8_t pad_rgb[3],
+                                        vali_stream_t stream);
+
 /* ---- JPEG: baseline sequential JFIF encoder ------------------------------------------------
  *
  * The reference's PyNvJpegEncoder (src/TC/src/TaskNvJpegEncode.cpp) on nvJPEG.  Definition (tests/jpeg_model.py

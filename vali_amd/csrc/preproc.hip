@@ -660,6 +660,361 @@ static int launch_preproc_roi(RoiArgs& a, int canvas_w, int canvas_h, int dst_fm
   return VALI_OK;
 }
 
+// ---- regions of RGB-family sources (RGB, BGR, RGB_PLANAR; 8 bit) ------------------------------
+// The same item as above without a colour matrix and without evenness: inside the placement
+//   q_c = the bilinear resize of view(src, crop) to dw x dh, channel by channel (resize.hip's arithmetic and grid),
+//   out = step 3 on q_R, q_G, q_B (float outputs) or the bytes themselves (8-bit outputs),
+// i.e. vali_resize(LINEAR) on the views, then the plain converters, then the normalisation.
+// A lane owns 4 px of ONE row (no chroma couples rows or columns here), so every predicate is per pixel.
+// Fetch: the two horizontal taps of a packed pixel are 6 contiguous bytes at 3 (sx + i0), any alignment: ONE
+// 8-byte load per tap row (its window slides left at the end of the SURFACE row and is shifted back in registers,
+// load_tap_pair's rule), 8 loads per lane and row instead of 48.  Planar sources take 2 bytes per plane and tap row.
+// Equal sizes, all 4 pixels inside: the 12 bytes (packed) / 3 x 4 bytes (planar) of the lane stream in as they lie.
+// A crop that is 1 pixel wide, or a packed surface narrower than the 8-byte window (< 3 px), has one or two
+// texels per row: they are gathered byte by byte into the same 6-byte form (the second texel repeats the first
+// when there is only one), so the arithmetic below never knows.
+// BGR sources differ from RGB ones by a channel swap where the colours are named (a.swap), not by a kernel.
+struct RgbRoiArgs {
+  RoiArgs r;
+  int swap;  // packed source is B G R in memory
+  int whole; // no rectangle records: every item is its whole source onto its whole destination
+};
+
+// clamp (x, w) into [0, size] (the batch form's sanitising rule for these sources: no rounding)
+__device__ __forceinline__ void roi_clamp_any(int& x, int& w, int size) {
+  size = max(size, 0);
+  x = min(max(x, 0), size);
+  w = min(max(w, 0), size - x);
+}
+
+template <bool PLANAR, int OUT, bool TALL>
+__global__ void __launch_bounds__(kBlock) k_rgb_preproc_roi(const RgbRoiArgs ar) {
+  constexpr bool kFloat = OUT == PP_F32_PLANAR || OUT == PP_F32_PACKED;
+  constexpr int kTileW = TALL ? kWave * 4 : kPpTileW;
+  typedef unsigned long long u64;
+  typedef unsigned v3u32 __attribute__((ext_vector_type(3)));
+  const RoiArgs& a = ar.r;
+  __shared__ float lut[kFloat ? 3 : 1][256];
+  u32 tile_x, tile_y, frame;
+  if (!tile_of_block(a.map, tile_x, tile_y, frame))
+    return;
+  const SurfRef s = surf_ref(load_uniform(a.d_src, a.src, frame));
+  const SurfRef d = surf_ref(load_uniform(a.d_dst, a.dst, frame));
+  const vali_roi r = load_uniform(a.d_roi, a.roi, frame);
+  int sx = r.src_x, sy = r.src_y, sw = r.src_w, sh = r.src_h;
+  int dx = r.dst_x, dy = r.dst_y, dw = r.dst_w, dh = r.dst_h;
+  if (ar.whole) {
+    sx = sy = dx = dy = 0;
+    sw = s.width; sh = s.height; dw = d.width; dh = d.height;
+  }
+  roi_clamp_any(sx, sw, s.width);
+  roi_clamp_any(sy, sh, s.height);
+  const int cw = max(d.width, 0), ch = max(d.height, 0); // the canvas
+  roi_clamp_any(dx, dw, cw);
+  roi_clamp_any(dy, dh, ch);
+  const bool empty = sw < 1 || sh < 1 || dw < 1 || dh < 1;
+
+  // does this workgroup's tile meet the placement?  (block-uniform)
+  const int rows = a.row_pairs * 2; // rows a wave walks
+  const int tx0 = tile_x * kTileW;
+  const int th = rows * (TALL ? kWavesPerBlock : 1);
+  const int ty0 = tile_y * th;
+  const bool hits = !empty && tx0 < dx + dw && tx0 + kTileW > dx && ty0 < dy + dh && ty0 + th > dy;
+  if (!hits && !a.pad)
+    return;
+  if constexpr (kFloat) {
+    if (hits) {
+      for (int e = threadIdx.x; e < 3 * 256; e += kBlock)
+        lut[e >> 8][e & 255] = preproc_step3(e & 255, e >> 8, a.prm);
+      __syncthreads();
+    }
+  }
+
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int x0 = tx0 + (TALL ? 0 : wave * kWave * 4) + lane * 4;
+  if (x0 >= cw)
+    return;
+  const int n = min(4, cw - x0);
+  bool inx[4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+    inx[p] = hits && x0 + p >= dx && x0 + p < dx + dw;
+  const bool any_x = inx[0] || inx[1] || inx[2] || inx[3];
+  const bool all_x = inx[0] && inx[1] && inx[2] && inx[3];
+  float pv[3]; // the pad colour: the normalised value (float outputs); the byte itself is padq
+  u32 padq[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    padq[c] = (a.pad_rgb >> (8 * c)) & 255u;
+    const float v = kFloat ? preproc_step3((int)padq[c], c, a.prm) : 0.0f;
+    pv[c] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); // uniform: SGPRs
+  }
+
+  // the resize geometry of view -> view (resize_tile's expressions) and the lane's column taps
+  const int sp = s.pitch[0], dp = d.pitch[0];
+  const float lsx = (float)sw / (float)max(dw, 1), lsy = (float)sh / (float)max(dh, 1);
+  const int vx0 = x0 - dx; // the lane's first pixel in view coordinates (clamped below for pixels outside)
+  const bool same = sw == dw && sh == dh; // item-uniform
+  // one or two texels per crop row: gathered byte by byte
+  const bool narrow = sw == 1 || (!PLANAR && s.width < 3);
+  float ax[4];
+  int off[4];   // byte offset of the pixel's tap window from the start of the surface row
+  int shl[4];   // packed: bits to shift the window right (it slid left at the end of the row)
+  bool edge[4]; // the coordinate sits on the crop's last column: both taps are the window's second texel
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const Lerp l = make_lerp(min(max(vx0 + p, 0), max(dw - 1, 0)), lsx, max(sw, 1));
+    const int base = max(min(l.i0, sw - 2), 0);
+    ax[p] = l.a;
+    edge[p] = l.i0 != base;
+    if constexpr (PLANAR) {
+      off[p] = sx + base;
+      shl[p] = 0;
+    } else {
+      const int want = 3 * (sx + base);
+      off[p] = max(min(want, 3 * s.width - 8), 0);
+      shl[p] = 8 * (want - off[p]);
+    }
+  }
+
+#pragma unroll 1
+  for (int it = 0; it < rows; ++it) {
+    const int y = TALL ? ty0 + it * kWavesPerBlock + wave : ty0 + it; // wave-uniform
+    if (y >= ch)
+      break;
+    const bool row_in = y >= dy && y < dy + dh;
+    const bool any = row_in && any_x, all = row_in && all_x;
+    if (!a.pad && !any)
+      continue;
+    bool in[4], wr[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      in[p] = row_in && inx[p];
+      wr[p] = p < n && (in[p] || a.pad);
+    }
+    const bool full = wr[0] && wr[1] && wr[2] && wr[3];
+    u32 q[3][4]; // [channel in the source's memory order][pixel]: the resized u8 texels
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int p = 0; p < 4; ++p) q[c][p] = 0u;
+    if (any) {
+      const int vy = y - dy;
+      if (same && all) {
+        // ---- equal sizes, all 4 pixels inside: the texels themselves (scale 1, weights 0), streamed ----
+        if constexpr (PLANAR) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const u32 w = gload_u<u32>(s.p[c] + (size_t)(sy + vy) * s.pitch[c] + sx + vx0);
+            q[c][0] = ubyte<0>(w); q[c][1] = ubyte<1>(w); q[c][2] = ubyte<2>(w); q[c][3] = ubyte<3>(w);
+          }
+        } else {
+          const v3u32 w = gload_u<v3u32>(s.p[0] + (size_t)(sy + vy) * sp + 3 * (sx + vx0));
+          q[0][0] = ubyte<0>(w.x); q[1][0] = ubyte<1>(w.x); q[2][0] = ubyte<2>(w.x); q[0][1] = ubyte<3>(w.x);
+          q[1][1] = ubyte<0>(w.y); q[2][1] = ubyte<1>(w.y); q[0][2] = ubyte<2>(w.y); q[1][2] = ubyte<3>(w.y);
+          q[2][2] = ubyte<0>(w.z); q[0][3] = ubyte<1>(w.z); q[1][3] = ubyte<2>(w.z); q[2][3] = ubyte<3>(w.z);
+        }
+      } else {
+        // ---- bilinear taps of resize_tile on the view: t0, t1 along x on the two tap rows, then along y ----
+        Lerp ly = make_lerp(min(vy, dh - 1), lsy, sh);
+        if (ly.a == 0.0f) // (wave-uniform) fma(0, t1 - t0, t0) == t0: integer ratios never fetch the second tap row
+          ly.i1 = ly.i0;
+        auto lerp3 = [](float t00, float t10, float t01, float t11, float fx, float fy) {
+          const float t0 = __builtin_fmaf(fx, t10 - t00, t00);
+          const float t1 = __builtin_fmaf(fx, t11 - t01, t01);
+          return quantize_u8(__builtin_fmaf(fy, t1 - t0, t0));
+        };
+        if constexpr (PLANAR) {
+          u32 w0[3][4], w1[3][4]; // tap row 0 / 1: texel | next texel << 8
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const uint8_t* r0 = s.p[c] + (size_t)(sy + ly.i0) * s.pitch[c];
+            const uint8_t* r1 = s.p[c] + (size_t)(sy + ly.i1) * s.pitch[c];
+            if (!narrow) {
+#pragma unroll
+              for (int p = 0; p < 4; ++p) {
+                w0[c][p] = gload_u<uint16_t>(r0 + off[p]);
+                w1[c][p] = gload_u<uint16_t>(r1 + off[p]);
+              }
+            } else {
+              const u32 b0 = gload<uint8_t>(r0 + sx), b1 = gload<uint8_t>(r1 + sx);
+#pragma unroll
+              for (int p = 0; p < 4; ++p) {
+                w0[c][p] = b0 | b0 << 8;
+                w1[c][p] = b1 | b1 << 8;
+              }
+            }
+          }
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+              const float t10 = ubyte_f32<1>(w0[c][p]), t11 = ubyte_f32<1>(w1[c][p]);
+              const float t00 = edge[p] ? t10 : ubyte_f32<0>(w0[c][p]), t01 = edge[p] ? t11 : ubyte_f32<0>(w1[c][p]);
+              q[c][p] = lerp3(t00, t10, t01, t11, ax[p], ly.a);
+            }
+        } else {
+          const uint8_t* r0 = s.p[0] + (size_t)(sy + ly.i0) * sp;
+          const uint8_t* r1 = s.p[0] + (size_t)(sy + ly.i1) * sp;
+          u64 w0[4], w1[4]; // tap row 0 / 1: the 6 bytes of the texel and its right neighbour
+          if (!narrow) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+              w0[p] = gload_u<u64>(r0 + off[p]) >> shl[p];
+              w1[p] = gload_u<u64>(r1 + off[p]) >> shl[p];
+            }
+          } else {
+            u64 n0 = 0, n1 = 0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+              const int b = 3 * sx + (k < 3 || sw >= 2 ? k : k - 3);
+              n0 |= (u64)gload<uint8_t>(r0 + b) << (8 * k);
+              n1 |= (u64)gload<uint8_t>(r1 + b) << (8 * k);
+            }
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+              w0[p] = n0;
+              w1[p] = n1;
+            }
+          }
+#pragma unroll
+          for (int p = 0; p < 4; ++p) {
+            const u32 lo0 = (u32)w0[p], hi0 = (u32)(w0[p] >> 32), lo1 = (u32)w1[p], hi1 = (u32)(w1[p] >> 32);
+            const float t10[3] = {ubyte_f32<3>(lo0), ubyte_f32<0>(hi0), ubyte_f32<1>(hi0)};
+            const float t11[3] = {ubyte_f32<3>(lo1), ubyte_f32<0>(hi1), ubyte_f32<1>(hi1)};
+            const float t00[3] = {ubyte_f32<0>(lo0), ubyte_f32<1>(lo0), ubyte_f32<2>(lo0)};
+            const float t01[3] = {ubyte_f32<0>(lo1), ubyte_f32<1>(lo1), ubyte_f32<2>(lo1)};
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+              q[c][p] = lerp3(edge[p] ? t10[c] : t00[c], t10[c], edge[p] ? t11[c] : t01[c], t11[c], ax[p], ly.a);
+          }
+        }
+      }
+    }
+    // ---- the colours by name, the pad colour where the pixel lies outside the placement ----
+    u32 qc[3][4]; // [R, G, B][pixel]
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      qc[0][p] = in[p] ? (ar.swap ? q[2][p] : q[0][p]) : padq[0];
+      qc[1][p] = in[p] ? q[1][p] : padq[1];
+      qc[2][p] = in[p] ? (ar.swap ? q[0][p] : q[2][p]) : padq[2];
+    }
+    if constexpr (kFloat) {
+      float o[3][4];
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int p = 0; p < 4; ++p) o[c][p] = in[p] ? lut[c][qc[c][p]] : pv[c];
+      if constexpr (OUT == PP_F32_PLANAR) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          uint8_t* w = d.p[c] + (u32)(y * d.pitch[c]) + (size_t)x0 * 4;
+          if (full && (((uintptr_t)w) & 15u) == 0)
+            store16f_nt(w, make_float4(o[c][0], o[c][1], o[c][2], o[c][3]));
+          else
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+              if (wr[p]) gstore<float>(w + 4 * p, o[c][p]);
+        }
+      } else {
+        uint8_t* w = d.p[0] + (u32)(y * dp) + (size_t)x0 * 12;
+        if (full && (((uintptr_t)w) & 15u) == 0) {
+          store16f(w + 0, make_float4(o[0][0], o[1][0], o[2][0], o[0][1]));
+          store16f(w + 16, make_float4(o[1][1], o[2][1], o[0][2], o[1][2]));
+          store16f(w + 32, make_float4(o[2][2], o[0][3], o[1][3], o[2][3]));
+        } else {
+#pragma unroll
+          for (int p = 0; p < 4; ++p)
+            if (wr[p]) {
+              gstore<float>(w + 12 * p, o[0][p]); gstore<float>(w + 12 * p + 4, o[1][p]); gstore<float>(w + 12 * p + 8, o[2][p]);
+            }
+        }
+      }
+    } else if constexpr (OUT == PP_U8_PLANAR) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        uint8_t* w = d.p[c] + (u32)(y * d.pitch[c]) + x0;
+        if (full)
+          gstore_u<u32>(w, qc[c][0] | qc[c][1] << 8 | qc[c][2] << 16 | qc[c][3] << 24);
+        else
+#pragma unroll
+          for (int p = 0; p < 4; ++p)
+            if (wr[p]) gstore<uint8_t>(w + p, (uint8_t)qc[c][p]);
+      }
+    } else {
+      // memory order f g l per pixel: f = R (RGB) or B (BGR), l the other one
+      const u32 (&cf)[4] = OUT == PP_U8_RGB ? qc[0] : qc[2];
+      const u32 (&cg)[4] = qc[1];
+      const u32 (&cl)[4] = OUT == PP_U8_RGB ? qc[2] : qc[0];
+      uint8_t* w = d.p[0] + (u32)(y * dp) + (size_t)x0 * 3;
+      if (full) {
+        const v3u32 wv = {cf[0] | cg[0] << 8 | cl[0] << 16 | cf[1] << 24, cg[1] | cl[1] << 8 | cf[2] << 16 | cg[2] << 24,
+                          cl[2] | cf[3] << 8 | cg[3] << 16 | cl[3] << 24};
+        gstore_u<v3u32>(w, wv);
+      } else {
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+          if (wr[p]) {
+            gstore<uint8_t>(w + 3 * p, (uint8_t)cf[p]); gstore<uint8_t>(w + 3 * p + 1, (uint8_t)cg[p]);
+            gstore<uint8_t>(w + 3 * p + 2, (uint8_t)cl[p]);
+          }
+      }
+    }
+  }
+}
+
+static int rgb_out_form(int dst_fmt) {
+  switch (dst_fmt) {
+  case VALI_FMT_RGB_32F_PLANAR: return PP_F32_PLANAR;
+  case VALI_FMT_RGB_32F: return PP_F32_PACKED;
+  case VALI_FMT_RGB: return PP_U8_RGB;
+  case VALI_FMT_BGR: return PP_U8_BGR;
+  case VALI_FMT_RGB_PLANAR: return PP_U8_PLANAR;
+  default: return -1;
+  }
+}
+
+static bool rgb_src_ok(int fmt) { return fmt == VALI_FMT_RGB || fmt == VALI_FMT_BGR || fmt == VALI_FMT_RGB_PLANAR; }
+
+static int launch_rgb_preproc_roi(RgbRoiArgs& ar, int src_fmt, int canvas_w, int canvas_h, int dst_fmt, int n,
+                                  hipStream_t stream) {
+  RoiArgs& a = ar.r;
+  const int out = rgb_out_form(dst_fmt);
+  ar.swap = src_fmt == VALI_FMT_BGR;
+  const bool planar = src_fmt == VALI_FMT_RGB_PLANAR;
+  // tile shapes and rows per wave: launch_preproc_roi's rules
+  const bool tall = canvas_w <= kWave * 4;
+  const int tile_w = tall ? kWave * 4 : kPpTileW, rows_per_pair_step = tall ? 2 * kWavesPerBlock : 2;
+  const long long tiles_x = (canvas_w + tile_w - 1) / tile_w;
+  a.row_pairs = kPpRowPairsPerWave;
+  auto tiles_y = [&](int rp) { return (canvas_h + rows_per_pair_step * rp - 1) / (rows_per_pair_step * rp); };
+  while (a.row_pairs > 1 && tiles_x * tiles_y(a.row_pairs) * n * kWavesPerBlock < 2048)
+    a.row_pairs /= 2;
+  a.map = make_tile_map((u32)tiles_x, (u32)tiles_y(a.row_pairs), (u32)n);
+  const dim3 grid = tile_grid(a.map), block(kBlock);
+#define VALI_PPR_LAUNCH(P, O, T) hipLaunchKernelGGL((k_rgb_preproc_roi<P, O, T>), grid, block, 0, stream, ar)
+#define VALI_PPR_CASE(O)                                                                     \
+  case O:                                                                                   \
+    if (planar) {                                                                           \
+      if (tall) VALI_PPR_LAUNCH(true, O, true); else VALI_PPR_LAUNCH(true, O, false);       \
+    } else {                                                                                \
+      if (tall) VALI_PPR_LAUNCH(false, O, true); else VALI_PPR_LAUNCH(false, O, false);     \
+    }                                                                                       \
+    break;
+  switch (out) {
+    VALI_PPR_CASE(PP_F32_PLANAR)
+    VALI_PPR_CASE(PP_F32_PACKED)
+    VALI_PPR_CASE(PP_U8_RGB)
+    VALI_PPR_CASE(PP_U8_BGR)
+    VALI_PPR_CASE(PP_U8_PLANAR)
+  }
+#undef VALI_PPR_CASE
+#undef VALI_PPR_LAUNCH
+  VALI_LAUNCH_CHECK();
+  return VALI_OK;
+}
+
 } // namespace vali
 
 using namespace vali;
@@ -757,6 +1112,75 @@ int vali_nv12_preproc_roi_batch(const vali_surface* d_src, const vali_surface* d
   hipStream_t s = as_stream(stream);
   VALI_ENTRY(s);
   return launch_preproc_roi(a, dst_width, dst_height, dst_format, n, s);
+}
+
+static bool rgb_roi_axis_ok(int x, int w, int size) { return x >= 0 && w >= 1 && x <= size - w; }
+
+int vali_rgb_preproc_roi(const vali_surface* src, const vali_surface* dst, const vali_roi* roi,
+                         const vali_preproc_params* params, int pad, const uint8_t pad_rgb[3], vali_stream_t stream) {
+  VALI_REQUIRE(src && dst && params, "null argument");
+  VALI_REQUIRE(!pad || pad_rgb, "null pad colour");
+  if (!rgb_src_ok(src->format))
+    return fail(VALI_ERR_UNSUPPORTED, "rgb_preproc_roi: source must be RGB, BGR or RGB_PLANAR (got %d)", src->format);
+  if (rgb_out_form(dst->format) < 0)
+    return fail(VALI_ERR_UNSUPPORTED,
+                "rgb_preproc_roi: destination must be RGB_32F[_PLANAR], RGB, BGR or RGB_PLANAR (got %d)", dst->format);
+  VALI_REQUIRE(src->width >= 1 && src->height >= 1 && dst->width >= 1 && dst->height >= 1, "empty surface");
+  VALI_REQUIRE(src->plane[0] && dst->plane[0], "null plane");
+  if (src->format == VALI_FMT_RGB_PLANAR)
+    VALI_REQUIRE(src->plane[1] && src->plane[2], "null src plane");
+  if (dst->format == VALI_FMT_RGB_32F_PLANAR || dst->format == VALI_FMT_RGB_PLANAR)
+    VALI_REQUIRE(dst->plane[1] && dst->plane[2], "null dst plane");
+  VALI_REQUIRE(planes_fit_32bit(*src) && planes_fit_32bit(*dst), "plane of 4 GiB or more");
+  const vali_roi whole = {0, 0, src->width, src->height, 0, 0, dst->width, dst->height};
+  if (!roi)
+    roi = &whole;
+  VALI_REQUIRE(rgb_roi_axis_ok(roi->src_x, roi->src_w, src->width) && rgb_roi_axis_ok(roi->src_y, roi->src_h, src->height),
+               "crop must be at least 1 x 1 and inside the source");
+  VALI_REQUIRE(rgb_roi_axis_ok(roi->dst_x, roi->dst_w, dst->width) && rgb_roi_axis_ok(roi->dst_y, roi->dst_h, dst->height),
+               "placement must be at least 1 x 1 and inside the destination");
+  RgbRoiArgs ar = {};
+  RoiArgs& a = ar.r;
+  a.src = *src;
+  a.dst = *dst;
+  a.roi = *roi;
+  a.prm = *params;
+  a.pad = pad != 0;
+  if (pad)
+    a.pad_rgb = (u32)pad_rgb[0] | (u32)pad_rgb[1] << 8 | (u32)pad_rgb[2] << 16;
+  hipStream_t s = as_stream(stream);
+  VALI_ENTRY(s);
+  return launch_rgb_preproc_roi(ar, src->format, dst->width, dst->height, dst->format, 1, s);
+}
+
+int vali_rgb_preproc_roi_batch(const vali_surface* d_src, const vali_surface* d_dst, const vali_roi* d_roi, int n,
+                               int src_format, int dst_width, int dst_height, int dst_format,
+                               const vali_preproc_params* params, int pad, const uint8_t pad_rgb[3],
+                               vali_stream_t stream) {
+  VALI_REQUIRE(d_src && d_dst && params, "null argument");
+  VALI_REQUIRE(!pad || pad_rgb, "null pad colour");
+  if (!rgb_src_ok(src_format))
+    return fail(VALI_ERR_UNSUPPORTED, "rgb_preproc_roi_batch: sources must be RGB, BGR or RGB_PLANAR (got %d)", src_format);
+  if (rgb_out_form(dst_format) < 0)
+    return fail(VALI_ERR_UNSUPPORTED,
+                "rgb_preproc_roi_batch: destination must be RGB_32F[_PLANAR], RGB, BGR or RGB_PLANAR (got %d)", dst_format);
+  VALI_REQUIRE(dst_width >= 1 && dst_height >= 1, "bad geometry");
+  VALI_REQUIRE(n >= 0 && n <= 65535, "batch size out of range (0..65535)");
+  if (n == 0)
+    return VALI_OK;
+  RgbRoiArgs ar = {};
+  RoiArgs& a = ar.r;
+  a.d_src = d_src;
+  a.d_dst = d_dst;
+  a.d_roi = d_roi;
+  ar.whole = d_roi == nullptr;
+  a.prm = *params;
+  a.pad = pad != 0;
+  if (pad)
+    a.pad_rgb = (u32)pad_rgb[0] | (u32)pad_rgb[1] << 8 | (u32)pad_rgb[2] << 16;
+  hipStream_t s = as_stream(stream);
+  VALI_ENTRY(s);
+  return launch_rgb_preproc_roi(ar, src_format, dst_width, dst_height, dst_format, n, s);
 }
 
 } // extern "C"

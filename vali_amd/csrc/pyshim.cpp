@@ -508,6 +508,21 @@ PYBIND11_MODULE(_vali_shim, m) {
                                              pad ? 1 : 0, pad_rgb.data(), P(stream));
         },
         py::call_guard<py::gil_scoped_release>());
+  m.def("rgb_preproc_roi",
+        [](const SurfaceDesc& src, const SurfaceDesc& dst, const std::array<int32_t, 8>& roi, const PreprocParams& p,
+           bool pad, const std::array<uint8_t, 3>& pad_rgb, uintptr_t stream) {
+          const vali_roi r = to_roi(roi);
+          return vali_rgb_preproc_roi(&src.s, &dst.s, &r, &p.p, pad ? 1 : 0, pad_rgb.data(), P(stream));
+        },
+        py::call_guard<py::gil_scoped_release>());
+  m.def("rgb_preproc_roi_batch",
+        [](uintptr_t d_src, uintptr_t d_dst, uintptr_t d_roi, int n, int src_format, int dst_width, int dst_height,
+           int dst_format, const PreprocParams& p, bool pad, const std::array<uint8_t, 3>& pad_rgb, uintptr_t stream) {
+          return vali_rgb_preproc_roi_batch((const vali_surface*)P(d_src), (const vali_surface*)P(d_dst),
+                                            (const vali_roi*)P(d_roi), n, src_format, dst_width, dst_height, dst_format,
+                                            &p.p, pad ? 1 : 0, pad_rgb.data(), P(stream));
+        },
+        py::call_guard<py::gil_scoped_release>());
 
   // ---- JPEG: host-side parameters / header / sizes, then the batched encoder -----------------------------------
   py::class_<JpegParams>(m, "JpegParams")

@@ -598,7 +598,7 @@ class PySurfaceUD(_SurfaceTask):
 
 # ---- PySurfacePreprocessor (new: fused inference pre-processing) -------------
 class PySurfacePreprocessor(_SurfaceTask):
-    """NV12 -> (bilinear resize to dst size) -> RGB -> float -> normalised, ONE launch.
+    """NV12, RGB, BGR or RGB_PLANAR -> (bilinear resize to dst size) -> RGB -> float -> normalised, ONE launch.
 
     The reference has no such task: its samples and tests/test_TorchSegmentation.py:176-240
     chain PySurfaceConverter NV12->RGB, RGB->RGB_32F, RGB_32F->RGB_32F_PLANAR and then run
@@ -613,7 +613,21 @@ class PySurfacePreprocessor(_SurfaceTask):
     8-bit destinations (RGB, BGR, RGB_PLANAR) give the fused PySurfaceResizer ->
     PySurfaceConverter chain (resize + colour conversion, no float stage); they require the
     identity normalisation.
+
+    RGB, BGR and RGB_PLANAR sources (what PyNvJpegDecoder gives for files that are not 4:2:0 of even size) take the
+    chain PySurfaceResizer(fmt, LINEAR) -> PySurfaceConverter to the destination's layout -> the same normalisation,
+    with the channels named by colour whatever the memory order (vali_rgb_preproc_roi, include/vali_hip.h).  There is
+    no colour matrix for them: `cc_ctx` is accepted and ignored.  Nothing about them needs to be even: sizes, crops
+    and placements are any integers, a rectangle is at least 1 x 1.
     """
+
+    _RGB_SRC = (F.RGB, F.BGR, F.RGB_PLANAR)
+    _DST = (F.RGB_32F_PLANAR, F.RGB_32F, F.RGB, F.BGR, F.RGB_PLANAR)
+
+    @staticmethod
+    def SupportedFormats() -> List[Tuple[PixelFormat, PixelFormat]]:
+        """every (source, destination) pair the task runs"""
+        return [(s, d) for s in (F.NV12,) + PySurfacePreprocessor._RGB_SRC for d in PySurfacePreprocessor._DST]
 
     def __init__(self, gpu_id: int, stream=None, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0),
                  div: float = 1.0):
@@ -637,7 +651,11 @@ class PySurfacePreprocessor(_SurfaceTask):
 
     @staticmethod
     def _check(src_fmt, dst_fmt, sw, sh, dw, dh):
-        if src_fmt != F.NV12 or dst_fmt not in (F.RGB_32F, F.RGB_32F_PLANAR, F.RGB, F.BGR, F.RGB_PLANAR):
+        if dst_fmt not in PySurfacePreprocessor._DST:
+            return TaskExecDetails.failed(TaskExecInfo.NOT_SUPPORTED)
+        if src_fmt in PySurfacePreprocessor._RGB_SRC:
+            return None
+        if src_fmt != F.NV12:
             return TaskExecDetails.failed(TaskExecInfo.NOT_SUPPORTED)
         if (sw | sh | dw | dh) & 1:
             return _S_INVALID
@@ -655,6 +673,12 @@ class PySurfacePreprocessor(_SurfaceTask):
             return bad
         if self._u8_needs_identity(dst.Format):
             return TaskExecDetails.failed(TaskExecInfo.NOT_SUPPORTED)
+        if src.Format in self._RGB_SRC:    # the region kernel with whole rectangles; no colour matrix
+            args = ((0, 0, src.Width, src.Height, 0, 0, dst.Width, dst.Height), self._params(None), False, (0, 0, 0))
+            d = _status(shim.rgb_preproc_roi(src.desc(), dst.desc(), *args, self._stream))
+            if d is _S_OK:
+                self._memo_put((src.desc(), dst.desc(), _cc_key(cc_ctx)), shim.rgb_preproc_roi, args)
+            return d
         p = self._params(cc_ctx)
         if p is None:
             return _S_UNSUPP_CC
@@ -689,6 +713,11 @@ class PySurfacePreprocessor(_SurfaceTask):
             return bad.success, bad.info
         if self._u8_needs_identity(batch.dst_format):
             return False, TaskExecInfo.NOT_SUPPORTED
+        if batch.src_format in self._RGB_SRC:    # no rectangle records: whole surfaces
+            d = _status(shim.rgb_preproc_roi_batch(batch.d_src, batch.d_dst, 0, batch.n, int(batch.src_format),
+                                                   batch.dst_size[0], batch.dst_size[1], int(batch.dst_format),
+                                                   self._params(None), False, (0, 0, 0), self._stream))
+            return d.success, d.info
         p = self._params(cc_ctx)
         if p is None:
             return False, TaskExecInfo.UNSUPPORTED_FMT_CONV_PARAMS
@@ -703,7 +732,8 @@ class PySurfacePreprocessor(_SurfaceTask):
         return r
 
     # ---- regions: crop / letterbox / mosaic (vali_nv12_preproc_roi[_batch]) ----
-    # src_rect = (x, y, w, h) in source luma pixels, dst_rect in destination pixels, all even; None = the whole
+    # src_rect = (x, y, w, h) in source luma pixels, dst_rect in destination pixels, all even for NV12 sources (any
+    # integers, at least 1 x 1, for RGB, BGR and RGB_PLANAR sources); None = the whole
     # surface.  Inside dst_rect the result is exactly Run(view of src_rect, view of dst_rect); outside it the pad
     # colour (R, G, B) in u8 through the same normalisation, or -- pad=None -- nothing is written.
     def RunRoiAsync(self, src: Surface, dst: Surface, src_rect=None, dst_rect=None, pad=None,
@@ -715,11 +745,15 @@ class PySurfacePreprocessor(_SurfaceTask):
             return bad.success, bad.info
         if self._u8_needs_identity(dst.Format):
             return False, TaskExecInfo.NOT_SUPPORTED
+        is_rgb = src.Format in self._RGB_SRC
         try:
-            roi = _roi_record(src_rect, dst_rect, (src.Width, src.Height), (dst.Width, dst.Height))
+            roi = _roi_record(src_rect, dst_rect, (src.Width, src.Height), (dst.Width, dst.Height), even=not is_rgb)
             on, rgb = _pad_colour(pad)
         except ValueError:
             return False, TaskExecInfo.INVALID_INPUT
+        if is_rgb:
+            d = _status(shim.rgb_preproc_roi(src.desc(), dst.desc(), roi, self._params(None), on, rgb, self._stream))
+            return d.success, d.info
         p = self._params(cc_ctx)
         if p is None:
             return False, TaskExecInfo.UNSUPPORTED_FMT_CONV_PARAMS
@@ -743,8 +777,8 @@ class PySurfacePreprocessor(_SurfaceTask):
         device (include/vali_hip.h); the tensor must stay alive until the launch has run."""
         if not isinstance(batch, RoiBatch):
             raise ValueError("RunRoiBatch: pass a RoiBatch (PrepareRoiBatch)")
-        if any(f != F.NV12 for f in batch.src_formats) or batch.dst_format not in (
-                F.RGB_32F, F.RGB_32F_PLANAR, F.RGB, F.BGR, F.RGB_PLANAR):
+        is_rgb = batch.src_format in self._RGB_SRC
+        if (batch.src_format != F.NV12 and not is_rgb) or batch.dst_format not in self._DST:
             return False, TaskExecInfo.NOT_SUPPORTED
         if self._u8_needs_identity(batch.dst_format):
             return False, TaskExecInfo.NOT_SUPPORTED
@@ -752,10 +786,15 @@ class PySurfacePreprocessor(_SurfaceTask):
             on, rgb = _pad_colour(pad)
         except ValueError:
             return False, TaskExecInfo.INVALID_INPUT
-        p = self._params(cc_ctx)
+        p = self._params(None if is_rgb else cc_ctx)
         if p is None:
             return False, TaskExecInfo.UNSUPPORTED_FMT_CONV_PARAMS
         d_roi, _hold = (batch.d_roi, None) if rects is None else _device_rects(rects, batch.n, batch.gpu_id)
+        if is_rgb:
+            d = _status(shim.rgb_preproc_roi_batch(batch.d_src, batch.d_dst, d_roi, batch.n, int(batch.src_format),
+                                                   batch.dst_size[0], batch.dst_size[1], int(batch.dst_format), p, on,
+                                                   rgb, self._stream))
+            return d.success, d.info
         d = _status(shim.nv12_preproc_roi_batch(batch.d_src, batch.d_dst, d_roi, batch.n, batch.dst_size[0],
                                                 batch.dst_size[1], int(batch.dst_format), p, on, rgb, self._stream))
         return d.success, d.info
@@ -779,21 +818,58 @@ def letterbox_rect(src_w: int, src_h: int, dst_w: int, dst_h: int) -> Tuple[int,
     return ((dst_w - w) // 4) * 2, ((dst_h - h) // 4) * 2, w, h
 
 
-def _rect(r, size, what):
-    """A host rectangle (x, y, w, h): even, at least 2 x 2, inside `size`; None = the whole surface."""
+def _rect(r, size, what, even=True):
+    """A host rectangle (x, y, w, h): even, at least 2 x 2, inside `size` (even=False: any integers, at least 1 x 1);
+    None = the whole surface."""
     if r is None:
         return (0, 0, size[0], size[1])
     try:
         x, y, w, h = (operator.index(v) for v in r)
     except (TypeError, ValueError):
         raise ValueError(f"{what}: a rectangle is four integers (x, y, w, h)") from None
+    if not even:
+        if w < 1 or h < 1 or x < 0 or y < 0 or x + w > size[0] or y + h > size[1]:
+            raise ValueError(f"{what}: {(x, y, w, h)} must be at least 1 x 1 and inside {size[0]} x {size[1]}")
+        return (x, y, w, h)
     if (x | y | w | h) & 1 or w < 2 or h < 2 or x < 0 or y < 0 or x + w > size[0] or y + h > size[1]:
         raise ValueError(f"{what}: {(x, y, w, h)} must be even, at least 2 x 2 and inside {size[0]} x {size[1]}")
     return (x, y, w, h)
 
 
-def _roi_record(src_rect, dst_rect, src_size, dst_size):
-    return _rect(src_rect, src_size, "src_rect") + _rect(dst_rect, dst_size, "dst_rect")
+def _roi_record(src_rect, dst_rect, src_size, dst_size, even=True):
+    return _rect(src_rect, src_size, "src_rect", even) + _rect(dst_rect, dst_size, "dst_rect", even)
+
+
+def _roi_batch_records(srcs, dsts, src_rects=None, dst_rects=None):
+    """RoiBatch's host checks, without a device: (the sources' one format, the rectangle records).  All sources
+    share ONE format; NV12 sources, their destinations and rectangles are even, RGB / BGR / RGB_PLANAR ones are any
+    integers with rectangles of at least 1 x 1.  ValueError otherwise."""
+    srcs, dsts = list(srcs), list(dsts)
+    n = len(srcs)
+    if not n or len(dsts) != n:
+        raise ValueError("RoiBatch: need equally long, non-empty src and dst lists")
+    if n > 65535:
+        raise ValueError("RoiBatch: at most 65535 items")
+    src_rects = [None] * n if src_rects is None else list(src_rects)
+    dst_rects = [None] * n if dst_rects is None else list(dst_rects)
+    if len(src_rects) != n or len(dst_rects) != n:
+        raise ValueError("RoiBatch: src_rects / dst_rects need one entry per item")
+    if any(s is None or s.IsEmpty for s in srcs):
+        raise ValueError("RoiBatch: sources must be non-empty surfaces")
+    src_format = srcs[0].Format
+    if any(s.Format != src_format for s in srcs):
+        raise ValueError("RoiBatch: the sources of a batch must share one format")
+    even = src_format not in PySurfacePreprocessor._RGB_SRC
+    if even and any((s.Width | s.Height) & 1 for s in srcs):
+        raise ValueError("RoiBatch: sources must be non-empty surfaces of even size")
+    if dsts[0] is None:
+        raise ValueError("RoiBatch: destinations must be non-empty surfaces")
+    f0, s0 = dsts[0].Format, (dsts[0].Width, dsts[0].Height)
+    for d in dsts:
+        if d is None or d.IsEmpty or d.Format != f0 or (d.Width, d.Height) != s0 or (even and (d.Width | d.Height) & 1):
+            raise ValueError("RoiBatch: destinations must share format and (for NV12 sources: even) size")
+    return src_format, [_roi_record(sr, dr, (s.Width, s.Height), s0, even)
+                        for s, sr, dr in zip(srcs, src_rects, dst_rects)]
 
 
 def _pad_colour(pad):
@@ -841,30 +917,16 @@ def _device_rects(rects, n, gpu_id):
 
 
 class RoiBatch:
-    """Device-resident arrays for n region items: source descriptors (any NV12 sizes, repeats allowed), destination
-    descriptors (one format and size) and rectangle records, uploaded once (PySurfacePreprocessor.PrepareRoiBatch)."""
+    """Device-resident arrays for n region items: source descriptors (one format, any sizes, repeats allowed),
+    destination descriptors (one format and size) and rectangle records, uploaded once
+    (PySurfacePreprocessor.PrepareRoiBatch)."""
 
     def __init__(self, gpu_id: int, stream: int, srcs: Sequence[Surface], dsts: Sequence[Surface], src_rects=None,
                  dst_rects=None):
         srcs, dsts = list(srcs), list(dsts)
+        self.src_format, self.rects = _roi_batch_records(srcs, dsts, src_rects, dst_rects)
         n = len(srcs)
-        if not n or len(dsts) != n:
-            raise ValueError("RoiBatch: need equally long, non-empty src and dst lists")
-        if n > 65535:
-            raise ValueError("RoiBatch: at most 65535 items")
-        src_rects = [None] * n if src_rects is None else list(src_rects)
-        dst_rects = [None] * n if dst_rects is None else list(dst_rects)
-        if len(src_rects) != n or len(dst_rects) != n:
-            raise ValueError("RoiBatch: src_rects / dst_rects need one entry per item")
-        for s in srcs:
-            if s is None or s.IsEmpty or (s.Width | s.Height) & 1:
-                raise ValueError("RoiBatch: sources must be non-empty surfaces of even size")
         f0, s0 = dsts[0].Format, (dsts[0].Width, dsts[0].Height)
-        for d in dsts:
-            if d is None or d.IsEmpty or d.Format != f0 or (d.Width, d.Height) != s0 or (d.Width | d.Height) & 1:
-                raise ValueError("RoiBatch: destinations must share format and (even) size")
-        self.rects = [_roi_record(sr, dr, (s.Width, s.Height), s0)
-                      for s, sr, dr in zip(srcs, src_rects, dst_rects)]
         if is_capturing(gpu_id, stream):
             raise RuntimeError("RoiBatch: cannot be created while the stream is capturing -- PrepareRoiBatch() "
                                "before the StreamCapture block and Keep() the batch with the capture")
