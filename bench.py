@@ -9,16 +9,23 @@ far beyond the 256 MiB Infinity Cache).  Inputs are resident in HBM before the t
 region.  One process per GPU; frames are sharded, never exchanged: the only
 collective is the RCCL broadcast of the 32-byte colour-coefficient block.
 
-  python bench.py                      # 1 GPU
+  python bench.py                      # 1 GPU: set up, warm up, time the steps, print the line -- nothing else
+  python bench.py --full               # + everything else the benchmark measures and checks (below)
   python bench.py --gpus N             # spawns N ranks itself (one per GPU, RCCL), rank 0 prints the line
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W     # the same under torchrun
   python bench.py --dump-outputs DIR   # also write the last timed step's outputs to DIR/*.npy (seeded inputs:
                                        # two builds compare output for output)
 
-Prints ONE JSON line on rank 0 (contract in the task brief): value = whole-job frames/s,
-`roofline` = algorithmic bytes / HIP-event kernel time vs the 8 TB/s HBM peak,
-`cpu_baseline` = the C oracle (port of the same arithmetic) timed on the host cores.
+Prints ONE JSON line on rank 0: value = whole-job frames/s, `ms_per_step` = wall time of a timed step,
+`roofline` = algorithmic bytes / HIP-event kernel time of the timed steps vs the 8 TB/s HBM peak.
+
+A plain run does only what that needs.  `--full` adds, after the timed steps and the dump and never part of `value`:
+`verification` (every output frame against its seed frame's, on the GPU) and `parity_vs_oracle` (outputs against the
+C oracle), `host_placement.gpu_state` (clocks and power under this load), `host_fed` (the host-fed ingest ring),
+`cpu_baseline` (the C oracle, a port of the same arithmetic, timed on the host cores) and `secondary` (the other
+BASELINE configurations, tools/bench_configs.py).  --cpu-seconds, --ingest-seconds, --no-parity, --no-secondary and
+--verbose shape those parts and mean nothing without --full.
 """
 from __future__ import annotations
 
@@ -52,8 +59,12 @@ def parse():
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--dst", default="RGB", choices=["RGB", "BGR", "RGB_PLANAR"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything else: all-frame verification, parity with the "
+                         "oracle, GPU clocks under load, the host-fed pipeline, the CPU baseline and the secondary configurations "
+                         "(none of it is part of `value`; off by default: a plain run sets up, warms up, times and prints)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="budget of the CPU baseline sample (rank 0, N=1 only); 0 disables")
+                    help="--full: budget of the CPU baseline sample (rank 0, N=1 only); 0 disables")
     ap.add_argument("--ramp-ms", type=float, default=400.0,
                     help="untimed pre-conditioning before the W warm-up steps: the same launch repeated for this long, so "
                          "that the timed steps see the clocks the chip holds under this load and not the idle state of a "
@@ -64,14 +75,14 @@ def parse():
                          "preproc = fused NV12->normalised RGB_32F_PLANAR at --dst-size")
     ap.add_argument("--dst-size", default=None, help="WxH of the output for --op resize / ud / preproc (default: half the source)")
     ap.add_argument("--ingest-seconds", type=float, default=1.5,
-                    help="N=1: also time the HOST-FED pipeline (pinned staging + H2D on a copy stream overlapped with the "
+                    help="--full, N=1: also time the HOST-FED pipeline (pinned staging + H2D on a copy stream overlapped with the "
                          "conversion, IngestRing) for this long and report it beside the resident number; 0 disables")
     ap.add_argument("--no-numa-bind", action="store_true", help="do not pin each rank to the CPUs of its GPU's NUMA node")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the all-frame verification and the oracle parity check")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip BASELINE configs[1..3] (tools/bench_configs.py; a few seconds, N=1 only)")
+                    help="--full: skip BASELINE configs[1..3] (tools/bench_configs.py; a few seconds, N=1 only)")
     ap.add_argument("--verbose", action="store_true",
-                    help="the long form of the line (every note, the full roofline object of every secondary entry, ~18 KB: what "
+                    help="--full: the long form of the line (every note, the full roofline object of every secondary entry, ~18 KB: what "
                          "profiles/rNN_bench_line.json keeps).  The default line is the SAME measurements in < 7 500 characters, "
                          "weakest kernels last, so that a reader who keeps only the tail of the line sees every entry (VERDICT r05)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -550,9 +561,11 @@ def main():
         rank_devices = [dev]
         shards = [[begin, end]]
 
+    # everything below that is not the result line itself is --full's: a plain run has nothing left to launch or to check
+
     # the state the chip holds under this load, read from sysfs between launches AFTER the timed region (rank 0 only)
     clocks = None
-    if rank == 0:
+    if args.full and rank == 0:
         def _one():
             step()
             shim.stream_sync(dev, stream)
@@ -566,7 +579,7 @@ def main():
     # themselves are what rank 0 checks against the oracle below.  The per-rank 64-bit checksum
     # and mismatch count are summed over ranks (the optional all-reduce of SURVEY.md 8e).
     verification = None
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         outs = [torch.from_dlpack(d) for d in pipe.dsts]
         sums = [int(outs[i].sum(dtype=torch.int64).item()) for i in range(nseed)]
         bad = sum(0 if torch.equal(outs[i], outs[i % nseed]) else 1 for i in range(nseed, F))
@@ -578,7 +591,7 @@ def main():
         del outs
 
     parity = None
-    if not args.no_parity and rank == 0 and args.op == "convert":
+    if args.full and not args.no_parity and rank == 0 and args.op == "convert":
         from oracle import oracle as o
 
         dwn = vali.PySurfaceDownloader(dev, stream)
@@ -607,7 +620,7 @@ def main():
             "metric": f"{op_name}_2160p_frames_per_s" if (W, H) == (3840, 2160)
                       else f"{op_name}_{W}x{H}_frames_per_s",
             "value": round(fps, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ramp_ms_untimed": args.ramp_ms, "ramp_steps_untimed": ramp_steps,
+            "warmup": args.warmup, "full": args.full, "ramp_ms_untimed": args.ramp_ms, "ramp_steps_untimed": ramp_steps,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
             "data": "synthetic",
@@ -639,15 +652,15 @@ def main():
             out["dump_outputs"] = {"dir": args.dump_outputs, "arrays_of_rank0": dumped}
         out["host_placement"] = {"numa_bound_cpus": (f"{numa_cpus[0]}-{numa_cpus[-1]} ({len(numa_cpus)} CPUs)" if numa_cpus else None),
                                  "pci_bus_id": shim.device_pci_bus_id(dev), "gpu_state": clocks}
-        if world == 1 and args.ingest_seconds > 0:
+        if args.full and world == 1 and args.ingest_seconds > 0:
             try:
                 pipe.srcs.clear(); pipe.dsts.clear()          # the ring allocates its own slots
                 out["host_fed"] = host_fed_rate(vali, (dev, dst_fmt, args.op, dst_size), cc, args.ingest_seconds, W, H)
             except Exception as e:  # noqa: BLE001 -- a side measurement must not take the headline line down
                 out["host_fed"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and args.cpu_seconds > 0 and args.op == "convert":
+        if args.full and world == 1 and args.cpu_seconds > 0 and args.op == "convert":
             out["cpu_baseline"] = cpu_baseline(W, H, coeffs, args.cpu_seconds)
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             out["secondary"] = secondary_configs(pipe)
         if not args.verbose:
             out = compact_line(out)

@@ -46,3 +46,12 @@ def test_large_batch_is_sampled_within_the_budget(bench, tmp_path, monkeypatch):
     # the same positions in every run
     bench.dump_outputs(frames, tmp_path / "b", 1, 2)
     assert np.array_equal(np.load(tmp_path / "b" / "dst_rank1_index.npy"), idx)
+
+
+def test_full_is_an_option_that_is_off_by_default(bench, monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` only times its steps; --full asks for the rest."""
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and (a.gpus, a.steps, a.warmup) == (1, 7, 2)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--full"])
+    assert bench.parse().full is True

@@ -1,5 +1,6 @@
 """bench.py contract on a real GPU: one JSON line with the required keys; the N>1 code path
-(sharding, coefficient broadcast, barrier, max-over-ranks) with 2 ranks sharing the one GPU."""
+(sharding, coefficient broadcast, barrier, max-over-ranks) with 2 ranks sharing the one GPU.
+A plain run only times its steps; everything else the benchmark measures or checks is asked for with --full."""
 import json
 import os
 import subprocess
@@ -21,13 +22,37 @@ def last_json(out: str):
     return json.loads(lines[0])
 
 
+MOVED_BEHIND_FULL = ["verification", "parity_vs_oracle", "host_fed", "cpu_baseline", "secondary", "secondary_keys"]
+
+
+def test_bench_plain_run_only_times_its_steps(gpu):
+    """Without --full: the line with the required keys and the headline's own roofline (HIP events of the timed steps), and
+    nothing that takes launches, checks or host work of its own -- whatever --cpu-seconds and its like say."""
+    for extra in ([], ["--cpu-seconds", "1", "--ingest-seconds", "1", "--verbose"]):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--frames", "16"] + extra, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = last_json(r.stdout)
+        for k in REQUIRED:
+            assert k in j, k
+        assert j["full"] is False and j["n_gpus"] == 1 and j["steps"] == 3 and j["warmup"] == 1
+        assert j["unit"] == "frames/s" and j["dtype"] == "u8" and j["higher_is_better"] is True
+        assert j["metric"] == "nv12_to_rgb_2160p_frames_per_s" and j["value"] > 0 and j["ms_per_step"] > 0
+        assert j["value"] == pytest.approx(16 * 1e3 / j["ms_per_step"], rel=1e-2)   # both figures are rounded
+        assert j["roofline"]["bound"] == "hbm" and 0 < j["roofline"]["frac"] < 1
+        for k in MOVED_BEHIND_FULL:
+            assert k not in j, k
+        assert j["host_placement"]["gpu_state"] is None and j["host_placement"]["pci_bus_id"]
+
+
 def test_bench_single_gpu_contract(gpu):
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "3", "--warmup", "1",
                         "--frames", "16", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     j = last_json(r.stdout)
     for k in REQUIRED:
         assert k in j, k
+    assert j["full"] is True
     assert j["n_gpus"] == 1 and j["steps"] == 3 and j["unit"] == "frames/s" and j["dtype"] == "u8"
     assert j["ranks_seen"] == 1 and j["launcher"] == "single process"
     assert j["roofline"]["bound"] == "hbm" and 0 < j["roofline"]["frac"] < 1
@@ -61,7 +86,7 @@ def test_bench_single_gpu_contract(gpu):
 def test_bench_verbose_line_keeps_the_full_roofline_objects(gpu):
     """--verbose: the long form profiles/rNN_bench_line.json keeps (notes, bound / peak / unit / working set of every entry)."""
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1", "--frames", "8", "--cpu-seconds", "0",
-                        "--ingest-seconds", "0", "--verbose"], capture_output=True, text=True, timeout=600)
+                        "--ingest-seconds", "0", "--full", "--verbose"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     j = last_json(r.stdout)
     assert [c["config"][:4] for c in j["secondary"]] == ["NV12", "cfg2", "cfg3", "inte", "upsc", "cfg4", "udge", "udpl", "affi"]
@@ -133,7 +158,7 @@ def test_bench_two_ranks_share_one_gpu(gpu):
     env = dict(os.environ, VALI_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29617", str(ROOT / "bench.py"),
-                        "--gpus", "2", "--steps", "3", "--warmup", "1", "--frames", "16"],
+                        "--gpus", "2", "--steps", "3", "--warmup", "1", "--frames", "16", "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     j = last_json(r.stdout)
@@ -148,7 +173,7 @@ def test_bench_gpus_flag_spawns_the_ranks_itself(gpu):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["VALI_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--frames", "16"], capture_output=True, text=True, timeout=900, env=env)
+                        "--frames", "16", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     j = last_json(r.stdout)
     assert j["n_gpus"] == 2 and j["ranks_seen"] == 2 and j["launcher"] == "self-spawned"
@@ -164,7 +189,7 @@ def _self_spawned_ranks_64_frames(n):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["VALI_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", str(n), "--frames", str(per), "--width", "1920",
-                        "--height", "1080", "--steps", "2", "--warmup", "1", "--ramp-ms", "0"],
+                        "--height", "1080", "--steps", "2", "--warmup", "1", "--ramp-ms", "0", "--full"],
                        capture_output=True, text=True, timeout=1200, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     j = last_json(r.stdout)
@@ -245,7 +270,7 @@ def test_bench_dump_outputs_are_the_last_timed_steps_outputs(gpu, oracle, tmp_pa
 
 def test_bench_line_carries_the_gpu_state(gpu):
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1", "--frames", "8",
-                        "--cpu-seconds", "0", "--no-secondary", "--ingest-seconds", "0"],
+                        "--full", "--cpu-seconds", "0", "--no-secondary", "--ingest-seconds", "0"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     st = last_json(r.stdout)["host_placement"]["gpu_state"]
@@ -271,7 +296,7 @@ def test_bench_rccl_path_single_rank(gpu):
     env = dict(os.environ, VALI_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29618",
                RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--frames", "16", "--cpu-seconds", "0", "--no-secondary"],
+                        "--frames", "16", "--full", "--cpu-seconds", "0", "--no-secondary"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     j = last_json(r.stdout)
