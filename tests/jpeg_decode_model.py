@@ -12,6 +12,8 @@ MCU, an FF followed by anything but 00 or the expected RSTn, a wrong number of R
 """
 from __future__ import annotations
 
+import functools
+
 import numpy as np
 
 from jpeg_model import ZIGZAG
@@ -306,11 +308,17 @@ def ycc_to_rgb(y, cb, cr):
     return np.clip(np.stack([r, g, b], -1), 0, 255).astype(np.uint8)
 
 
+@functools.lru_cache(maxsize=4)
+def _parsed_planes(data: bytes):
+    """(info, component planes) of a file; kept for the next outputs asked of the same file (nothing writes to them)"""
+    info = parse(data)
+    return info, component_planes(info)
+
+
 def decode(data, out="RGB"):
     """out: "RGB" -> (h, w, 3); "Y" -> (h, w); "planes" -> the component planes cropped to the image.
     None when the entropy data is corrupt."""
-    info = parse(data)
-    planes = component_planes(info)
+    info, planes = _parsed_planes(bytes(data))
     if planes is None:
         return None
     w, h = info["w"], info["h"]

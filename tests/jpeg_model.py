@@ -189,11 +189,12 @@ def component_blocks(plane, qtab, bw, bh):
     return quantize(fdct_islow(blk).reshape(-1, 64), qtab).reshape(bh, bw, 64)
 
 
-def scan_blocks(fmt, planes, w, h, quality):
-    """every block in MCU-interleaved scan order, dummy blocks included: (coefficients (N, 64), component (N,))"""
-    H, V = sampling(fmt)
+def scan_blocks(fmt, planes, w, h, quality, tables=None, samp=None):
+    """every block in MCU-interleaved scan order, dummy blocks included: (coefficients (N, 64), component (N,)).
+    tables: (luma, chroma) quantisation tables instead of those of `quality`; samp: (H, V) instead of fmt's"""
+    H, V = samp or sampling(fmt)
     mx, my = -(-w // (8 * H)), -(-h // (8 * V))
-    lq, cq = quant_tables(quality)
+    lq, cq = tables if tables is not None else quant_tables(quality)
     comps = []
     for c, (pl, hs, vs) in enumerate(zip(planes, (H, 1, 1), (V, 1, 1))):
         cw, ch = -(-w * hs // H), -(-h * vs // V)           # component size (jdiv_round_up)

@@ -2,6 +2,10 @@
 //
 // DEFINITION = libjpeg-turbo's default decompression; tests/jpeg_decode_model.py restates it and
 // tests/test_jpeg_decode_host.py pins the restatement to Pillow byte for byte.
+// It is the C path (jidctint.c: the dequantised coefficient is an int, the passes run in JLONG).  Pillow runs the SIMD
+// path, which keeps dequantised coefficients and their first sums in 16-bit lanes: the two agree while those stay within
+// 16 bits (the q50 tables times 3 still do, times 4 no longer: DESIGN.md section 4) and beyond that this decoder follows
+// the C path, not the SIMD one -- 16-bit quantisation values wrap as a short, nothing else narrows.
 //
 // The entropy decode is serial by nature, and most files have no restart markers.  It runs self-synchronising
 // (Weissenberger & Schmidt, ICPP 2018): every restart segment is cut into subsequences of kSubBits bits, a lane
