@@ -293,11 +293,12 @@ def _seg(marker, payload):
     return bytes([0xFF, marker]) + (len(payload) + 2).to_bytes(2, "big") + payload
 
 
-def header(w, h, fmt, quality, R=None):
-    """SOI, APP0 (JFIF 1.1, aspect 1:1), DQT (both tables), SOF0, DHT (four tables), DRI, SOS"""
+def header(w, h, fmt, quality, R=None, tables=None):
+    """SOI, APP0 (JFIF 1.1, aspect 1:1), DQT (both tables), SOF0, DHT (four tables), DRI, SOS.
+    tables: (luma, chroma) quantisation tables in natural order instead of those of `quality`"""
     R = restart_interval(fmt) if R is None else R
     H, V = sampling(fmt)
-    lq, cq = quant_tables(quality)
+    lq, cq = (np.asarray(t) for t in tables) if tables is not None else quant_tables(quality)
     out = b"\xff\xd8" + _seg(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
     out += _seg(0xDB, bytes([0]) + bytes(lq[ZIGZAG].tolist()) + bytes([1]) + bytes(cq[ZIGZAG].tolist()))
     out += _seg(0xC0, bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([3, 1, (H << 4) | V, 0,
@@ -312,16 +313,18 @@ def header(w, h, fmt, quality, R=None):
     return out
 
 
-def entropy(fmt, host, w, h, quality, R=None):
+def entropy(fmt, host, w, h, quality, R=None, tables=None):
     """the entropy-coded data (restart markers included) of one image"""
     R = restart_interval(fmt) if R is None else R
-    coefs, comp, bpm = scan_blocks(fmt, planes_of(fmt, host, w, h), w, h, quality)
+    if tables is not None:
+        tables = tuple(np.asarray(t) for t in tables)
+    coefs, comp, bpm = scan_blocks(fmt, planes_of(fmt, host, w, h), w, h, quality, tables=tables)
     return huffman(coefs, comp, bpm, R)
 
 
-def encode(fmt, host, w, h, quality, R=None):
+def encode(fmt, host, w, h, quality, R=None, tables=None):
     """the whole file vali_jpeg_header + vali_jpeg_encode_batch + EOI produce"""
-    return header(w, h, fmt, quality, R) + entropy(fmt, host, w, h, quality, R) + b"\xff\xd9"
+    return header(w, h, fmt, quality, R, tables) + entropy(fmt, host, w, h, quality, R, tables) + b"\xff\xd9"
 
 
 def entropy_of_file(data):
@@ -365,8 +368,10 @@ def make_host(fmt, w, h, content="noise", seed=0, frame=None):
     return np.concatenate([y.reshape(-1), u[::sy, ::sx][:ch, :cw].reshape(-1), v[::sy, ::sx][:ch, :cw].reshape(-1)])
 
 
-def pillow_encode(fmt, host, w, h, quality):
-    """what the CPU backend of PyNvJpegEncoder writes for this host image (vali_amd/codecs.py: Pillow, libjpeg)"""
+def pillow_encode(fmt, host, w, h, quality, tables=None):
+    """what the CPU backend of PyNvJpegEncoder writes for this host image (vali_amd/codecs.py: Pillow, libjpeg).
+    tables: (luma, chroma) in natural order, unscaled, instead of those of `quality`; the order and the scale Pillow
+    applies are checked by reading the file's tables back"""
     import io
 
     from PIL import Image
@@ -383,5 +388,11 @@ def pillow_encode(fmt, host, w, h, quality):
         img = Image.fromarray(np.ascontiguousarray(np.stack([y, u, v], -1)), "YCbCr")
         sub = {YUV444: 0, YUV422: 1, YUV420: 2}[fmt]
     out = io.BytesIO()
-    img.save(out, format="JPEG", quality=max(1, min(100, int(quality))), subsampling=sub)
+    if tables is None:
+        img.save(out, format="JPEG", quality=max(1, min(100, int(quality))), subsampling=sub)
+        return out.getvalue()
+    want = [[int(v) for v in t] for t in tables]
+    img.save(out, format="JPEG", qtables=want, subsampling=sub)    # no quality: Pillow would scale the tables by it
+    back = Image.open(io.BytesIO(out.getvalue())).quantization
+    assert [list(back[0]), list(back[1])] == want, "Pillow did not write the tables as given"
     return out.getvalue()

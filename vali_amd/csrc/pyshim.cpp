@@ -532,12 +532,17 @@ PYBIND11_MODULE(_vali_shim, m) {
       .def_property_readonly("v_samp", [](const JpegParams& j) { return j.p.v_samp; })
       .def_property("restart_interval", [](const JpegParams& j) { return j.p.restart_interval; },
                     [](JpegParams& j, int r) { j.p.restart_interval = r; })
-      .def_property_readonly("qtable", [](const JpegParams& j) {
+      .def_property("qtable", [](const JpegParams& j) {
         std::vector<std::vector<int>> t(2, std::vector<int>(64));
         for (int i = 0; i < 2; ++i)
           for (int k = 0; k < 64; ++k)
             t[i][k] = j.p.qtable[i][k];
         return t;
+      }, [](JpegParams& j, const std::array<std::array<uint8_t, 64>, 2>& t) {
+        // (luma, chroma) in natural order; vali_jpeg_* validate it, not the shim
+        for (int i = 0; i < 2; ++i)
+          for (int k = 0; k < 64; ++k)
+            j.p.qtable[i][k] = t[i][k];
       });
   m.def("jpeg_params_init", [](int quality, int format) {
     JpegParams j;
