@@ -8,8 +8,8 @@
 
     python examples/jpeg_to_detector_input.py [file.jpg ...]
 
-Without arguments it encodes a few synthetic 1080p pictures with Pillow first."""
-import io
+Without arguments it first encodes a few synthetic 1080p RGB surfaces on the GPU, 4:2:0
+(PyNvJpegEncoder(backend="hip"), Context(..., subsampling="420")): the whole round trip then stays on the device."""
 import sys
 from pathlib import Path
 
@@ -19,22 +19,25 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import python_vali as vali  # noqa: E402
 
 
-def synthetic(n=4, w=1920, h=1080):
-    from PIL import Image
-
+def synthetic(gpu_id, n=4, w=1920, h=1080):
     yy, xx = np.mgrid[0:h, 0:w]
-    files = []
+    surfaces = []
     for i in range(n):
         rgb = np.stack([(xx + 40 * i) % 256, (yy + xx // 3) % 256, (2 * yy + 9 * i) % 256], -1).astype(np.uint8)
-        out = io.BytesIO()
-        Image.fromarray(rgb).save(out, "JPEG", quality=90, subsampling=2)     # 4:2:0, Pillow's default
-        files.append(out.getvalue())
-    return files
+        s = vali.Surface.Make(vali.PixelFormat.RGB, w, h, gpu_id)
+        ok, info = vali.PyFrameUploader(gpu_id).Run(rgb.reshape(-1), s)
+        assert ok, info
+        surfaces.append(s)
+    enc = vali.PyNvJpegEncoder(gpu_id, backend="hip")
+    # 4:2:0, as libjpeg and Pillow write RGB pixels by default: the files PyNvJpegDecoder returns as NV12
+    files, status = enc.Run(enc.Context(90, vali.PixelFormat.RGB, subsampling="420"), surfaces)
+    assert status == vali.TaskExecInfo.SUCCESS
+    return [f.tobytes() for f in files]
 
 
 def main():
     gpu_id = 0
-    files = [Path(p).read_bytes() for p in sys.argv[1:]] or synthetic()
+    files = [Path(p).read_bytes() for p in sys.argv[1:]] or synthetic(gpu_id)
     dec = vali.PyNvJpegDecoder(gpu_id)
     for f in files:
         info = dec.Info(f)                                  # host only: size, sampling, restart interval

@@ -351,8 +351,20 @@ VALI_API int vali_rgb_preproc_roi_batch(const vali_surface* d_src, const vali_su
  *
  * The reference's PyNvJpegEncoder (src/TC/src/TaskNvJpegEncode.cpp) on nvJPEG.  Definition (tests/jpeg_model.py
  * restates it; with no restart markers its entropy data is byte-identical to libjpeg's for the same pixels):
- *   - RGB, BGR, RGB_PLANAR: libjpeg's fixed-point rgb_ycc, coded 4:4:4.  YUV444, YUV422, YUV420: the planes as
- *     they are (no colour conversion), coded with their own sampling.  Other formats: VALI_ERR_UNSUPPORTED.
+ *   - RGB, BGR, RGB_PLANAR: libjpeg's fixed-point rgb_ycc, coded 4:4:4 (vali_jpeg_params_init) or 4:2:2 / 4:2:0
+ *     (vali_jpeg_params_init_sampled).  YUV444, YUV422, YUV420: the planes as they are (no colour conversion), coded
+ *     with their own sampling.  Other formats: VALI_ERR_UNSUPPORTED.
+ *   - RGB sources coded 4:2:2 / 4:2:0 are downsampled as libjpeg-turbo does by default (jcsample, no smoothing, no
+ *     fancy downsampling), for any size (component size ceil(w / H) x ceil(h / V)).  Every full-resolution pixel is
+ *     converted and truncated to 8 bits first; then
+ *       4:2:0  c[y][x] = (p[2y][2x] + p[2y][2x+1] + p[2y+1][2x] + p[2y+1][2x+1] + bias) >> 2, bias 1 / 2 for even / odd x
+ *       4:2:2  c[y][x] = (p[y][2x] + p[y][2x+1] + bias) >> 1,                                bias 0 / 1 for even / odd x
+ *     The edges are not symmetric.  Horizontally the full-resolution row is replicated at its last pixel out to the
+ *     edge of the chroma component's last real block: a chroma sample at x >= ceil(w / 2) is an average of replicated
+ *     pixels with its own bias, not a copy of its neighbour.  Vertically the full-resolution image is replicated to a
+ *     multiple of V rows only, and below ch = ceil(h / V) the downsampled rows are replicated.  In index form: chroma
+ *     (x, y) reads columns min(2x, w-1), min(2x+1, w-1) and, with y' = min(y, ch-1), rows min(2y', h-1), min(2y'+1, h-1)
+ *     at 4:2:0, row y' at 4:2:2.  Luma is coded as at 4:4:4.
  *   - the last column and row of every component are replicated out to its block edge; the dummy blocks of a
  *     partial MCU have zero AC and the DC of the block to their left (a dummy row: of the previous block of the
  *     same component in that MCU), as libjpeg's jccoefct;
@@ -373,6 +385,10 @@ typedef struct vali_jpeg_params {
 /* host only: the parameters of `quality` (clamped to 1..100) for surfaces of `format`; restart_interval is the
  * largest that keeps a segment within 64 blocks (21 MCUs at 4:4:4, 16 at 4:2:2, 10 at 4:2:0) */
 VALI_API int vali_jpeg_params_init(int quality, int format, vali_jpeg_params* out);
+/* host only: as vali_jpeg_params_init, with the luma sampling h_samp x v_samp: 1x1, 2x1 or 2x2 for RGB, BGR and
+ * RGB_PLANAR (chroma is downsampled as above); for a YUV format only its own.  Everything else is
+ * VALI_ERR_INVALID_ARG; a format that cannot be encoded is VALI_ERR_UNSUPPORTED */
+VALI_API int vali_jpeg_params_init_sampled(int quality, int format, int h_samp, int v_samp, vali_jpeg_params* out);
 /* host only: SOI, APP0 (JFIF), DQT, SOF0, DHT, DRI, SOS of a width x height image (1..65535) into out[0..cap),
  * its length in *len.  out == NULL asks for the length only; cap < length is VALI_ERR_INVALID_ARG (*len still set) */
 VALI_API int vali_jpeg_header(int width, int height, const vali_jpeg_params* params, uint8_t* out, size_t cap,
@@ -383,7 +399,7 @@ VALI_API int vali_jpeg_workspace_size(int n, int width, int height, const vali_j
 VALI_API int vali_jpeg_stream_capacity(int width, int height, const vali_jpeg_params* params, size_t* bytes);
 /*
  * Entropy-codes n (0..65535) images: d_src is a DEVICE array of n descriptors of `format` and width x height
- * (sizes as everywhere: 4:2:0 even width and height, YUV422 even width).  Image i's entropy data, restart markers
+ * (sizes as everywhere: YUV420 even width and height, YUV422 even width; an RGB source takes any size at any sampling).  Image i's entropy data, restart markers
  * included, header and EOI not, goes to d_out + i * out_stride (out_stride >= vali_jpeg_stream_capacity), its
  * length in bytes to d_sizes[i] (device memory).  workspace: ws_bytes >= vali_jpeg_workspace_size, device memory,
  * 256-byte aligned.  Four launches in stream order; nothing is allocated and nothing synchronises, so the call

@@ -3,6 +3,10 @@ calls: launches, sizes, the exact D2H copies and the headers included.  1080p an
 batch 1 / 16 / 64.  Prints one JSON line per configuration and a markdown table (profiles/jpeg.md).
 
   python tools/bench_jpeg.py [--gpu 0] [--quick]     (--quick: 1080p RGB batch 16, hip only: the profiling run)
+  python tools/bench_jpeg.py --sampled [--size 3840x2160]
+      RGB batch 16 coded 4:4:4, 4:2:2 and 4:2:0 (Context(..., subsampling=...)), hip only, the three alternating in
+      one process, best of 5 Run calls each (profiles/jpeg_subsampling.md); with --quick --subsampling 420 one of them
+      alone, for a profiling run
 """
 import argparse
 import json
@@ -47,12 +51,41 @@ def run(enc, ctx, surfs, reps):
     return best, nbytes
 
 
+def sampled(a):
+    w, h = (int(v) for v in a.size.split("x")) if a.size else (1920, 1080)
+    pool = frames(vali.RGB, w, h, 4, a.gpu)
+    surfs = [pool[i % len(pool)] for i in range(16)]
+    enc = vali.PyNvJpegEncoder(a.gpu, backend="hip")
+    ctxs = {s: enc.Context(90, vali.RGB, s) for s in ("444", "422", "420")}
+    best, nbytes = {s: float("inf") for s in ctxs}, {}
+    for s, ctx in ctxs.items():
+        enc.Run(ctx, surfs)                                   # warm-up
+    for _ in range(5):
+        for s, ctx in ctxs.items():
+            t0 = time.perf_counter()
+            out, info = enc.Run(ctx, surfs)
+            best[s] = min(best[s], time.perf_counter() - t0)
+            assert info == vali.TaskExecInfo.SUCCESS
+            nbytes[s] = sum(b.size for b in out)
+    for s in ctxs:
+        print(json.dumps({"size": f"{w}x{h}", "format": "RGB", "subsampling": s, "batch": 16,
+                          "ms_per_call": round(best[s] * 1e3, 3), "images_per_s": round(16 / best[s], 1),
+                          "mean_file_kib": round(nbytes[s] / 16 / 1024, 1)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpu", type=int, default=0)
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--sampled", action="store_true")
+    ap.add_argument("--subsampling", choices=["444", "422", "420"], default=None, help="of RGB surfaces")
+    ap.add_argument("--size", default=None, help="WxH instead of the default sizes")
     a = ap.parse_args()
+    if a.sampled:
+        return sampled(a)
     sizes = [(1920, 1080)] if a.quick else [(1920, 1080), (3840, 2160)]
+    if a.size:
+        sizes = [tuple(int(v) for v in a.size.split("x"))]
     fmts = [vali.RGB] if a.quick else [vali.RGB, vali.YUV420]
     batches = [16] if a.quick else [1, 16, 64]
     backends = ["hip"] if a.quick else ["hip", "cpu"]
@@ -64,7 +97,7 @@ def main():
                 surfs = [pool[i % len(pool)] for i in range(n)]
                 for backend in backends:
                     enc = vali.PyNvJpegEncoder(a.gpu, backend=backend)
-                    ctx = enc.Context(90, fmt)
+                    ctx = enc.Context(90, fmt, a.subsampling if fmt == vali.RGB else None)
                     reps = 10 if backend == "hip" else (3 if n == 1 else 1)
                     t, nbytes = run(enc, ctx, surfs, reps)
                     r = {"size": f"{w}x{h}", "format": fmt.name, "batch": n, "backend": backend,

@@ -731,18 +731,34 @@ class NvJpegEncodeContext:
 
     # format -> PIL JPEG `subsampling` (TaskNvJpegEncode.cpp:101-124: RGB inputs encode 4:4:4, YUV inputs keep theirs)
     _SUBSAMPLING = {F.RGB: 0, F.BGR: 0, F.RGB_PLANAR: 0, F.YUV444: 0, F.YUV422: 1, F.YUV420: 2}
+    # JpegInfo.sampling string -> luma sampling factors, in the order of PIL's `subsampling` values 0, 1, 2
+    _SAMPLINGS = {"444": (1, 1), "422": (2, 1), "420": (2, 2)}
 
-    def __init__(self, compression: int = 100, pixel_format: PixelFormat = F.RGB):
+    def __init__(self, compression: int = 100, pixel_format: PixelFormat = F.RGB, subsampling: Optional[str] = None):
+        """subsampling: None (RGB, BGR and RGB_PLANAR are coded 4:4:4, a YUV format with its own sampling), or "444",
+        "422" or "420" for RGB, BGR and RGB_PLANAR: chroma is then downsampled as libjpeg-turbo does by default.  A YUV
+        format takes its own sampling only."""
         fmt = PixelFormat(pixel_format)
         if fmt not in self._SUBSAMPLING:
             raise ValueError("unsupported pixel format")            # std::invalid_argument, :123
-        self._compression, self._format = int(compression), fmt
+        own = list(self._SAMPLINGS)[self._SUBSAMPLING[fmt]]
+        if subsampling is None:
+            subsampling = own
+        elif subsampling not in self._SAMPLINGS:
+            raise ValueError(f"subsampling must be None, \"444\", \"422\" or \"420\", not {subsampling!r}")
+        elif subsampling != own and fmt not in (F.RGB, F.BGR, F.RGB_PLANAR):
+            raise ValueError(f"{fmt.name} surfaces are coded {own}: their chroma planes are taken as they are")
+        self._compression, self._format, self._subsampling = int(compression), fmt, subsampling
 
     def Compression(self) -> int:
         return self._compression
 
     def Format(self) -> PixelFormat:
         return self._format
+
+    def Subsampling(self) -> str:
+        """the sampling of the files: "444", "422" or "420" """
+        return self._subsampling
 
 
 class PyNvJpegEncoder:
@@ -753,8 +769,9 @@ class PyNvJpegEncoder:
     * "cpu" (the default): the surface is downloaded on the encoder's stream and compressed with Pillow (libjpeg).
     * "hip": baseline JPEG on the GPU (vali_jpeg_encode_batch, include/vali_hip.h): colour conversion, FDCT,
       quantisation and Huffman coding run in HIP; only the finished entropy data of each image comes back over PCIe.
-      Every surface of one size goes into one launch; the header (cached per size, format and quality) and EOI are
-      added on the host.  The files decode to what the "cpu" backend's files decode to (the encoder definition is
+      Every surface of one size goes into one launch; the header (cached per size, format, quality and sampling) and
+      EOI are added on the host.  RGB, BGR and RGB_PLANAR surfaces are coded 4:4:4, or 4:2:2 / 4:2:0 with
+      `Context(..., subsampling="422" / "420")`.  The files decode to what the "cpu" backend's files decode to (the encoder definition is
       libjpeg's); they differ in bytes only by the restart markers the GPU coder needs (DRI)."""
 
     BACKENDS = ("cpu", "hip")
@@ -782,8 +799,9 @@ class PyNvJpegEncoder:
     def Backend(self) -> str:
         return self._backend
 
-    def Context(self, compression: int, pixel_format: PixelFormat) -> NvJpegEncodeContext:
-        return NvJpegEncodeContext(compression, pixel_format)
+    def Context(self, compression: int, pixel_format: PixelFormat,
+                subsampling: Optional[str] = None) -> NvJpegEncodeContext:
+        return NvJpegEncodeContext(compression, pixel_format, subsampling)
 
     def _image(self, fmt: PixelFormat, w: int, h: int, host: np.ndarray):
         from PIL import Image
@@ -821,21 +839,22 @@ class PyNvJpegEncoder:
             out = io.BytesIO()
             q = max(1, min(100, context.Compression()))
             self._image(surf.Format, surf.Width, surf.Height, host).save(
-                out, format="JPEG", quality=q, subsampling=NvJpegEncodeContext._SUBSAMPLING[surf.Format])
+                out, format="JPEG", quality=q, subsampling=list(NvJpegEncodeContext._SAMPLINGS).index(context.Subsampling()))
             buffers.append(np.frombuffer(out.getvalue(), np.uint8).copy())
         return buffers, TaskExecInfo.SUCCESS
 
     # ---- hip backend ----------------------------------------------------------------------------------------------------
-    def _jpeg_params(self, quality: int, fmt: PixelFormat):
-        key = (quality, int(fmt))
+    def _jpeg_params(self, quality: int, fmt: PixelFormat, samp: str):
+        key = (quality, int(fmt), samp)
         if key not in self._params:
-            self._params[key] = shim.jpeg_params_init(quality, int(fmt))
+            h_samp, v_samp = NvJpegEncodeContext._SAMPLINGS[samp]
+            self._params[key] = shim.jpeg_params_init_sampled(quality, int(fmt), h_samp, v_samp)
         return self._params[key]
 
-    def _header(self, w: int, h: int, fmt: PixelFormat, quality: int) -> np.ndarray:
-        key = (w, h, int(fmt), quality)
+    def _header(self, w: int, h: int, fmt: PixelFormat, quality: int, samp: str) -> np.ndarray:
+        key = (w, h, int(fmt), quality, samp)
         if key not in self._headers:
-            self._headers[key] = np.frombuffer(shim.jpeg_header(w, h, self._jpeg_params(quality, fmt)), np.uint8)
+            self._headers[key] = np.frombuffer(shim.jpeg_header(w, h, self._jpeg_params(quality, fmt, samp)), np.uint8)
         return self._headers[key]
 
     def _grow(self, name: str, need: int) -> int:
@@ -860,7 +879,8 @@ class PyNvJpegEncoder:
             if (fmt == F.YUV420 and (w | h) & 1) or (fmt == F.YUV422 and w & 1):
                 return [], TaskExecInfo.FAIL
         q = max(1, min(100, context.Compression()))
-        params = self._jpeg_params(q, fmt)
+        samp = context.Subsampling()
+        params = self._jpeg_params(q, fmt, samp)
         groups = {}
         for i, surf in enumerate(surfaces):
             groups.setdefault((surf.Width, surf.Height), []).append(i)
@@ -881,7 +901,7 @@ class PyNvJpegEncoder:
                 shim.stream_sync(g, s)
             finally:
                 shim.mem_free(g, d_src)
-            hdr = self._header(w, h, fmt, q)
+            hdr = self._header(w, h, fmt, q, samp)
             for k, i in enumerate(idx):             # one exact D2H copy per image, between its header and EOI
                 size = int(sizes[k])
                 buf = np.empty(hdr.size + size + 2, np.uint8)

@@ -7,6 +7,8 @@
 //   k_jpeg_fdct      lane = one 8x8 block of one component, in MCU-interleaved scan order: load (edge replication,
 //                    rgb_ycc for RGB sources), islow FDCT, quantise, zigzag -> 128 B of int16 in the workspace.
 //                    A dummy block of a partial MCU computes the block whose DC it copies and keeps only that DC.
+//                    RGB sources coded 4:2:2 / 4:2:0: a luma lane also averages the chroma of its 8x8 pixels (jcsample)
+//                    and hands it to the MCU's chroma lanes through LDS (fdct_subsampled).
 //   k_jpeg_huff      wave = one restart segment (<= 64 blocks), lane = one block: count the bits of each block,
 //                    prefix-sum them into bit offsets, OR the codes into an LDS bit buffer (ds_or_b32), pad with
 //                    1-bits, then stuff a 0x00 after every 0xFF (per-chunk counts + prefix sum) into the segment's
@@ -120,6 +122,20 @@ int jpeg_sampling(int format, int* H, int* V) {
   }
 }
 
+bool jpeg_is_rgb(int format) {
+  return format == VALI_FMT_RGB || format == VALI_FMT_BGR || format == VALI_FMT_RGB_PLANAR;
+}
+
+// the luma samplings a format can be coded with: its own; RGB sources also 2x1 and 2x2 (chroma is downsampled)
+bool jpeg_sampling_ok(int format, int h_samp, int v_samp) {
+  int H, V;
+  if (!jpeg_sampling(format, &H, &V))
+    return false;
+  if (h_samp == H && v_samp == V)
+    return true;
+  return jpeg_is_rgb(format) && h_samp == 2 && (v_samp == 1 || v_samp == 2);
+}
+
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // checks params and sizes; fills g (workspace layout for a batch of n)
@@ -131,9 +147,10 @@ int jpeg_geom(const char* fn, int n, int w, int h, const vali_jpeg_params* p, Jp
   int H, V;
   if (!jpeg_sampling(p->format, &H, &V))
     return fail(VALI_ERR_UNSUPPORTED, "%s: format %d cannot be encoded", fn, p->format);
-  if (p->h_samp != H || p->v_samp != V)
+  if (!jpeg_sampling_ok(p->format, p->h_samp, p->v_samp))
     return fail(VALI_ERR_INVALID_ARG, "%s: sampling %dx%d does not match format %d", fn, p->h_samp, p->v_samp,
                 p->format);
+  H = p->h_samp, V = p->v_samp;
   if (!subsampled_sizes_ok(p->format, w, h))
     return fail(VALI_ERR_INVALID_ARG, "%s: %d x %d: 4:2:0 needs an even width and height, 4:2:2 an even width", fn,
                 w, h);
@@ -263,61 +280,188 @@ __device__ __forceinline__ void fdct_pass(int* d) {
   d[S] = descale(t7 + z1 + z4, sh);
 }
 
-template <int SRC>
-__global__ void __launch_bounds__(256) k_jpeg_fdct(const FdctArgs a) {
-  const int gb = blockIdx.x * 256 + threadIdx.x;
-  if (gb >= a.nblocks)
-    return;
-  const vali_surface s = a.d_src[blockIdx.y];
-  const int mcu = gb / a.bpm, p = gb - mcu * a.bpm;
-  const int mx = mcu % a.mcux, my = mcu / a.mcux;
-  const int c = p < a.HV ? 0 : p - a.HV + 1;
-  int bx = c ? mx : mx * a.H + p % a.H;
-  int by = c ? my : my * a.V + p / a.H;
-  const int bw = c ? a.bw[1] : a.bw[0], bh = c ? a.bh[1] : a.bh[0];
-  const int cw = c ? a.cw[1] : a.cw[0], ch = c ? a.ch[1] : a.ch[0];
-  // a dummy block of a partial MCU computes the block whose DC it copies (jccoefct): the block to its left, for a
-  // dummy row the last block of the row above in this MCU -- always a real block after clamping
-  const bool dummy = bx >= bw || by >= bh;
-  if (by >= bh) {
-    bx = c ? mx : mx * a.H + a.H - 1;
-    by = bh - 1;
-  }
-  bx = min(bx, bw - 1);
+// CS: chroma sampling of an RGB source, 0 = 1x1 (4:4:4), 1 = 2x1 (4:2:2), 2 = 2x2 (4:2:0)
+template <int CS>
+struct SubGeom {
+  static constexpr int V = CS == 2 ? 2 : 1, HV = 2 * V, BPM = HV + 2;
+  static constexpr int MPW = 256 / BPM;  // whole MCUs of one workgroup: 64 (all 256 lanes) / 42 (252 lanes)
+  static constexpr int NQ = 8 / V;       // dwords of one component of one quadrant: its rows of 4 chroma samples
+  static constexpr int STRIDE = 2 * HV * NQ + 1;  // dwords of one MCU in LDS: 32, + 1 so that MCUs start on different banks
+};
 
-  int d[64];
-  const int x0 = bx * 8;
+// One 8x8 quadrant of an MCU of a subsampled RGB source, pixel columns x0.. (replicated at column w - 1) and rows y0..:
+// LUMA: d = Y - 128.  CHROMA: cq[0 / 1][k] = row k of the quadrant's 4 wide Cb / Cr samples, one byte each: jccolor on
+// every pixel, truncated to 8 bits, then jcsample's h2v1 / h2v2 average with its alternating bias (0, 1 / 1, 2; the
+// quadrant starts on an even chroma column).  Rows are replicated as the component wants them: luma at row h - 1;
+// chroma (CROWS) at 4:2:0 in pairs, row 2 y' + (Y & 1) of y' = min(Y / 2, ch - 1) -- the same row wherever Y < h.
+template <int SRC, int CS, bool LUMA, bool CHROMA, bool CROWS>
+__device__ __forceinline__ void load_quadrant(const vali_surface& s, int x0, int y0, int w, int h, int ch, int* d,
+                                              u32 (*cq)[SubGeom<CS>::NQ]) {
+  int even[2][4];  // 4:2:0: the horizontal sums of the even row
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
-    const int y = min(by * 8 + r, ch - 1);
-    int* v = d + 8 * r;
-    if (SRC == SRC_YUV) {
-      const u8* plane = (const u8*)(c == 0 ? s.plane[0] : c == 1 ? s.plane[1] : s.plane[2]);
-      const int pitch = c == 0 ? s.pitch[0] : c == 1 ? s.pitch[1] : s.pitch[2];
-      load_row_u8(plane + (size_t)y * pitch, x0, cw, v);
+    const int Y = y0 + r;
+    const int y = CROWS && CS == 2 ? min(2 * min(Y >> 1, ch - 1) + (Y & 1), h - 1) : min(Y, h - 1);
+    int R[8], G[8], B[8];
+    if (SRC == SRC_RGB_PLANAR) {
+      load_row_u8((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, w, R);
+      load_row_u8((const u8*)s.plane[1] + (size_t)y * s.pitch[1], x0, w, G);
+      load_row_u8((const u8*)s.plane[2] + (size_t)y * s.pitch[2], x0, w, B);
+    } else if (SRC == SRC_RGB) {
+      load_row_rgb((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, w, R, G, B);
     } else {
-      int R[8], G[8], B[8];
-      if (SRC == SRC_RGB_PLANAR) {
-        load_row_u8((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, cw, R);
-        load_row_u8((const u8*)s.plane[1] + (size_t)y * s.pitch[1], x0, cw, G);
-        load_row_u8((const u8*)s.plane[2] + (size_t)y * s.pitch[2], x0, cw, B);
-      } else if (SRC == SRC_RGB) {
-        load_row_rgb((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, cw, R, G, B);
-      } else {
-        load_row_rgb((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, cw, B, G, R);
-      }
-      // jccolor rgb_ycc_convert: this lane's component only
-      const int kr = c == 0 ? fix16(0.299) : c == 1 ? -fix16(0.16874) : fix16(0.5);
-      const int kg = c == 0 ? fix16(0.587) : c == 1 ? -fix16(0.33126) : -fix16(0.41869);
-      const int kb = c == 0 ? fix16(0.114) : c == 1 ? fix16(0.5) : -fix16(0.08131);
-      const int off = c == 0 ? (1 << 15) : (128 << 16) + (1 << 15) - 1;
+      load_row_rgb((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, w, B, G, R);
+    }
+    if (LUMA) {
 #pragma unroll
       for (int i = 0; i < 8; ++i)
-        v[i] = (kr * R[i] + kg * G[i] + kb * B[i] + off) >> 16;
+        d[8 * r + i] = ((fix16(0.299) * R[i] + fix16(0.587) * G[i] + fix16(0.114) * B[i] + (1 << 15)) >> 16) - 128;
     }
+    if (CHROMA) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i)
-      v[i] -= 128;
+      for (int k = 0; k < 2; ++k) {
+        const int kr = k == 0 ? -fix16(0.16874) : fix16(0.5);
+        const int kg = k == 0 ? -fix16(0.33126) : -fix16(0.41869);
+        const int kb = k == 0 ? fix16(0.5) : -fix16(0.08131);
+        constexpr int off = (128 << 16) + (1 << 15) - 1;
+        u32 packed = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int sum = ((kr * R[2 * j] + kg * G[2 * j] + kb * B[2 * j] + off) >> 16) +
+                          ((kr * R[2 * j + 1] + kg * G[2 * j + 1] + kb * B[2 * j + 1] + off) >> 16);
+          if (CS == 1)
+            packed |= (u32)((sum + (j & 1)) >> 1) << (8 * j);
+          else if ((r & 1) == 0)
+            even[k][j] = sum;
+          else
+            packed |= (u32)((even[k][j] + sum + 1 + (j & 1)) >> 2) << (8 * j);
+        }
+        if (CS == 1)
+          cq[k][r] = packed;
+        else if (r & 1)
+          cq[k][r / 2] = packed;
+      }
+    }
+  }
+}
+
+// CS != 0, a subsampled RGB source: the lane of a luma block loads its 8x8 pixels once, keeps Y and hands the 4 wide Cb
+// and Cr samples of its quadrant of the MCU to the MCU's two chroma lanes through LDS; a chroma lane that loaded its own
+// 16 x 8 or 16 x 16 pixels would do so while the luma lanes of its wave wait.  A workgroup holds whole MCUs (the last
+// 256 % BPM lanes idle); the order of the blocks in the workspace stays the MCU-interleaved scan order.
+template <int SRC, int CS>
+__global__ void __launch_bounds__(256) k_jpeg_fdct(const FdctArgs a) {
+  static_assert(CS == 0 || SRC != SRC_YUV, "planar YUV sources bring their own chroma planes");
+  int d[64];
+  int gb, c;
+  bool dummy;
+  if constexpr (CS != 0) {
+    using SG = SubGeom<CS>;
+    __shared__ u32 s_c[SG::MPW * SG::STRIDE];
+    const int ml = threadIdx.x / SG::BPM, p = threadIdx.x - ml * SG::BPM;
+    gb = blockIdx.x * (SG::MPW * SG::BPM) + threadIdx.x;
+    const bool act = ml < SG::MPW && gb < a.nblocks;
+    const int mcu = blockIdx.x * SG::MPW + ml;
+    const int mx = mcu % a.mcux, my = mcu / a.mcux;
+    c = p < SG::HV ? 0 : p - SG::HV + 1;
+    dummy = false;  // a chroma block of an MCU is always real: mcux = bw[1], mcuy = bh[1]
+    if (act && c == 0) {
+      const vali_surface s = a.d_src[blockIdx.y];
+      const int w = a.cw[0], h = a.ch[0];
+      const int bx = mx * 2 + (p & 1), by = my * SG::V + (p >> 1);
+      dummy = bx >= a.bw[0] || by >= a.bh[0];
+      u32 cq[2][SG::NQ];
+      // A dummy block codes the block whose DC it copies (jccoefct: the block to its left, for a dummy row the last block
+      // of the row above in this MCU) but still owns the chroma of its own quadrant, and at 4:2:0 the bottom blocks
+      // replicate rows for chroma in another way than for luma: those few take their chroma from a pass of its own.
+      // It comes first, while d is not live yet.
+      const bool own = dummy || (CS == 2 && by * 8 + 8 > h);
+      u32 cown[2][SG::NQ] = {};
+      if (own)
+        load_quadrant<SRC, CS, false, true, true>(s, bx * 8, by * 8, w, h, a.ch[1], d, cown);
+      int lx = bx, ly = by;
+      if (by >= a.bh[0]) {
+        lx = mx * 2 + 1;
+        ly = a.bh[0] - 1;
+      }
+      lx = min(lx, a.bw[0] - 1);
+      load_quadrant<SRC, CS, true, true, false>(s, lx * 8, ly * 8, w, h, a.ch[1], d, cq);
+      u32* o = s_c + ml * SG::STRIDE + p * SG::NQ;
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int i = 0; i < SG::NQ; ++i)
+          o[k * SG::HV * SG::NQ + i] = own ? cown[k][i] : cq[k][i];
+    }
+    __syncthreads();
+    if (!act)
+      return;
+    if (c) {
+      const u32* in = s_c + ml * SG::STRIDE + (c - 1) * SG::HV * SG::NQ;
+#pragma unroll
+      for (int q = 0; q < SG::HV; ++q)
+#pragma unroll
+        for (int i = 0; i < SG::NQ; ++i) {
+          const u32 v = in[q * SG::NQ + i];
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            d[8 * (SG::NQ * (q >> 1) + i) + 4 * (q & 1) + j] = (int)((v >> (8 * j)) & 0xFF) - 128;
+        }
+    }
+  } else {
+    gb = blockIdx.x * 256 + threadIdx.x;
+    if (gb >= a.nblocks)
+      return;
+    const vali_surface s = a.d_src[blockIdx.y];
+    const int mcu = gb / a.bpm, p = gb - mcu * a.bpm;
+    const int mx = mcu % a.mcux, my = mcu / a.mcux;
+    c = p < a.HV ? 0 : p - a.HV + 1;
+    int bx = c ? mx : mx * a.H + p % a.H;
+    int by = c ? my : my * a.V + p / a.H;
+    const int bw = c ? a.bw[1] : a.bw[0], bh = c ? a.bh[1] : a.bh[0];
+    const int cw = c ? a.cw[1] : a.cw[0], ch = c ? a.ch[1] : a.ch[0];
+    // a dummy block of a partial MCU computes the block whose DC it copies (jccoefct): the block to its left, for a
+    // dummy row the last block of the row above in this MCU -- always a real block after clamping
+    dummy = bx >= bw || by >= bh;
+    if (by >= bh) {
+      bx = c ? mx : mx * a.H + a.H - 1;
+      by = bh - 1;
+    }
+    bx = min(bx, bw - 1);
+
+    const int x0 = bx * 8;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int y = min(by * 8 + r, ch - 1);
+      int* v = d + 8 * r;
+      if (SRC == SRC_YUV) {
+        const u8* plane = (const u8*)(c == 0 ? s.plane[0] : c == 1 ? s.plane[1] : s.plane[2]);
+        const int pitch = c == 0 ? s.pitch[0] : c == 1 ? s.pitch[1] : s.pitch[2];
+        load_row_u8(plane + (size_t)y * pitch, x0, cw, v);
+      } else {
+        int R[8], G[8], B[8];
+        if (SRC == SRC_RGB_PLANAR) {
+          load_row_u8((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, cw, R);
+          load_row_u8((const u8*)s.plane[1] + (size_t)y * s.pitch[1], x0, cw, G);
+          load_row_u8((const u8*)s.plane[2] + (size_t)y * s.pitch[2], x0, cw, B);
+        } else if (SRC == SRC_RGB) {
+          load_row_rgb((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, cw, R, G, B);
+        } else {
+          load_row_rgb((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, cw, B, G, R);
+        }
+        // jccolor rgb_ycc_convert: this lane's component only
+        const int kr = c == 0 ? fix16(0.299) : c == 1 ? -fix16(0.16874) : fix16(0.5);
+        const int kg = c == 0 ? fix16(0.587) : c == 1 ? -fix16(0.33126) : -fix16(0.41869);
+        const int kb = c == 0 ? fix16(0.114) : c == 1 ? fix16(0.5) : -fix16(0.08131);
+        const int off = c == 0 ? (1 << 15) : (128 << 16) + (1 << 15) - 1;
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          v[i] = (kr * R[i] + kg * G[i] + kb * B[i] + off) >> 16;
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        v[i] -= 128;
+    }
   }
 #pragma unroll
   for (int r = 0; r < 8; ++r)
@@ -633,6 +777,17 @@ void reciprocal(int q, u32* recip, u32* corr_shift) {
   *corr_shift = c | ((u32)r << 16);
 }
 
+// an RGB source with chroma sampling cs: 0 = 1x1, 1 = 2x1, 2 = 2x2
+template <int SRC>
+void launch_fdct(int cs, dim3 grid, hipStream_t s, const FdctArgs& f) {
+  if (cs == 0)
+    hipLaunchKernelGGL((k_jpeg_fdct<SRC, 0>), grid, dim3(256), 0, s, f);
+  else if (cs == 1)
+    hipLaunchKernelGGL((k_jpeg_fdct<SRC, 1>), grid, dim3(256), 0, s, f);
+  else
+    hipLaunchKernelGGL((k_jpeg_fdct<SRC, 2>), grid, dim3(256), 0, s, f);
+}
+
 } // namespace
 } // namespace vali
 
@@ -645,6 +800,17 @@ int vali_jpeg_params_init(int quality, int format, vali_jpeg_params* out) {
   int H, V;
   if (!jpeg_sampling(format, &H, &V))
     return fail(VALI_ERR_UNSUPPORTED, "%s: format %d cannot be encoded", __func__, format);
+  return vali_jpeg_params_init_sampled(quality, format, H, V, out);
+}
+
+int vali_jpeg_params_init_sampled(int quality, int format, int h_samp, int v_samp, vali_jpeg_params* out) {
+  VALI_REQUIRE(out, "null output");
+  int H, V;
+  if (!jpeg_sampling(format, &H, &V))
+    return fail(VALI_ERR_UNSUPPORTED, "%s: format %d cannot be encoded", __func__, format);
+  if (!jpeg_sampling_ok(format, h_samp, v_samp))
+    return fail(VALI_ERR_INVALID_ARG, "%s: sampling %dx%d does not fit format %d", __func__, h_samp, v_samp, format);
+  H = h_samp, V = v_samp;
   memset(out, 0, sizeof(*out));
   const int q = quality < 1 ? 1 : quality > 100 ? 100 : quality;
   const int scale = q < 50 ? 5000 / q : 200 - 2 * q;  // jpeg_quality_scaling
@@ -729,19 +895,22 @@ int vali_jpeg_encode_batch(const vali_surface* d_src, int n, int width, int heig
 
   hipStream_t s = as_stream(stream);
   VALI_ENTRY(s);
-  const dim3 fgrid((g.nblocks + 255) / 256, n);
+  // a subsampled RGB source: workgroups of whole MCUs (fdct_subsampled)
+  const int cs = jpeg_is_rgb(format) ? g.H * g.V / 2 : 0;  // 0 = 1x1, 1 = 2x1, 2 = 2x2
+  const int per_wg = cs ? 256 / g.bpm * g.bpm : 256;
+  const dim3 fgrid((g.nblocks + per_wg - 1) / per_wg, n);
   switch (format) {
   case VALI_FMT_RGB:
-    hipLaunchKernelGGL(k_jpeg_fdct<SRC_RGB>, fgrid, dim3(256), 0, s, f);
+    launch_fdct<SRC_RGB>(cs, fgrid, s, f);
     break;
   case VALI_FMT_BGR:
-    hipLaunchKernelGGL(k_jpeg_fdct<SRC_BGR>, fgrid, dim3(256), 0, s, f);
+    launch_fdct<SRC_BGR>(cs, fgrid, s, f);
     break;
   case VALI_FMT_RGB_PLANAR:
-    hipLaunchKernelGGL(k_jpeg_fdct<SRC_RGB_PLANAR>, fgrid, dim3(256), 0, s, f);
+    launch_fdct<SRC_RGB_PLANAR>(cs, fgrid, s, f);
     break;
   default:
-    hipLaunchKernelGGL(k_jpeg_fdct<SRC_YUV>, fgrid, dim3(256), 0, s, f);
+    hipLaunchKernelGGL((k_jpeg_fdct<SRC_YUV, 0>), fgrid, dim3(256), 0, s, f);
     break;
   }
   VALI_LAUNCH_CHECK();

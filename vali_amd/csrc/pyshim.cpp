@@ -549,6 +549,11 @@ PYBIND11_MODULE(_vali_shim, m) {
     check(vali_jpeg_params_init(quality, format, &j.p), "vali_jpeg_params_init");
     return j;
   });
+  m.def("jpeg_params_init_sampled", [](int quality, int format, int h_samp, int v_samp) {
+    JpegParams j;
+    check(vali_jpeg_params_init_sampled(quality, format, h_samp, v_samp, &j.p), "vali_jpeg_params_init_sampled");
+    return j;
+  });
   m.def("jpeg_header", [](int width, int height, const JpegParams& j) {
     size_t len = 0;
     check(vali_jpeg_header(width, height, &j.p, nullptr, 0, &len), "vali_jpeg_header");
