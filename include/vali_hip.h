@@ -347,6 +347,45 @@ VALI_API int vali_rgb_preproc_roi_batch(const vali_surface* d_src, const vali_su
                                         const vali_preproc_params* params, int pad, const uint8_t pad_rgb[3],
                                         vali_stream_t stream);
 
+/*
+ * Regions into ONE batch tensor: the network's input itself, float32, float16 or bfloat16, with no surfaces in
+ * between.  For item i, colour c (0 = R, 1 = G, 2 = B by name, whatever the source's memory order) and pixel (x, y) of
+ * the canvas dst->width x dst->height:
+ *   element (i, c, y, x) = convert(dtype, v),
+ *   v = the float32 that vali_nv12_preproc_roi_batch / vali_rgb_preproc_roi_batch write to a VALI_FMT_RGB_32F_PLANAR
+ *       destination of the canvas size from the same sources, rectangle records, parameters and pad colour.
+ * convert: the identity for VALI_DTYPE_F32; IEEE round-to-nearest-even for VALI_DTYPE_F16 (subnormals are kept,
+ * magnitudes that round past 65504 become +-inf) and for VALI_DTYPE_BF16.  Element (i, c, y, x) lies at
+ *   planar (packed == 0):        data + (i * stride_n + c * stride_c + y * stride_y + x) * element size
+ *   channels last (packed == 1): data + (i * stride_n + y * stride_y + 3 * x + c) * element size
+ * so a contiguous (N, 3, H, W) tensor, any slice of it that keeps rows contiguous, and a channels-last tensor all
+ * fit as they are.  With pad == 0 elements outside the placement are not written.
+ * d_src is a DEVICE array of dst->n descriptors (NV12 of even size / all of src_format: RGB, BGR or RGB_PLANAR);
+ * d_roi is a DEVICE array of dst->n records, sanitised on the device by the rules of the batched forms above, or
+ * NULL: every item is its whole source onto the whole canvas.  dst is a HOST struct that travels in the kernel
+ * arguments.  One launch; nothing is allocated, nothing synchronises.
+ * VALI_ERR_INVALID_ARG, before any device is touched, for: null arguments; dtype or packed out of range; n outside
+ * 1..65535; a canvas below 1 x 1 (NV12: below 2 x 2 or odd); strides <= 0; stride_y below the row's extent (width,
+ * 3 * width when packed); data not aligned to the element; a row pitch of 2 GiB or more or a plane (height x pitch,
+ * in bytes) of 4 GiB or more; pad without a colour.  VALI_ERR_UNSUPPORTED for a src_format outside the list.
+ */
+enum vali_dtype { VALI_DTYPE_F32 = 0, VALI_DTYPE_F16 = 1, VALI_DTYPE_BF16 = 2 };
+typedef struct vali_tensor_dst {
+  void* data;               /* device memory, aligned to the element size */
+  int32_t dtype;            /* enum vali_dtype */
+  int32_t packed;           /* 0: planar, x stride 1.  1: channels last, c stride 1, x stride 3 */
+  int32_t n, width, height; /* items, canvas size */
+  int32_t reserved;
+  int64_t stride_n, stride_c, stride_y; /* in ELEMENTS; stride_c is ignored when packed */
+} vali_tensor_dst;                      /* 56 bytes */
+
+VALI_API int vali_nv12_preproc_roi_tensor(const vali_surface* d_src, const vali_roi* d_roi,
+                                          const vali_tensor_dst* dst, const vali_preproc_params* params, int pad,
+                                          const uint8_t pad_rgb[3], vali_stream_t stream);
+VALI_API int vali_rgb_preproc_roi_tensor(const vali_surface* d_src, const vali_roi* d_roi, int src_format,
+                                         const vali_tensor_dst* dst, const vali_preproc_params* params, int pad,
+                                         const uint8_t pad_rgb[3], vali_stream_t stream);
+
 /* ---- JPEG: baseline sequential JFIF encoder ------------------------------------------------
  *
  * The reference's PyNvJpegEncoder (src/TC/src/TaskNvJpegEncode.cpp) on nvJPEG.  Definition (tests/jpeg_model.py

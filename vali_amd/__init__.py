@@ -19,7 +19,7 @@ if not _BUILDING:
     from .surface import Surface, SurfacePlane
     from .buffer import CudaBuffer
     from .tasks import (PySurfaceConverter, PySurfacePreprocessor, PySurfaceResizer, PySurfaceRotator, PySurfaceUD,
-                        RoiBatch, SurfaceBatch, letterbox_rect)
+                        RoiBatch, SurfaceBatch, TensorBatch, letterbox_rect)
     from .pipeline import BatchedFramePipeline, broadcast_coefficients, shard_frames
     from .transfer import PyFrameUploader, PySurfaceDownloader
     from . import tuning

@@ -339,7 +339,108 @@ struct RoiArgs {
   int row_pairs; // row pairs a wave walks
   int pad;       // 0: pixels outside the placement are not written
   u32 pad_rgb;   // R | G << 8 | B << 16
+  vali_tensor_dst tdst; // the tensor forms (DST != TD_SURF): the destination of every item, instead of d_dst / dst
+  int whole;            // the tensor forms of NV12: no rectangle records, every item is its whole source onto the canvas
 };
+
+// DST: where the float outputs go.  TD_SURF: the items' own surfaces (d_dst / dst), float32.  TD_F32 / TD_F16 / TD_BF16:
+// ONE batch tensor of that element type (a.tdst; OUT names its layout: PP_F32_PLANAR x stride 1, PP_F32_PACKED channels
+// last).  The 16-bit forms convert WHEN THE TABLE IS FILLED (a u16 table) and convert the pad colour once: the per-pixel
+// path moves finished bits and contains no conversion, so each element is convert(the float32 of the surface form) by
+// construction.
+enum : int { TD_SURF = 0, TD_F32 = 1, TD_F16 = 2, TD_BF16 = 3 };
+
+// float32 -> float16 bits, IEEE round-to-nearest-even in integers: independent of the wave's denormal mode (subnormal
+// results are kept), magnitudes of 65520 and more give +-inf, NaN gives a quiet NaN.  torch.Tensor.to(torch.float16).
+__device__ __forceinline__ u32 f32_to_f16_bits(float v) {
+  const u32 x = __builtin_bit_cast(u32, v);
+  const u32 sign = (x >> 16) & 0x8000u, a = x & 0x7fffffffu;
+  if (a > 0x7f800000u)
+    return sign | 0x7e00u;
+  if (a >= 0x477ff000u) // 65520 = the tie between 65504 and 2^16, and everything above it
+    return sign | 0x7c00u;
+  if (a >= 0x38800000u) { // 2^-14 and more: a normal half; the carry of the rounding walks into the exponent
+    const u32 r = a - 0x38000000u;
+    return sign | ((r + 0xfffu + ((r >> 13) & 1u)) >> 13);
+  }
+  const u32 e = a >> 23;
+  if (e < 102u) // below 2^-25: under half of the smallest subnormal (2^-25 itself is the tie with 0, handled below)
+    return sign;
+  // subnormal half: m * 2^(e - 150) in units of 2^-24 = m >> (126 - e), remainder rounded half to even
+  const u32 m = (a & 0x7fffffu) | 0x800000u, sh = 126u - e; // sh = 14..24
+  u32 q = m >> sh;
+  const u32 rem = m & ((1u << sh) - 1u), half = 1u << (sh - 1u);
+  if (rem > half || (rem == half && (q & 1u)))
+    ++q;
+  return sign | q;
+}
+
+// float32 -> bfloat16 bits, round-to-nearest-even (torch.Tensor.to(torch.bfloat16)); NaN gives a quiet NaN
+__device__ __forceinline__ u32 f32_to_bf16_bits(float v) {
+  const u32 x = __builtin_bit_cast(u32, v);
+  if ((x & 0x7fffffffu) > 0x7f800000u)
+    return (x >> 16) | 0x40u;
+  return (x + 0x7fffu + ((x >> 16) & 1u)) >> 16;
+}
+
+// a table entry / an output element of the form DST: the float itself, or the finished 16 bits
+template <int DST> struct TdElem {
+  typedef float lut_t;
+  typedef float val_t;
+  static __device__ __forceinline__ float make(float v) { return v; }
+};
+template <> struct TdElem<TD_F16> {
+  typedef uint16_t lut_t;
+  typedef u32 val_t;
+  static __device__ __forceinline__ u32 make(float v) { return f32_to_f16_bits(v); }
+};
+template <> struct TdElem<TD_BF16> {
+  typedef uint16_t lut_t;
+  typedef u32 val_t;
+  static __device__ __forceinline__ u32 make(float v) { return f32_to_bf16_bits(v); }
+};
+
+// item `frame` of the batch tensor as the planes of a surface: addresses in 64 bits, the pitch in bytes (the host has
+// checked that it and height x pitch fit the 32-bit in-plane offset)
+template <int ESIZE> __device__ __forceinline__ SurfRef tensor_ref(const vali_tensor_dst& t, u32 frame) {
+  SurfRef r;
+  uint8_t* base = (uint8_t*)t.data + (long long)frame * t.stride_n * ESIZE;
+  r.p[0] = base;
+  r.p[1] = base + (t.packed ? 0 : t.stride_c * ESIZE);
+  r.p[2] = base + (t.packed ? 0 : 2 * t.stride_c * ESIZE);
+  r.pitch[0] = r.pitch[1] = r.pitch[2] = (int)(t.stride_y * ESIZE);
+  r.width = t.width; r.height = t.height;
+  return r;
+}
+
+// the 16-bit stores of one lane and row: 4 elements of a plane (8 bytes) / its 4 channels-last pixels (24 bytes) as
+// 8-byte stores when the lane has all 4 pixels and the address is 8-byte aligned, single elements under wr[] otherwise
+// (a view whose rows start 2, 4 or 6 bytes off): every access naturally aligned
+__device__ __forceinline__ void store_h4_planar(uint8_t* q, const u32 (&o)[4], bool full, const bool (&wr)[4]) {
+  if (full && (((uintptr_t)q) & 7u) == 0) {
+    const v2u32 w = {o[0] | o[1] << 16, o[2] | o[3] << 16};
+    gstore_nt<v2u32>(q, w); // a wave writes 512 contiguous bytes: whole lines, as the f32 planar form
+  } else {
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+      if (wr[p]) gstore<uint16_t>(q + 2 * p, (uint16_t)o[p]);
+  }
+}
+__device__ __forceinline__ void store_h4_packed(uint8_t* q, const u32 (&o)[3][4], bool full, const bool (&wr)[4]) {
+  if (full && (((uintptr_t)q) & 7u) == 0) {
+    const v2u32 w0 = {o[0][0] | o[1][0] << 16, o[2][0] | o[0][1] << 16};
+    const v2u32 w1 = {o[1][1] | o[2][1] << 16, o[0][2] | o[1][2] << 16};
+    const v2u32 w2 = {o[2][2] | o[0][3] << 16, o[1][3] | o[2][3] << 16};
+    gstore<v2u32>(q, w0); gstore<v2u32>(q + 8, w1); gstore<v2u32>(q + 16, w2);
+  } else {
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+      if (wr[p]) {
+        gstore<uint16_t>(q + 6 * p, (uint16_t)o[0][p]); gstore<uint16_t>(q + 6 * p + 2, (uint16_t)o[1][p]);
+        gstore<uint16_t>(q + 6 * p + 4, (uint16_t)o[2][p]);
+      }
+  }
+}
 
 // step 3 of the definition for (channel c, u8 value q): the operations of k_nv12_preproc's table
 __device__ __forceinline__ float preproc_step3(int q, int c, const vali_preproc_params& prm) {
@@ -380,19 +481,32 @@ __device__ __forceinline__ void roi_clamp(int& x, int& w, int size) {
   w = min(max(w, 0), size - x) & ~1;
 }
 
-template <int OUT, bool TALL>
+template <int OUT, bool TALL, int DST = TD_SURF>
 __global__ void __launch_bounds__(kBlock) k_nv12_preproc_roi(const RoiArgs a) {
   constexpr bool kFloat = OUT == PP_F32_PLANAR || OUT == PP_F32_PACKED;
+  constexpr bool kHalf = DST == TD_F16 || DST == TD_BF16; // 16-bit elements: finished bits from the table on
+  static_assert(DST == TD_SURF || kFloat, "the tensor forms are float layouts");
   constexpr int kTileW = TALL ? kWave * 4 : kPpTileW;
-  __shared__ float lut[kFloat ? 3 : 1][256];
+  typedef TdElem<DST> Elem;
+  __shared__ typename Elem::lut_t lut[kFloat ? 3 : 1][256];
   u32 tile_x, tile_y, frame;
   if (!tile_of_block(a.map, tile_x, tile_y, frame))
     return;
   const SurfRef s = surf_ref(load_uniform(a.d_src, a.src, frame));
-  const SurfRef d = surf_ref(load_uniform(a.d_dst, a.dst, frame));
+  SurfRef d;
+  if constexpr (DST == TD_SURF)
+    d = surf_ref(load_uniform(a.d_dst, a.dst, frame));
+  else
+    d = tensor_ref<kHalf ? 2 : 4>(a.tdst, frame);
   const vali_roi r = load_uniform(a.d_roi, a.roi, frame);
   int sx = r.src_x, sy = r.src_y, sw = r.src_w, sh = r.src_h;
   int dx = r.dst_x, dy = r.dst_y, dw = r.dst_w, dh = r.dst_h;
+  if constexpr (DST != TD_SURF) {
+    if (a.whole) {
+      sx = sy = dx = dy = 0;
+      sw = s.width; sh = s.height; dw = d.width; dh = d.height;
+    }
+  }
   roi_clamp(sx, sw, s.width);
   roi_clamp(sy, sh, s.height);
   const int cw = max(d.width, 0) & ~1, ch = max(d.height, 0) & ~1; // the canvas
@@ -410,7 +524,7 @@ __global__ void __launch_bounds__(kBlock) k_nv12_preproc_roi(const RoiArgs a) {
   if constexpr (kFloat) {
     if (hits) {
       for (int e = threadIdx.x; e < 3 * 256; e += kBlock)
-        lut[e >> 8][e & 255] = preproc_step3(e & 255, e >> 8, a.prm);
+        lut[e >> 8][e & 255] = Elem::make(preproc_step3(e & 255, e >> 8, a.prm));
       __syncthreads();
     }
   }
@@ -425,12 +539,13 @@ __global__ void __launch_bounds__(kBlock) k_nv12_preproc_roi(const RoiArgs a) {
   // pair is wholly inside or wholly outside the placement
   const bool in0 = hits && x0 >= dx && x0 < dx + dw;
   const bool in1 = hits && x0 + 2 >= dx && x0 + 2 < dx + dw;
-  float pv[3]; // the pad colour: the normalised value (float outputs) or the byte (8-bit outputs)
+  // the pad colour: the normalised value (float outputs; its finished bits for 16-bit elements) or the byte (8-bit outputs)
+  typename Elem::val_t pv[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const int q = (a.pad_rgb >> (8 * c)) & 255u;
-    const float v = kFloat ? preproc_step3(q, c, a.prm) : (float)q;
-    pv[c] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); // uniform: SGPRs
+    const auto v = kFloat ? Elem::make(preproc_step3(q, c, a.prm)) : Elem::make((float)q);
+    pv[c] = __builtin_bit_cast(typename Elem::val_t, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); // uniform: SGPRs
   }
 
   // the view of the crop, and the resize geometry of view -> view (k_nv12_preproc's expressions)
@@ -535,7 +650,7 @@ __global__ void __launch_bounds__(kBlock) k_nv12_preproc_roi(const RoiArgs a) {
 #pragma unroll 1
     for (int rr = 0; rr < 2; ++rr) {
       const int y = y0 + rr;
-      float o[3][4]; // [channel][pixel]: float outputs the final value, 8-bit outputs the pre-quantised one
+      typename Elem::val_t o[3][4]; // [channel][pixel]: float outputs the final value, 8-bit outputs the pre-quantised one
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
         const bool inside = p < 2 ? c0 : c1;
@@ -552,7 +667,16 @@ __global__ void __launch_bounds__(kBlock) k_nv12_preproc_roi(const RoiArgs a) {
         }
       }
       auto writes = [&](int p) { return p < n && (p < 2 ? w01 : w23); };
-      if constexpr (OUT == PP_F32_PLANAR) {
+      if constexpr (kHalf) {
+        const bool wr[4] = {writes(0), writes(1), writes(2), writes(3)};
+        if constexpr (OUT == PP_F32_PLANAR) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+            store_h4_planar(d.p[c] + (u32)(y * dp) + (size_t)x0 * 2, o[c], full, wr);
+        } else {
+          store_h4_packed(d.p[0] + (u32)(y * dp) + (size_t)x0 * 6, o, full, wr);
+        }
+      } else if constexpr (OUT == PP_F32_PLANAR) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           uint8_t* q = d.p[c] + (u32)(y * dp) + (size_t)x0 * 4;
@@ -618,7 +742,9 @@ __global__ void __launch_bounds__(kBlock) k_nv12_preproc_roi(const RoiArgs a) {
   }
 }
 
-static int launch_preproc_roi(RoiArgs& a, int canvas_w, int canvas_h, int dst_fmt, int n, hipStream_t stream) {
+// td: TD_SURF, or the element type of the batch tensor a.tdst (dst_fmt then names its layout)
+static int launch_preproc_roi(RoiArgs& a, int canvas_w, int canvas_h, int dst_fmt, int n, hipStream_t stream,
+                              int td = TD_SURF) {
   int out;
   switch (dst_fmt) {
   case VALI_FMT_RGB_32F_PLANAR: out = PP_F32_PLANAR; break;
@@ -641,21 +767,37 @@ static int launch_preproc_roi(RoiArgs& a, int canvas_w, int canvas_h, int dst_fm
     a.row_pairs /= 2;
   a.map = make_tile_map((u32)tiles_x, (u32)tiles_y(a.row_pairs), (u32)n);
   const dim3 grid = tile_grid(a.map), block(kBlock);
-#define VALI_PPR_CASE(O)                                                                     \
-  case O:                                                                                   \
+#define VALI_PPR_LAUNCH(O, D)                                                                \
+  do {                                                                                      \
     if (tall)                                                                               \
-      hipLaunchKernelGGL((k_nv12_preproc_roi<O, true>), grid, block, 0, stream, a);         \
+      hipLaunchKernelGGL((k_nv12_preproc_roi<O, true, D>), grid, block, 0, stream, a);      \
     else                                                                                    \
-      hipLaunchKernelGGL((k_nv12_preproc_roi<O, false>), grid, block, 0, stream, a);        \
+      hipLaunchKernelGGL((k_nv12_preproc_roi<O, false, D>), grid, block, 0, stream, a);     \
+  } while (0)
+#define VALI_PPR_CASE(O)                                                                     \
+  case O: VALI_PPR_LAUNCH(O, TD_SURF); break;
+#define VALI_PPT_CASE(D)                                                                     \
+  case D:                                                                                   \
+    if (out == PP_F32_PLANAR) VALI_PPR_LAUNCH(PP_F32_PLANAR, D); else VALI_PPR_LAUNCH(PP_F32_PACKED, D); \
     break;
-  switch (out) {
-    VALI_PPR_CASE(PP_F32_PLANAR)
-    VALI_PPR_CASE(PP_F32_PACKED)
-    VALI_PPR_CASE(PP_U8_RGB)
-    VALI_PPR_CASE(PP_U8_BGR)
-    VALI_PPR_CASE(PP_U8_PLANAR)
+  if (td != TD_SURF) {
+    switch (td) {
+      VALI_PPT_CASE(TD_F32)
+      VALI_PPT_CASE(TD_F16)
+      VALI_PPT_CASE(TD_BF16)
+    }
+  } else {
+    switch (out) {
+      VALI_PPR_CASE(PP_F32_PLANAR)
+      VALI_PPR_CASE(PP_F32_PACKED)
+      VALI_PPR_CASE(PP_U8_RGB)
+      VALI_PPR_CASE(PP_U8_BGR)
+      VALI_PPR_CASE(PP_U8_PLANAR)
+    }
   }
+#undef VALI_PPT_CASE
 #undef VALI_PPR_CASE
+#undef VALI_PPR_LAUNCH
   VALI_LAUNCH_CHECK();
   return VALI_OK;
 }
@@ -687,19 +829,26 @@ __device__ __forceinline__ void roi_clamp_any(int& x, int& w, int size) {
   w = min(max(w, 0), size - x);
 }
 
-template <bool PLANAR, int OUT, bool TALL>
+template <bool PLANAR, int OUT, bool TALL, int DST = TD_SURF>
 __global__ void __launch_bounds__(kBlock) k_rgb_preproc_roi(const RgbRoiArgs ar) {
   constexpr bool kFloat = OUT == PP_F32_PLANAR || OUT == PP_F32_PACKED;
+  constexpr bool kHalf = DST == TD_F16 || DST == TD_BF16; // 16-bit elements: finished bits from the table on
+  static_assert(DST == TD_SURF || kFloat, "the tensor forms are float layouts");
   constexpr int kTileW = TALL ? kWave * 4 : kPpTileW;
   typedef unsigned long long u64;
   typedef unsigned v3u32 __attribute__((ext_vector_type(3)));
+  typedef TdElem<DST> Elem;
   const RoiArgs& a = ar.r;
-  __shared__ float lut[kFloat ? 3 : 1][256];
+  __shared__ typename Elem::lut_t lut[kFloat ? 3 : 1][256];
   u32 tile_x, tile_y, frame;
   if (!tile_of_block(a.map, tile_x, tile_y, frame))
     return;
   const SurfRef s = surf_ref(load_uniform(a.d_src, a.src, frame));
-  const SurfRef d = surf_ref(load_uniform(a.d_dst, a.dst, frame));
+  SurfRef d;
+  if constexpr (DST == TD_SURF)
+    d = surf_ref(load_uniform(a.d_dst, a.dst, frame));
+  else
+    d = tensor_ref<kHalf ? 2 : 4>(a.tdst, frame);
   const vali_roi r = load_uniform(a.d_roi, a.roi, frame);
   int sx = r.src_x, sy = r.src_y, sw = r.src_w, sh = r.src_h;
   int dx = r.dst_x, dy = r.dst_y, dw = r.dst_w, dh = r.dst_h;
@@ -725,7 +874,7 @@ __global__ void __launch_bounds__(kBlock) k_rgb_preproc_roi(const RgbRoiArgs ar)
   if constexpr (kFloat) {
     if (hits) {
       for (int e = threadIdx.x; e < 3 * 256; e += kBlock)
-        lut[e >> 8][e & 255] = preproc_step3(e & 255, e >> 8, a.prm);
+        lut[e >> 8][e & 255] = Elem::make(preproc_step3(e & 255, e >> 8, a.prm));
       __syncthreads();
     }
   }
@@ -742,13 +891,14 @@ __global__ void __launch_bounds__(kBlock) k_rgb_preproc_roi(const RgbRoiArgs ar)
     inx[p] = hits && x0 + p >= dx && x0 + p < dx + dw;
   const bool any_x = inx[0] || inx[1] || inx[2] || inx[3];
   const bool all_x = inx[0] && inx[1] && inx[2] && inx[3];
-  float pv[3]; // the pad colour: the normalised value (float outputs); the byte itself is padq
+  // the pad colour: the normalised value (float outputs; its finished bits for 16-bit elements); the byte itself is padq
+  typename Elem::val_t pv[3];
   u32 padq[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     padq[c] = (a.pad_rgb >> (8 * c)) & 255u;
-    const float v = kFloat ? preproc_step3((int)padq[c], c, a.prm) : 0.0f;
-    pv[c] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); // uniform: SGPRs
+    const auto v = Elem::make(kFloat ? preproc_step3((int)padq[c], c, a.prm) : 0.0f);
+    pv[c] = __builtin_bit_cast(typename Elem::val_t, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); // uniform: SGPRs
   }
 
   // the resize geometry of view -> view (resize_tile's expressions) and the lane's column taps
@@ -901,12 +1051,20 @@ __global__ void __launch_bounds__(kBlock) k_rgb_preproc_roi(const RgbRoiArgs ar)
       qc[2][p] = in[p] ? (ar.swap ? q[0][p] : q[2][p]) : padq[2];
     }
     if constexpr (kFloat) {
-      float o[3][4];
+      typename Elem::val_t o[3][4];
 #pragma unroll
       for (int c = 0; c < 3; ++c)
 #pragma unroll
         for (int p = 0; p < 4; ++p) o[c][p] = in[p] ? lut[c][qc[c][p]] : pv[c];
-      if constexpr (OUT == PP_F32_PLANAR) {
+      if constexpr (kHalf) {
+        if constexpr (OUT == PP_F32_PLANAR) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+            store_h4_planar(d.p[c] + (u32)(y * d.pitch[c]) + (size_t)x0 * 2, o[c], full, wr);
+        } else {
+          store_h4_packed(d.p[0] + (u32)(y * dp) + (size_t)x0 * 6, o, full, wr);
+        }
+      } else if constexpr (OUT == PP_F32_PLANAR) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           uint8_t* w = d.p[c] + (u32)(y * d.pitch[c]) + (size_t)x0 * 4;
@@ -978,7 +1136,7 @@ static int rgb_out_form(int dst_fmt) {
 static bool rgb_src_ok(int fmt) { return fmt == VALI_FMT_RGB || fmt == VALI_FMT_BGR || fmt == VALI_FMT_RGB_PLANAR; }
 
 static int launch_rgb_preproc_roi(RgbRoiArgs& ar, int src_fmt, int canvas_w, int canvas_h, int dst_fmt, int n,
-                                  hipStream_t stream) {
+                                  hipStream_t stream, int td = TD_SURF) {
   RoiArgs& a = ar.r;
   const int out = rgb_out_form(dst_fmt);
   ar.swap = src_fmt == VALI_FMT_BGR;
@@ -993,23 +1151,39 @@ static int launch_rgb_preproc_roi(RgbRoiArgs& ar, int src_fmt, int canvas_w, int
     a.row_pairs /= 2;
   a.map = make_tile_map((u32)tiles_x, (u32)tiles_y(a.row_pairs), (u32)n);
   const dim3 grid = tile_grid(a.map), block(kBlock);
-#define VALI_PPR_LAUNCH(P, O, T) hipLaunchKernelGGL((k_rgb_preproc_roi<P, O, T>), grid, block, 0, stream, ar)
-#define VALI_PPR_CASE(O)                                                                     \
-  case O:                                                                                   \
+#define VALI_PPR_LAUNCH(P, O, T, D) hipLaunchKernelGGL((k_rgb_preproc_roi<P, O, T, D>), grid, block, 0, stream, ar)
+#define VALI_PPR_FORM(O, D)                                                                  \
+  do {                                                                                      \
     if (planar) {                                                                           \
-      if (tall) VALI_PPR_LAUNCH(true, O, true); else VALI_PPR_LAUNCH(true, O, false);       \
+      if (tall) VALI_PPR_LAUNCH(true, O, true, D); else VALI_PPR_LAUNCH(true, O, false, D); \
     } else {                                                                                \
-      if (tall) VALI_PPR_LAUNCH(false, O, true); else VALI_PPR_LAUNCH(false, O, false);     \
+      if (tall) VALI_PPR_LAUNCH(false, O, true, D); else VALI_PPR_LAUNCH(false, O, false, D); \
     }                                                                                       \
+  } while (0)
+#define VALI_PPR_CASE(O)                                                                     \
+  case O: VALI_PPR_FORM(O, TD_SURF); break;
+#define VALI_PPT_CASE(D)                                                                     \
+  case D:                                                                                   \
+    if (out == PP_F32_PLANAR) VALI_PPR_FORM(PP_F32_PLANAR, D); else VALI_PPR_FORM(PP_F32_PACKED, D); \
     break;
-  switch (out) {
-    VALI_PPR_CASE(PP_F32_PLANAR)
-    VALI_PPR_CASE(PP_F32_PACKED)
-    VALI_PPR_CASE(PP_U8_RGB)
-    VALI_PPR_CASE(PP_U8_BGR)
-    VALI_PPR_CASE(PP_U8_PLANAR)
+  if (td != TD_SURF) {
+    switch (td) {
+      VALI_PPT_CASE(TD_F32)
+      VALI_PPT_CASE(TD_F16)
+      VALI_PPT_CASE(TD_BF16)
+    }
+  } else {
+    switch (out) {
+      VALI_PPR_CASE(PP_F32_PLANAR)
+      VALI_PPR_CASE(PP_F32_PACKED)
+      VALI_PPR_CASE(PP_U8_RGB)
+      VALI_PPR_CASE(PP_U8_BGR)
+      VALI_PPR_CASE(PP_U8_PLANAR)
+    }
   }
+#undef VALI_PPT_CASE
 #undef VALI_PPR_CASE
+#undef VALI_PPR_FORM
 #undef VALI_PPR_LAUNCH
   VALI_LAUNCH_CHECK();
   return VALI_OK;
@@ -1181,6 +1355,78 @@ int vali_rgb_preproc_roi_batch(const vali_surface* d_src, const vali_surface* d_
   hipStream_t s = as_stream(stream);
   VALI_ENTRY(s);
   return launch_rgb_preproc_roi(ar, src_format, dst_width, dst_height, dst_format, n, s);
+}
+
+// the checks the two tensor entry points share, all on the host
+static int tensor_dst_check(const char* who, const vali_tensor_dst* t, bool even) {
+#define VALI_T_REQUIRE(cond, msg)                                              \
+  do {                                                                         \
+    if (!(cond))                                                               \
+      return fail(VALI_ERR_INVALID_ARG, "%s: %s", who, msg);                   \
+  } while (0)
+  VALI_T_REQUIRE(t->data, "null tensor data");
+  VALI_T_REQUIRE(t->dtype >= VALI_DTYPE_F32 && t->dtype <= VALI_DTYPE_BF16, "dtype must be VALI_DTYPE_F32, _F16 or _BF16");
+  VALI_T_REQUIRE(t->packed == 0 || t->packed == 1, "packed must be 0 or 1");
+  VALI_T_REQUIRE(t->n >= 1 && t->n <= 65535, "batch size out of range (1..65535)");
+  if (even)
+    VALI_T_REQUIRE(t->width >= 2 && t->height >= 2 && ((t->width | t->height) & 1) == 0, "bad geometry");
+  else
+    VALI_T_REQUIRE(t->width >= 1 && t->height >= 1, "bad geometry");
+  VALI_T_REQUIRE(t->stride_n > 0 && t->stride_y > 0 && (t->packed || t->stride_c > 0), "strides must be positive");
+  VALI_T_REQUIRE(t->stride_y >= (int64_t)t->width * (t->packed ? 3 : 1), "stride_y is shorter than a row");
+  const int64_t esize = t->dtype == VALI_DTYPE_F32 ? 4 : 2;
+  VALI_T_REQUIRE(((uintptr_t)t->data & (uintptr_t)(esize - 1)) == 0, "data is not aligned to its element");
+  // the kernels address a row as (u32)(y * pitch) inside its plane
+  VALI_T_REQUIRE(t->stride_y <= (int64_t)0x7fffffff / esize &&
+                     (uint64_t)t->height * (uint64_t)(t->stride_y * esize) < (1ull << 32),
+                 "row pitch of 2 GiB or plane of 4 GiB or more");
+#undef VALI_T_REQUIRE
+  return VALI_OK;
+}
+
+static void tensor_dst_args(RoiArgs& a, const vali_surface* d_src, const vali_roi* d_roi, const vali_tensor_dst* dst,
+                            const vali_preproc_params* params, int pad, const uint8_t* pad_rgb) {
+  a.d_src = d_src;
+  a.d_roi = d_roi;
+  a.whole = d_roi == nullptr;
+  a.tdst = *dst;
+  a.prm = *params;
+  a.pad = pad != 0;
+  if (pad)
+    a.pad_rgb = (u32)pad_rgb[0] | (u32)pad_rgb[1] << 8 | (u32)pad_rgb[2] << 16;
+}
+
+int vali_nv12_preproc_roi_tensor(const vali_surface* d_src, const vali_roi* d_roi, const vali_tensor_dst* dst,
+                                 const vali_preproc_params* params, int pad, const uint8_t pad_rgb[3],
+                                 vali_stream_t stream) {
+  VALI_REQUIRE(d_src && dst && params, "null argument");
+  VALI_REQUIRE(!pad || pad_rgb, "null pad colour");
+  if (const int rc = tensor_dst_check(__func__, dst, true))
+    return rc;
+  RoiArgs a = {};
+  tensor_dst_args(a, d_src, d_roi, dst, params, pad, pad_rgb);
+  hipStream_t s = as_stream(stream);
+  VALI_ENTRY(s);
+  return launch_preproc_roi(a, dst->width, dst->height, dst->packed ? VALI_FMT_RGB_32F : VALI_FMT_RGB_32F_PLANAR, dst->n,
+                            s, TD_F32 + dst->dtype);
+}
+
+int vali_rgb_preproc_roi_tensor(const vali_surface* d_src, const vali_roi* d_roi, int src_format,
+                                const vali_tensor_dst* dst, const vali_preproc_params* params, int pad,
+                                const uint8_t pad_rgb[3], vali_stream_t stream) {
+  VALI_REQUIRE(d_src && dst && params, "null argument");
+  VALI_REQUIRE(!pad || pad_rgb, "null pad colour");
+  if (!rgb_src_ok(src_format))
+    return fail(VALI_ERR_UNSUPPORTED, "rgb_preproc_roi_tensor: sources must be RGB, BGR or RGB_PLANAR (got %d)", src_format);
+  if (const int rc = tensor_dst_check(__func__, dst, false))
+    return rc;
+  RgbRoiArgs ar = {};
+  tensor_dst_args(ar.r, d_src, d_roi, dst, params, pad, pad_rgb);
+  ar.whole = d_roi == nullptr;
+  hipStream_t s = as_stream(stream);
+  VALI_ENTRY(s);
+  return launch_rgb_preproc_roi(ar, src_format, dst->width, dst->height,
+                                dst->packed ? VALI_FMT_RGB_32F : VALI_FMT_RGB_32F_PLANAR, dst->n, s, TD_F32 + dst->dtype);
 }
 
 } // extern "C"

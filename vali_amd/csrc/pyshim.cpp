@@ -49,6 +49,10 @@ struct PreprocParams {
   vali_preproc_params p;
 };
 
+struct TensorDst {
+  vali_tensor_dst t;
+};
+
 struct JpegParams {
   vali_jpeg_params p;
 };
@@ -521,6 +525,38 @@ PYBIND11_MODULE(_vali_shim, m) {
           return vali_rgb_preproc_roi_batch((const vali_surface*)P(d_src), (const vali_surface*)P(d_dst),
                                             (const vali_roi*)P(d_roi), n, src_format, dst_width, dst_height, dst_format,
                                             &p.p, pad ? 1 : 0, pad_rgb.data(), P(stream));
+        },
+        py::call_guard<py::gil_scoped_release>());
+
+  // the batch tensor of the tensor forms: (data, dtype, packed, n, width, height, stride_n, stride_c, stride_y), strides in
+  // elements; the C entry points judge it
+  py::class_<TensorDst>(m, "TensorDst")
+      .def(py::init([](uintptr_t data, int dtype, int packed, int n, int width, int height, int64_t stride_n,
+                       int64_t stride_c, int64_t stride_y) {
+        TensorDst d;
+        std::memset(&d.t, 0, sizeof(d.t));
+        d.t.data = P(data);
+        d.t.dtype = dtype; d.t.packed = packed;
+        d.t.n = n; d.t.width = width; d.t.height = height;
+        d.t.stride_n = stride_n; d.t.stride_c = stride_c; d.t.stride_y = stride_y;
+        return d;
+      }));
+  m.attr("TENSOR_DST_SIZE") = sizeof(vali_tensor_dst);
+  m.attr("DTYPE_F32") = (int)VALI_DTYPE_F32;
+  m.attr("DTYPE_F16") = (int)VALI_DTYPE_F16;
+  m.attr("DTYPE_BF16") = (int)VALI_DTYPE_BF16;
+  m.def("nv12_preproc_roi_tensor",
+        [](uintptr_t d_src, uintptr_t d_roi, const TensorDst& dst, const PreprocParams& p, bool pad,
+           const std::array<uint8_t, 3>& pad_rgb, uintptr_t stream) {
+          return vali_nv12_preproc_roi_tensor((const vali_surface*)P(d_src), (const vali_roi*)P(d_roi), &dst.t, &p.p,
+                                              pad ? 1 : 0, pad_rgb.data(), P(stream));
+        },
+        py::call_guard<py::gil_scoped_release>());
+  m.def("rgb_preproc_roi_tensor",
+        [](uintptr_t d_src, uintptr_t d_roi, int src_format, const TensorDst& dst, const PreprocParams& p, bool pad,
+           const std::array<uint8_t, 3>& pad_rgb, uintptr_t stream) {
+          return vali_rgb_preproc_roi_tensor((const vali_surface*)P(d_src), (const vali_roi*)P(d_roi), src_format,
+                                             &dst.t, &p.p, pad ? 1 : 0, pad_rgb.data(), P(stream));
         },
         py::call_guard<py::gil_scoped_release>());
 

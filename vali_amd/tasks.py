@@ -804,6 +804,41 @@ class PySurfacePreprocessor(_SurfaceTask):
         self._sync()
         return r
 
+    # ---- regions into ONE batch tensor (vali_nv12_preproc_roi_tensor / vali_rgb_preproc_roi_tensor) ----
+    # `out`: a float32, float16 or bfloat16 device tensor of logical shape (N, 3, H, W), handed over by DLPack (or
+    # __cuda_array_interface__), contiguous, a slice that keeps rows contiguous, or channels last.  out[i, c, y, x] is the
+    # float32 that RunRoiBatch writes to an RGB_32F_PLANAR canvas of H x W, converted to out's dtype round-to-nearest-
+    # even: no surfaces, no torch.stack, no .half().
+    def PrepareTensorBatch(self, srcs: Sequence[Surface], out, src_rects=None, dst_rects=None) -> "TensorBatch":
+        return TensorBatch(self._gpu_id, self._stream, srcs, out, src_rects, dst_rects)
+
+    def RunTensorBatchAsync(self, batch: "TensorBatch", pad=None, cc_ctx=None, rects=None) -> Tuple[bool, TaskExecInfo]:
+        """One launch over the items of `batch`; `pad`, `cc_ctx` and `rects` as for RunRoiBatchAsync."""
+        if not isinstance(batch, TensorBatch):
+            raise ValueError("RunTensorBatch: pass a TensorBatch (PrepareTensorBatch)")
+        is_rgb = batch.src_format in self._RGB_SRC
+        if batch.src_format != F.NV12 and not is_rgb:
+            return False, TaskExecInfo.NOT_SUPPORTED
+        try:
+            on, rgb = _pad_colour(pad)
+        except ValueError:
+            return False, TaskExecInfo.INVALID_INPUT
+        p = self._params(None if is_rgb else cc_ctx)
+        if p is None:
+            return False, TaskExecInfo.UNSUPPORTED_FMT_CONV_PARAMS
+        d_roi, _hold = (batch.d_roi, None) if rects is None else _device_rects(rects, batch.n, batch.gpu_id)
+        if is_rgb:
+            d = _status(shim.rgb_preproc_roi_tensor(batch.d_src, d_roi, int(batch.src_format), batch.dst, p, on, rgb,
+                                                    self._stream))
+        else:
+            d = _status(shim.nv12_preproc_roi_tensor(batch.d_src, d_roi, batch.dst, p, on, rgb, self._stream))
+        return d.success, d.info
+
+    def RunTensorBatch(self, batch: "TensorBatch", pad=None, cc_ctx=None, rects=None) -> Tuple[bool, TaskExecInfo]:
+        r = self.RunTensorBatchAsync(batch, pad, cc_ctx, rects)
+        self._sync()
+        return r
+
 
 def letterbox_rect(src_w: int, src_h: int, dst_w: int, dst_h: int) -> Tuple[int, int, int, int]:
     """The centred, aspect-preserving, even placement (x, y, w, h) of a src_w x src_h picture inside a
@@ -950,6 +985,146 @@ class RoiBatch:
             except Exception:
                 pass
         for name in ("d_src", "d_dst", "d_roi"):
+            p = getattr(self, name, 0)
+            if p:
+                try:
+                    shim.mem_free(self.gpu_id, p)
+                except Exception:
+                    pass
+                setattr(self, name, 0)
+
+
+# DLPack dtype (code, bits) -> (name, enum vali_dtype): kDLFloat = 2, kDLBfloat = 4
+_TENSOR_DTYPES = {(2, 32): ("float32", 0), (2, 16): ("float16", 1), (4, 16): ("bfloat16", 2)}
+
+
+def tensor_layout(shape, strides, code, bits):
+    """Classify a destination tensor from its DLPack view, without a device: ("planar" | "packed", dtype name).
+    `shape` is the logical (N, 3, H, W), `strides` are in elements.  planar: x stride 1 (contiguous tensors and every
+    slice that keeps rows contiguous); packed: c stride 1 and x stride 3 (channels last).  ValueError, naming what is
+    wrong, for everything else."""
+    shape = tuple(int(v) for v in shape)
+    dtype = _TENSOR_DTYPES.get((int(code), int(bits)))
+    if dtype is None:
+        raise ValueError(f"out: the dtype must be float32, float16 or bfloat16 (DLPack code {code}, {bits} bits)")
+    if len(shape) != 4:
+        raise ValueError(f"out: need a 4-D tensor (N, 3, H, W), got {len(shape)}-D {shape}")
+    if strides is None:
+        strides = (3 * shape[2] * shape[3], shape[2] * shape[3], shape[3], 1)
+    strides = tuple(int(v) for v in strides)
+    if len(strides) != 4:
+        raise ValueError(f"out: {len(strides)} strides for a 4-D tensor")
+    n, c, h, w = shape
+    if c != 3:
+        raise ValueError(f"out: need 3 channels (N, 3, H, W), got C = {c}")
+    if n < 1 or h < 1 or w < 1:
+        raise ValueError(f"out: empty tensor {shape}")
+    if n > 65535:
+        raise ValueError("out: at most 65535 items")
+    if any(v < 0 for v in strides):
+        raise ValueError(f"out: negative strides {strides} (a flipped view) are not supported")
+    sn, sc, sy, sx = strides
+    # a dimension of size 1 has no meaningful stride: give it the one its layout would have
+    if sx == 1 or (w == 1 and sc != 1):
+        layout, row = "planar", w
+    elif sc == 1 and (sx == 3 or w == 1):
+        layout, row = "packed", 3 * w
+    else:
+        raise ValueError(f"out: strides {strides} are neither planar (x stride 1) nor channels last (c stride 1, "
+                         "x stride 3) -- a transposed or strided view")
+    if (h > 1 and sy < row) or (layout == "planar" and sc < 1) or (n > 1 and sn < 1):
+        raise ValueError(f"out: strides {strides} of a {layout} {shape} tensor: rows overlap -- a transposed or "
+                         "broadcast view")
+    return layout, dtype[0]
+
+
+def _tensor_dst(out, gpu_id):
+    """(shim.TensorDst, layout, dtype name, (n, h, w), holder) of a destination tensor on `gpu_id`"""
+    if hasattr(out, "__dlpack__"):
+        info, holder = shim.dlpack_import(out.__dlpack__())
+        if info["lanes"] != 1:
+            raise ValueError("out: vector dtypes are not supported")
+        shape, strides, code, bits = tuple(info["shape"]), tuple(info["strides"]), info["code"], info["bits"]
+        layout, dtype = tensor_layout(shape, strides, code, bits)
+        if info["device_type"] not in (int(DLDeviceType.kDLROCM), int(DLDeviceType.kDLCUDA)):
+            raise ValueError("out: the tensor must live on the GPU")
+        ptr, device = int(info["ptr"]), int(info["device_id"])
+    elif hasattr(out, "__cuda_array_interface__"):
+        cai = out.__cuda_array_interface__
+        typestr = cai["typestr"]
+        if typestr not in ("<f4", "<f2"):
+            raise ValueError(f"out: the dtype must be float32 or float16 through __cuda_array_interface__, got {typestr}")
+        bits = 32 if typestr == "<f4" else 16
+        shape = tuple(int(v) for v in cai["shape"])
+        strides = cai.get("strides")
+        if strides is not None:
+            if any(int(v) % (bits // 8) for v in strides):
+                raise ValueError("out: strides that are no multiple of the element size")
+            strides = tuple(int(v) // (bits // 8) for v in strides)
+        layout, dtype = tensor_layout(shape, strides, 2, bits)
+        if strides is None:
+            strides = (3 * shape[2] * shape[3], shape[2] * shape[3], shape[3], 1)
+        ptr, holder = int(cai["data"][0]), out
+        dev = getattr(out, "device", None)
+        device = dev.index if getattr(dev, "type", None) == "cuda" and dev.index is not None else shim.ptr_device(ptr)
+    else:
+        raise ValueError("out: a device tensor with __dlpack__ or __cuda_array_interface__")
+    if device != gpu_id:
+        raise ValueError(f"out: the tensor is on device {device}, the task on {gpu_id}")
+    n, _, h, w = shape
+    sn, sc, sy, _ = strides
+    row = w if layout == "planar" else 3 * w
+    # strides of dimensions of size 1 are arbitrary: the kernel's addressing needs them positive and rows apart
+    sy = max(sy, row)
+    sc = max(sc, 1)
+    sn = max(sn, 1)
+    code = {"float32": shim.DTYPE_F32, "float16": shim.DTYPE_F16, "bfloat16": shim.DTYPE_BF16}[dtype]
+    dst = shim.TensorDst(ptr, code, 1 if layout == "packed" else 0, n, w, h, sn, sc, sy)
+    return dst, layout, dtype, (n, h, w), holder
+
+
+class _Canvas:
+    """what _roi_batch_records reads of a destination: the tensor's canvas stands in for N equal surfaces"""
+    IsEmpty = False
+
+    def __init__(self, w, h):
+        self.Format, self.Width, self.Height = F.RGB_32F_PLANAR, w, h
+
+
+class TensorBatch:
+    """Device-resident arrays for n region items that land in ONE batch tensor: source descriptors (one format, any
+    sizes, repeats allowed) and rectangle records, uploaded once (PySurfacePreprocessor.PrepareTensorBatch).  Keeps the
+    sources and the tensor alive."""
+
+    def __init__(self, gpu_id: int, stream: int, srcs: Sequence[Surface], out, src_rects=None, dst_rects=None):
+        srcs = list(srcs)
+        self.dst, self.layout, self.dtype, (n, h, w), holder = _tensor_dst(out, gpu_id)
+        if len(srcs) != n:
+            raise ValueError(f"TensorBatch: {len(srcs)} sources for a tensor of {n} items")
+        canvas = _Canvas(w, h)
+        self.src_format, self.rects = _roi_batch_records(srcs, [canvas] * n, src_rects, dst_rects)
+        if is_capturing(gpu_id, stream):
+            raise RuntimeError("TensorBatch: cannot be created while the stream is capturing -- PrepareTensorBatch() "
+                               "before the StreamCapture block and Keep() the batch with the capture")
+        self.gpu_id = gpu_id
+        self._stream = stream
+        self.n = n
+        self.dst_size = (w, h)
+        self.out = out
+        self._keep = (srcs, out, holder)
+        self.d_src = shim.descs_upload(gpu_id, [s.desc() for s in srcs], stream)
+        self.d_roi = shim.rois_upload(gpu_id, self.rects, stream)
+
+    def __len__(self):
+        return self.n
+
+    def __del__(self):
+        if getattr(self, "d_src", 0) or getattr(self, "d_roi", 0):
+            try:    # a launch issued on the batch's stream may still be reading the arrays
+                shim.stream_sync(self.gpu_id, self._stream)
+            except Exception:
+                pass
+        for name in ("d_src", "d_roi"):
             p = getattr(self, name, 0)
             if p:
                 try:
