@@ -369,7 +369,8 @@ VALI_API int vali_rgb_preproc_roi_batch(const vali_surface* d_src, const vali_su
  * 3 * width when packed); data not aligned to the element; a row pitch of 2 GiB or more or a plane (height x pitch,
  * in bytes) of 4 GiB or more; pad without a colour.  VALI_ERR_UNSUPPORTED for a src_format outside the list.
  */
-enum vali_dtype { VALI_DTYPE_F32 = 0, VALI_DTYPE_F16 = 1, VALI_DTYPE_BF16 = 2 };
+enum vali_dtype { VALI_DTYPE_F32 = 0, VALI_DTYPE_F16 = 1, VALI_DTYPE_BF16 = 2,
+                  VALI_DTYPE_U8 = 3 /* a source of vali_jpeg_encode_tensor only: the tensor forms above refuse it */ };
 typedef struct vali_tensor_dst {
   void* data;               /* device memory, aligned to the element size */
   int32_t dtype;            /* enum vali_dtype */
@@ -447,6 +448,40 @@ VALI_API int vali_jpeg_stream_capacity(int width, int height, const vali_jpeg_pa
 VALI_API int vali_jpeg_encode_batch(const vali_surface* d_src, int n, int width, int height, int format,
                                     const vali_jpeg_params* params, void* workspace, size_t ws_bytes, uint8_t* d_out,
                                     size_t out_stride, uint32_t* d_sizes, vali_stream_t stream);
+
+/*
+ * The same files straight from ONE batch tensor of logical shape (N, 3, H, W): float32, float16, bfloat16 or uint8,
+ * addressed as vali_tensor_dst is (planar or channels last, strides in elements).  For item i, channel c and pixel
+ * (x, y):
+ *   e = element (i, c, y, x) as float32        exact for float16 (subnormals included), bfloat16 and uint8
+ *   v = fl32(fl32(e * scale[c]) + offset[c])   two IEEE roundings, never a fused multiply-add
+ *   p = 0 if v is NaN, else min(max(rint(v), 0), 255)      rint: round half to even; -inf -> 0, +inf -> 255
+ * which is torch.nan_to_num(x.float() * scale + offset, nan=0.0).round().clamp(0, 255).to(torch.uint8) bit for bit.
+ * The entropy data of item i is byte for byte what vali_jpeg_encode_batch writes for an 8-bit surface of
+ * params->format that holds p, with the same params.  params->format names the channels:
+ *   RGB, RGB_PLANAR: R, G, B;  BGR: B, G, R  -- coded 1x1, 2x1 or 2x2 as vali_jpeg_params_init_sampled allows;
+ *   YUV444: Y, Cb, Cr, coded as they are, 1x1;  every other format: VALI_ERR_UNSUPPORTED.
+ * The file never depends on the tensor's layout or dtype beyond p.  Any size, odd ones included, at every sampling.
+ * Workspace, stream capacity and header: vali_jpeg_workspace_size, vali_jpeg_stream_capacity and vali_jpeg_header
+ * of (src->n, src->width, src->height, params).  Output layout, d_sizes and the four launches are those of
+ * vali_jpeg_encode_batch; src is a HOST struct that travels in the kernel arguments; nothing is allocated, nothing
+ * synchronises.  VALI_ERR_INVALID_ARG, before any device is touched, for: null arguments; dtype outside 0..3 or
+ * packed outside 0..1; n outside 1..65535; a size outside 1..65535; strides <= 0 or stride_y below the row's extent
+ * (width, 3 * width when packed); data not aligned to its element; a non-finite scale or offset; and whatever
+ * vali_jpeg_encode_batch refuses in params, workspace and out_stride.
+ */
+typedef struct vali_tensor_src {
+  const void* data;         /* device memory, aligned to the element size */
+  int32_t dtype;            /* enum vali_dtype, VALI_DTYPE_U8 included */
+  int32_t packed;           /* 0: planar, x stride 1.  1: channels last, c stride 1, x stride 3 */
+  int32_t n, width, height; /* items, image size */
+  int32_t reserved;
+  int64_t stride_n, stride_c, stride_y; /* in ELEMENTS; stride_c is ignored when packed */
+} vali_tensor_src;                      /* 56 bytes: vali_tensor_dst with const data */
+
+VALI_API int vali_jpeg_encode_tensor(const vali_tensor_src* src, const float scale[3], const float offset[3],
+                                     const vali_jpeg_params* params, void* workspace, size_t ws_bytes,
+                                     uint8_t* d_out, size_t out_stride, uint32_t* d_sizes, vali_stream_t stream);
 
 /* ---- JPEG: baseline sequential decoder ----------------------------------------------------
  *

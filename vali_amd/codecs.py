@@ -17,7 +17,8 @@ offline.  What IS provided so pipelines written against python_vali keep running
                  (src/python_vali/src/PyFrameConverter.cpp:21-129) served by the HIP converter:
                  ndarray -> upload -> kernel -> download.  It is NOT a CPU code path.
 * PyNvJpegEncoder -- the reference's JPEG encoder API: backend="cpu" (default) downloads and compresses with Pillow;
-                 backend="hip" encodes baseline JPEG on the GPU (vali_jpeg_encode_batch).
+                 backend="hip" encodes baseline JPEG on the GPU (vali_jpeg_encode_batch).  RunTensor encodes a
+                 (N, 3, H, W) float32 / float16 / bfloat16 / uint8 tensor as it is (vali_jpeg_encode_tensor).
 * PyNvJpegDecoder -- baseline JPEG decoded on the GPU into Surfaces (vali_jpeg_decode_batch): RGB / BGR / RGB_PLANAR / Y
                  from any supported file, YUV444 / YUV422 / YUV420 / NV12 from files of that sampling.
 * PyNvEncoder  -- the reference's video encoder API (src/python_vali/src/PyNvEncoder.cpp:388-630) as "download + CPU
@@ -36,7 +37,7 @@ from .enums import ColorRange, ColorSpace, DecodeMode, FfmpegLogLevel, PixelForm
 from ._native import shim
 from .runtime import HipResMgr
 from .surface import FORMATS, Surface, _DeviceMem
-from .tasks import PySurfaceConverter
+from .tasks import PySurfaceConverter, _tensor_src
 from .transfer import PyFrameUploader, PySurfaceDownloader
 
 F = PixelFormat
@@ -761,6 +762,42 @@ class NvJpegEncodeContext:
         return self._subsampling
 
 
+_TENSOR_ESIZE = {"float32": 4, "float16": 2, "bfloat16": 2, "uint8": 1}
+
+
+def _triple(name: str, value) -> Tuple[float, float, float]:
+    """a number or three numbers, per tensor channel, as the float32 values the kernel gets; ValueError if not finite"""
+    try:
+        with np.errstate(over="ignore"):
+            v = np.asarray(value, np.float64).astype(np.float32)
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f"{name}: a number or three numbers, got {value!r}") from exc
+    if v.shape not in ((), (3,)):
+        raise ValueError(f"{name}: a number or three numbers (one per channel), got shape {v.shape}")
+    v = np.broadcast_to(v, (3,))
+    if not np.isfinite(v).all():
+        raise ValueError(f"{name}: {value!r} is not finite in float32")
+    return float(v[0]), float(v[1]), float(v[2])
+
+
+def _quantise_tensor(raw: np.ndarray, dtype: str, scale, offset) -> np.ndarray:
+    """The pixels of vali_jpeg_encode_tensor's definition (include/vali_hip.h) in numpy: `raw` holds the elements'
+    bits (float32 as float32, float16 and bfloat16 as uint16, uint8), channels along the LAST axis."""
+    if dtype == "float32":
+        e = raw.view(np.float32)
+    elif dtype == "float16":
+        e = raw.view(np.float16).astype(np.float32)
+    elif dtype == "bfloat16":       # numpy has no such dtype: its 16 bits are the top half of a float32
+        e = (raw.astype(np.uint32) << 16).view(np.float32)
+    else:
+        e = raw.astype(np.float32)
+    with np.errstate(all="ignore"):
+        v = e * np.asarray(scale, np.float32)       # two float32 roundings: numpy fuses nothing
+        v = v + np.asarray(offset, np.float32)
+        v = np.where(np.isnan(v), np.float32(0), v)
+        return np.clip(np.rint(v), 0, 255).astype(np.uint8)
+
+
 class PyNvJpegEncoder:
     """JPEG encoder with the reference's call surface (src/python_vali/src/PyNvJpegEncoder.cpp:21-160).
     `Run(context, surfaces)` -> (list of uint8 arrays, TaskExecInfo): all surfaces or none (:36-75).
@@ -843,6 +880,67 @@ class PyNvJpegEncoder:
             buffers.append(np.frombuffer(out.getvalue(), np.uint8).copy())
         return buffers, TaskExecInfo.SUCCESS
 
+    def RunTensor(self, context: NvJpegEncodeContext, tensor, scale=None, offset=0.0) -> Tuple[list, TaskExecInfo]:
+        """One file per item of a GPU tensor of shape (N, 3, H, W): float32, float16, bfloat16 or uint8, through
+        `__dlpack__` or `__cuda_array_interface__`; contiguous, a slice that keeps rows contiguous, or channels last.
+        Element e of channel c becomes the pixel clamp(rint(e * scale[c] + offset[c]), 0, 255) (NaN: 0; float32
+        arithmetic, two roundings), and the files are those of `Run` on 8-bit surfaces of these pixels.
+        `context.Format()` names the channels: RGB / RGB_PLANAR (R, G, B) and BGR (B, G, R) with any `Subsampling()`,
+        YUV444 (Y, Cb, Cr as they are).  YUV422 / YUV420 contexts fail: a tensor has no subsampled planes.
+        `scale`, `offset`: a number or three, per tensor channel; scale=None is 255 for the float dtypes, 1 for uint8.
+        The tensor's producer must have finished (or be ordered before the encoder's stream), as for surfaces
+        borrowed from DLPack.  ValueError for what is not such a tensor on the encoder's GPU."""
+        offset = _triple("offset", offset)
+        if scale is not None:
+            scale = _triple("scale", scale)
+        src, layout, dtype, (n, h, w), where, holder = _tensor_src(tensor, self._gpu_id)
+        if scale is None:
+            scale = _triple("scale", 1.0 if dtype == "uint8" else 255.0)
+        fmt = context.Format()
+        if fmt not in (F.RGB, F.BGR, F.RGB_PLANAR, F.YUV444) or not (1 <= w <= 65535 and 1 <= h <= 65535):
+            return [], TaskExecInfo.FAIL
+        q = max(1, min(100, context.Compression()))
+        samp = context.Subsampling()
+        if self._backend == "hip":
+            params = self._jpeg_params(q, fmt, samp)
+            ws, out, d_sizes, cap = self._buffers(n, w, h, params)
+            rc = shim.jpeg_encode_tensor(src, scale, offset, params, ws, self._ws_bytes, out, cap, d_sizes, self._stream)
+            if rc != 0:
+                return [], TaskExecInfo.FAIL
+            buffers = self._fetch(n, self._header(w, h, fmt, q, samp), out, cap, d_sizes)
+            del holder                              # the tensor was kept alive until the final synchronisation
+            return buffers, TaskExecInfo.SUCCESS
+        return self._run_tensor_cpu(fmt, q, samp, layout, dtype, (n, h, w), where, scale, offset)
+
+    def _run_tensor_cpu(self, fmt, q, samp, layout, dtype, shape, where, scale, offset) -> Tuple[list, TaskExecInfo]:
+        """rows to the host with pitched copies, the definition's pixels with numpy, then Pillow as `Run`"""
+        import io
+
+        (n, h, w), (ptr, sn, sc, sy) = shape, where
+        es = _TENSOR_ESIZE[dtype]
+        bits = {4: np.float32, 2: np.uint16, 1: np.uint8}[es]
+        g, s = self._gpu_id, self._stream
+        buffers = []
+        for i in range(n):
+            if layout == "planar":
+                raw = np.empty((3, h, w), bits)
+                for c in range(3):
+                    shim.memcpy2d_async(g, raw[c].ctypes.data, w * es, ptr + (i * sn + c * sc) * es, sy * es, w * es, h, 1, s)
+                shim.stream_sync(g, s)
+                raw = raw.transpose(1, 2, 0)
+            else:
+                raw = np.empty((h, w, 3), bits)
+                shim.memcpy2d_async(g, raw.ctypes.data, 3 * w * es, ptr + i * sn * es, sy * es, 3 * w * es, h, 1, s)
+                shim.stream_sync(g, s)
+            p = _quantise_tensor(raw, dtype, scale, offset)             # (h, w, 3), channels as the tensor has them
+            if fmt in (F.RGB_PLANAR, F.YUV444):
+                p = p.transpose(2, 0, 1)
+            out = io.BytesIO()
+            self._image(fmt, w, h, np.ascontiguousarray(p).reshape(-1)).save(
+                out, format="JPEG", quality=q, subsampling=list(NvJpegEncodeContext._SAMPLINGS).index(samp))
+            buffers.append(np.frombuffer(out.getvalue(), np.uint8).copy())
+        return buffers, TaskExecInfo.SUCCESS
+
     # ---- hip backend ----------------------------------------------------------------------------------------------------
     def _jpeg_params(self, quality: int, fmt: PixelFormat, samp: str):
         key = (quality, int(fmt), samp)
@@ -888,29 +986,42 @@ class PyNvJpegEncoder:
         g, s = self._gpu_id, self._stream
         for (w, h), idx in groups.items():
             n = len(idx)
-            ws_bytes = shim.jpeg_workspace_size(n, w, h, params)
-            cap = shim.jpeg_stream_capacity(w, h, params)
-            ws, out, d_sizes = self._grow("ws", ws_bytes), self._grow("out", n * cap), self._grow("sizes", 4 * n)
+            ws, out, d_sizes, cap = self._buffers(n, w, h, params)
             d_src = shim.descs_upload(g, [surfaces[i].desc() for i in idx], s)
             try:
                 rc = shim.jpeg_encode_batch(d_src, n, w, h, int(fmt), params, ws, self._ws_bytes, out, cap, d_sizes, s)
                 if rc != 0:
                     return [], TaskExecInfo.FAIL
-                sizes = np.zeros(n, np.uint32)
-                shim.memcpy2d_async(g, sizes.ctypes.data, 4 * n, d_sizes, 4 * n, 4 * n, 1, 1, s)
-                shim.stream_sync(g, s)
+                files = self._fetch(n, self._header(w, h, fmt, q, samp), out, cap, d_sizes)
             finally:
                 shim.mem_free(g, d_src)
-            hdr = self._header(w, h, fmt, q, samp)
-            for k, i in enumerate(idx):             # one exact D2H copy per image, between its header and EOI
-                size = int(sizes[k])
-                buf = np.empty(hdr.size + size + 2, np.uint8)
-                buf[:hdr.size] = hdr
-                buf[-2:] = (0xFF, 0xD9)
-                shim.memcpy2d_async(g, buf.ctypes.data + hdr.size, size, out + k * cap, size, size, 1, 1, s)
-                buffers[i] = buf
-            shim.stream_sync(g, s)
+            for k, i in enumerate(idx):
+                buffers[i] = files[k]
         return buffers, TaskExecInfo.SUCCESS
+
+    def _buffers(self, n: int, w: int, h: int, params):
+        """(workspace, output, sizes, output stride) of a launch over n images of w x h: the encoder's own buffers"""
+        ws_bytes = shim.jpeg_workspace_size(n, w, h, params)
+        cap = shim.jpeg_stream_capacity(w, h, params)
+        return self._grow("ws", ws_bytes), self._grow("out", n * cap), self._grow("sizes", 4 * n), cap
+
+    def _fetch(self, n: int, hdr: np.ndarray, out: int, cap: int, d_sizes: int) -> list:
+        """the n files of a launch: the sizes, then one exact D2H copy per image, between its header and EOI;
+        synchronises the encoder's stream twice"""
+        g, s = self._gpu_id, self._stream
+        sizes = np.zeros(n, np.uint32)
+        shim.memcpy2d_async(g, sizes.ctypes.data, 4 * n, d_sizes, 4 * n, 4 * n, 1, 1, s)
+        shim.stream_sync(g, s)
+        files = []
+        for k in range(n):
+            size = int(sizes[k])
+            buf = np.empty(hdr.size + size + 2, np.uint8)
+            buf[:hdr.size] = hdr
+            buf[-2:] = (0xFF, 0xD9)
+            shim.memcpy2d_async(g, buf.ctypes.data + hdr.size, size, out + k * cap, size, size, 1, 1, s)
+            files.append(buf)
+        shim.stream_sync(g, s)
+        return files
 
 
 class JpegInfo:

@@ -6,6 +6,8 @@
 // Four launches in stream order; none hands data to another workgroup of the same launch:
 //   k_jpeg_fdct      lane = one 8x8 block of one component, in MCU-interleaved scan order: load (edge replication,
 //                    rgb_ycc for RGB sources), islow FDCT, quantise, zigzag -> 128 B of int16 in the workspace.
+//                    The pixels come from 8-bit surfaces, or from one float32 / float16 / bfloat16 / uint8 tensor
+//                    whose elements are scaled, rounded and clamped to 0..255 in registers (vali_jpeg_encode_tensor).
 //                    A dummy block of a partial MCU computes the block whose DC it copies and keeps only that DC.
 //                    RGB sources coded 4:2:2 / 4:2:0: a luma lane also averages the chroma of its 8x8 pixels (jcsample)
 //                    and hands it to the MCU's chroma lanes through LDS (fdct_subsampled).
@@ -15,7 +17,9 @@
 //                    worst-case slot; its length goes to the length array.
 //   k_jpeg_offsets   workgroup = one image: exclusive scan of (segment length + 2 bytes of RST) -> offsets, size.
 //   k_jpeg_assemble  workgroup = one segment: copy it and its RST marker to the image's output slot.
+#include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "common.hpp"
 
@@ -193,7 +197,6 @@ size_t jpeg_ws_bytes(const JpegGeom& g, int n) { return g.slot_at + (size_t)(n >
 
 // ---- k_jpeg_fdct -----------------------------------------------------------------------------------------------------
 struct FdctArgs {
-  const vali_surface* d_src;
   int16_t* coef;  // image i: coef + i * nblocks * 64
   int H, V, HV, bpm, mcux, nblocks;
   int cw[3], ch[3], bw[3], bh[3];
@@ -201,7 +204,14 @@ struct FdctArgs {
   u32 corr_shift[2][64];  // correction | shift << 16
 };
 
-enum { SRC_YUV = 0, SRC_RGB = 1, SRC_BGR = 2, SRC_RGB_PLANAR = 3 };
+// 8-bit surfaces; from SRC_TENSOR on one (N, 3, H, W) tensor: SRC_TENSOR | dtype << 2 | channels last << 1 | YUV
+// (a named type: k_jpeg_fdct's signature spells `SRC >= SRC_TENSOR` out, and an unnamed enum is numbered differently in
+// the host and the device pass, so the host looked for a kernel symbol the code object does not have)
+enum JpegSrc { SRC_YUV = 0, SRC_RGB = 1, SRC_BGR = 2, SRC_RGB_PLANAR = 3, SRC_TENSOR = 16 };
+
+constexpr int tensor_src(int dtype, bool packed, bool yuv) {
+  return SRC_TENSOR | dtype << 2 | (packed ? 2 : 0) | (yuv ? 1 : 0);
+}
 
 constexpr int fix16(double x) { return (int)(x * 65536 + 0.5); }
 
@@ -244,6 +254,216 @@ __device__ __forceinline__ void load_row_rgb(const u8* row, int x0, int cw, int 
     }
   }
 }
+
+// ---- where k_jpeg_fdct takes its pixels from ---------------------------------------------------------------------------
+// A source hands out rows of 8 pixels, columns x0.. clamped to the last column cw - 1, as ints 0..255: rgb_row the
+// three colours by name, comp_row component c as it is (kYuv sources).  Everything after the load is the same code.
+// Args travel as a kernel argument; Item is what a lane keeps of its image.  The functions are static and the Item a
+// local of the kernel: held as a member of an object, a vali_surface stayed in memory and was promoted to LDS.
+
+// 8-bit surfaces
+template <int SRC>
+struct SurfIn {
+  static constexpr bool kYuv = SRC == SRC_YUV;
+  struct Args {
+    const vali_surface* d_src;
+  };
+  typedef vali_surface Item;  // what a lane keeps of its image
+  static __device__ __forceinline__ Item item(const Args& a, int i) { return a.d_src[i]; }
+  static __device__ __forceinline__ void rgb_row(const Args&, const Item& s, int y, int x0, int cw, int R[8], int G[8],
+                                                 int B[8]) {
+    if (SRC == SRC_RGB_PLANAR) {
+      load_row_u8((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, cw, R);
+      load_row_u8((const u8*)s.plane[1] + (size_t)y * s.pitch[1], x0, cw, G);
+      load_row_u8((const u8*)s.plane[2] + (size_t)y * s.pitch[2], x0, cw, B);
+    } else if (SRC == SRC_RGB) {
+      load_row_rgb((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, cw, R, G, B);
+    } else {
+      load_row_rgb((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, cw, B, G, R);
+    }
+  }
+  static __device__ __forceinline__ void comp_row(const Args&, const Item& s, int c, int y, int x0, int cw, int v[8]) {
+    // values first, then the choice: a choice between the members themselves is a choice of addresses, and kept s
+    // in memory
+    const void *p0 = s.plane[0], *p1 = s.plane[1], *p2 = s.plane[2];
+    const int q0 = s.pitch[0], q1 = s.pitch[1], q2 = s.pitch[2];
+    const u8* plane = (const u8*)(c == 0 ? p0 : c == 1 ? p1 : p2);
+    const int pitch = c == 0 ? q0 : c == 1 ? q1 : q2;
+    load_row_u8(plane + (size_t)y * pitch, x0, cw, v);
+  }
+};
+
+// One (N, 3, H, W) tensor (vali_jpeg_encode_tensor): elements are quantised in registers on their way in.
+struct TensorArgs {
+  vali_tensor_src t;
+  float scale[3], offset[3];
+  int swap_rb;  // BGR: tensor channel 0 is blue
+};
+
+// an element from its bits, as float32: exact for every dtype
+template <int DT>
+struct TensorElem;
+template <>
+struct TensorElem<VALI_DTYPE_F32> {
+  typedef u32 Bits;
+  static __device__ __forceinline__ float f(u32 b) { return __uint_as_float(b); }
+};
+template <>
+struct TensorElem<VALI_DTYPE_F16> {
+  typedef uint16_t Bits;
+  static __device__ __forceinline__ float f(u32 b) { return (float)__builtin_bit_cast(_Float16, (uint16_t)b); }
+};
+template <>
+struct TensorElem<VALI_DTYPE_BF16> {
+  typedef uint16_t Bits;
+  static __device__ __forceinline__ float f(u32 b) { return __uint_as_float(b << 16); }
+};
+template <>
+struct TensorElem<VALI_DTYPE_U8> {
+  typedef u8 Bits;
+  static __device__ __forceinline__ float f(u32 b) { return (float)b; }
+};
+
+// element i of a run of elements held in dwords
+template <int ES>
+__device__ __forceinline__ u32 elem_bits(const u32* w, int i) {
+  return ES == 4 ? w[i] : ES == 2 ? (w[i / 2] >> (16 * (i % 2))) & 0xFFFF : (w[i / 4] >> (8 * (i % 4))) & 0xFF;
+}
+
+// NE elements from p into dwords: 16-byte loads (p is 16-byte aligned), for uint8 dwords (p is 4-byte aligned)
+template <int ES, int NE>
+__device__ __forceinline__ void load_elems(const void* p, u32* w) {
+  if (ES == 1) {
+#pragma unroll
+    for (int i = 0; i < NE / 4; ++i)
+      w[i] = ((const u32*)p)[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < NE * ES / 16; ++i) {
+      const uint4 q = ((const uint4*)p)[i];
+      w[4 * i] = q.x, w[4 * i + 1] = q.y, w[4 * i + 2] = q.z, w[4 * i + 3] = q.w;
+    }
+  }
+}
+
+// p of the definition (include/vali_hip.h): two roundings, never an FMA; NaN -> 0; clamping first leaves rint nothing
+// outside 0..255 and changes no result
+__device__ __forceinline__ int quantise_elem(float e, float scale, float offset) {
+#pragma clang fp contract(off)
+  float v = __fadd_rn(__fmul_rn(e, scale), offset);
+  v = v != v ? 0.0f : v;
+  return (int)rintf(fminf(fmaxf(v, 0.0f), 255.0f));
+}
+
+template <int DT, bool PACKED, bool YUV>
+struct TensorIn {
+  static constexpr bool kYuv = YUV;
+  typedef TensorArgs Args;
+  typedef TensorElem<DT> E;
+  typedef typename E::Bits Bits;
+  static constexpr int ES = sizeof(Bits);
+  static constexpr uintptr_t kAlign = ES == 1 ? 3 : 15;  // of the vector path
+  typedef const Bits* Item;  // element (item, 0, 0, 0)
+  static __device__ __forceinline__ Item item(const Args& a, int i) {
+    return (const Bits*)a.t.data + (size_t)i * (size_t)a.t.stride_n;
+  }
+
+  // 8 raw elements of channel c of a planar row
+  static __device__ __forceinline__ void planar_row(const Args& a, Item base, int c, int y, int x0, int cw,
+                                                    float e[8]) {
+    const Bits* row = base + (size_t)c * (size_t)a.t.stride_c + (size_t)y * (size_t)a.t.stride_y;
+    const Bits* p = row + x0;
+    if (x0 + 8 <= cw && (((uintptr_t)p) & kAlign) == 0) {
+      u32 w[2 * ES];
+      load_elems<ES, 8>(p, w);
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        e[i] = E::f(elem_bits<ES>(w, i));
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        e[i] = E::f(row[min(x0 + i, cw - 1)]);
+    }
+  }
+  // 8 raw pixels of a channels-last row: e[k] is tensor channel k
+  static __device__ __forceinline__ void packed_row(const Args& a, Item base, int y, int x0, int cw, float e[3][8]) {
+    const Bits* row = base + (size_t)y * (size_t)a.t.stride_y;
+    const Bits* p = row + 3 * x0;
+    if (x0 + 8 <= cw && (((uintptr_t)p) & kAlign) == 0) {
+      u32 w[6 * ES];
+      load_elems<ES, 24>(p, w);
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          e[k][i] = E::f(elem_bits<ES>(w, 3 * i + k));
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const Bits* q = row + 3 * min(x0 + i, cw - 1);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          e[k][i] = E::f(q[k]);
+      }
+    }
+  }
+
+  static __device__ __forceinline__ void rgb_row(const Args& a, Item base, int y, int x0, int cw, int R[8], int G[8],
+                                                 int B[8]) {
+    const bool swap = a.swap_rb != 0;
+    if (PACKED) {
+      float e[3][8];
+      packed_row(a, base, y, x0, cw, e);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int p0 = quantise_elem(e[0][i], a.scale[0], a.offset[0]);
+        const int p2 = quantise_elem(e[2][i], a.scale[2], a.offset[2]);
+        G[i] = quantise_elem(e[1][i], a.scale[1], a.offset[1]);
+        R[i] = swap ? p2 : p0;
+        B[i] = swap ? p0 : p2;
+      }
+    } else {
+      // the channel order decides which plane feeds R and B, not what is computed
+      const int cr = swap ? 2 : 0, cb = 2 - cr;
+      const float sr = swap ? a.scale[2] : a.scale[0], orr = swap ? a.offset[2] : a.offset[0];
+      const float sb = swap ? a.scale[0] : a.scale[2], ob = swap ? a.offset[0] : a.offset[2];
+      float e[8];
+      planar_row(a, base, cr, y, x0, cw, e);
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        R[i] = quantise_elem(e[i], sr, orr);
+      planar_row(a, base, 1, y, x0, cw, e);
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        G[i] = quantise_elem(e[i], a.scale[1], a.offset[1]);
+      planar_row(a, base, cb, y, x0, cw, e);
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        B[i] = quantise_elem(e[i], sb, ob);
+    }
+  }
+  static __device__ __forceinline__ void comp_row(const Args& a, Item base, int c, int y, int x0, int cw, int v[8]) {
+    const float sc = c == 0 ? a.scale[0] : c == 1 ? a.scale[1] : a.scale[2];
+    const float of = c == 0 ? a.offset[0] : c == 1 ? a.offset[1] : a.offset[2];
+    float e[8];
+    if (PACKED) {
+      // the lane's own channel only: every third element, one load each (the clamped form serves the right edge too)
+      const Bits* row = base + (size_t)y * (size_t)a.t.stride_y + c;
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        e[i] = E::f(row[3 * min(x0 + i, cw - 1)]);
+    } else {
+      planar_row(a, base, c, y, x0, cw, e);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      v[i] = quantise_elem(e[i], sc, of);
+  }
+};
+
+template <int SRC>
+using SourceOf = std::conditional_t<(SRC >= SRC_TENSOR), TensorIn<(SRC >> 2) & 3, (SRC & 2) != 0, (SRC & 1) != 0>,
+                                    SurfIn<SRC>>;
 
 __device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
 
@@ -294,24 +514,16 @@ struct SubGeom {
 // every pixel, truncated to 8 bits, then jcsample's h2v1 / h2v2 average with its alternating bias (0, 1 / 1, 2; the
 // quadrant starts on an even chroma column).  Rows are replicated as the component wants them: luma at row h - 1;
 // chroma (CROWS) at 4:2:0 in pairs, row 2 y' + (Y & 1) of y' = min(Y / 2, ch - 1) -- the same row wherever Y < h.
-template <int SRC, int CS, bool LUMA, bool CHROMA, bool CROWS>
-__device__ __forceinline__ void load_quadrant(const vali_surface& s, int x0, int y0, int w, int h, int ch, int* d,
-                                              u32 (*cq)[SubGeom<CS>::NQ]) {
+template <class IN, int CS, bool LUMA, bool CHROMA, bool CROWS>
+__device__ __forceinline__ void load_quadrant(const typename IN::Args& src, const typename IN::Item& s, int x0,
+                                              int y0, int w, int h, int ch, int* d, u32 (*cq)[SubGeom<CS>::NQ]) {
   int even[2][4];  // 4:2:0: the horizontal sums of the even row
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
     const int Y = y0 + r;
     const int y = CROWS && CS == 2 ? min(2 * min(Y >> 1, ch - 1) + (Y & 1), h - 1) : min(Y, h - 1);
     int R[8], G[8], B[8];
-    if (SRC == SRC_RGB_PLANAR) {
-      load_row_u8((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, w, R);
-      load_row_u8((const u8*)s.plane[1] + (size_t)y * s.pitch[1], x0, w, G);
-      load_row_u8((const u8*)s.plane[2] + (size_t)y * s.pitch[2], x0, w, B);
-    } else if (SRC == SRC_RGB) {
-      load_row_rgb((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, w, R, G, B);
-    } else {
-      load_row_rgb((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, w, B, G, R);
-    }
+    IN::rgb_row(src, s, y, x0, w, R, G, B);
     if (LUMA) {
 #pragma unroll
       for (int i = 0; i < 8; ++i)
@@ -349,9 +561,12 @@ __device__ __forceinline__ void load_quadrant(const vali_surface& s, int x0, int
 // and Cr samples of its quadrant of the MCU to the MCU's two chroma lanes through LDS; a chroma lane that loaded its own
 // 16 x 8 or 16 x 16 pixels would do so while the luma lanes of its wave wait.  A workgroup holds whole MCUs (the last
 // 256 % BPM lanes idle); the order of the blocks in the workspace stays the MCU-interleaved scan order.
+// The source's own arguments travel beside FdctArgs: `a` stays a plain kernel argument that nothing takes the address
+// of, so its tables are read where they are used.
 template <int SRC, int CS>
-__global__ void __launch_bounds__(256) k_jpeg_fdct(const FdctArgs a) {
-  static_assert(CS == 0 || SRC != SRC_YUV, "planar YUV sources bring their own chroma planes");
+__global__ void __launch_bounds__(256) k_jpeg_fdct(const FdctArgs a, const typename SourceOf<SRC>::Args src) {
+  using IN = SourceOf<SRC>;
+  static_assert(CS == 0 || !IN::kYuv, "YUV sources bring their own chroma");
   int d[64];
   int gb, c;
   bool dummy;
@@ -366,7 +581,7 @@ __global__ void __launch_bounds__(256) k_jpeg_fdct(const FdctArgs a) {
     c = p < SG::HV ? 0 : p - SG::HV + 1;
     dummy = false;  // a chroma block of an MCU is always real: mcux = bw[1], mcuy = bh[1]
     if (act && c == 0) {
-      const vali_surface s = a.d_src[blockIdx.y];
+      const typename IN::Item s = IN::item(src, blockIdx.y);
       const int w = a.cw[0], h = a.ch[0];
       const int bx = mx * 2 + (p & 1), by = my * SG::V + (p >> 1);
       dummy = bx >= a.bw[0] || by >= a.bh[0];
@@ -378,14 +593,14 @@ __global__ void __launch_bounds__(256) k_jpeg_fdct(const FdctArgs a) {
       const bool own = dummy || (CS == 2 && by * 8 + 8 > h);
       u32 cown[2][SG::NQ] = {};
       if (own)
-        load_quadrant<SRC, CS, false, true, true>(s, bx * 8, by * 8, w, h, a.ch[1], d, cown);
+        load_quadrant<IN, CS, false, true, true>(src, s, bx * 8, by * 8, w, h, a.ch[1], d, cown);
       int lx = bx, ly = by;
       if (by >= a.bh[0]) {
         lx = mx * 2 + 1;
         ly = a.bh[0] - 1;
       }
       lx = min(lx, a.bw[0] - 1);
-      load_quadrant<SRC, CS, true, true, false>(s, lx * 8, ly * 8, w, h, a.ch[1], d, cq);
+      load_quadrant<IN, CS, true, true, false>(src, s, lx * 8, ly * 8, w, h, a.ch[1], d, cq);
       u32* o = s_c + ml * SG::STRIDE + p * SG::NQ;
 #pragma unroll
       for (int k = 0; k < 2; ++k)
@@ -412,7 +627,7 @@ __global__ void __launch_bounds__(256) k_jpeg_fdct(const FdctArgs a) {
     gb = blockIdx.x * 256 + threadIdx.x;
     if (gb >= a.nblocks)
       return;
-    const vali_surface s = a.d_src[blockIdx.y];
+    const typename IN::Item s = IN::item(src, blockIdx.y);
     const int mcu = gb / a.bpm, p = gb - mcu * a.bpm;
     const int mx = mcu % a.mcux, my = mcu / a.mcux;
     c = p < a.HV ? 0 : p - a.HV + 1;
@@ -434,21 +649,11 @@ __global__ void __launch_bounds__(256) k_jpeg_fdct(const FdctArgs a) {
     for (int r = 0; r < 8; ++r) {
       const int y = min(by * 8 + r, ch - 1);
       int* v = d + 8 * r;
-      if (SRC == SRC_YUV) {
-        const u8* plane = (const u8*)(c == 0 ? s.plane[0] : c == 1 ? s.plane[1] : s.plane[2]);
-        const int pitch = c == 0 ? s.pitch[0] : c == 1 ? s.pitch[1] : s.pitch[2];
-        load_row_u8(plane + (size_t)y * pitch, x0, cw, v);
+      if (IN::kYuv) {
+        IN::comp_row(src, s, c, y, x0, cw, v);
       } else {
         int R[8], G[8], B[8];
-        if (SRC == SRC_RGB_PLANAR) {
-          load_row_u8((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, cw, R);
-          load_row_u8((const u8*)s.plane[1] + (size_t)y * s.pitch[1], x0, cw, G);
-          load_row_u8((const u8*)s.plane[2] + (size_t)y * s.pitch[2], x0, cw, B);
-        } else if (SRC == SRC_RGB) {
-          load_row_rgb((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, cw, R, G, B);
-        } else {
-          load_row_rgb((const u8*)s.plane[0] + (size_t)y * s.pitch[0], x0, cw, B, G, R);
-        }
+        IN::rgb_row(src, s, y, x0, cw, R, G, B);
         // jccolor rgb_ycc_convert: this lane's component only
         const int kr = c == 0 ? fix16(0.299) : c == 1 ? -fix16(0.16874) : fix16(0.5);
         const int kg = c == 0 ? fix16(0.587) : c == 1 ? -fix16(0.33126) : -fix16(0.41869);
@@ -779,13 +984,86 @@ void reciprocal(int q, u32* recip, u32* corr_shift) {
 
 // an RGB source with chroma sampling cs: 0 = 1x1, 1 = 2x1, 2 = 2x2
 template <int SRC>
-void launch_fdct(int cs, dim3 grid, hipStream_t s, const FdctArgs& f) {
+void launch_fdct(int cs, dim3 grid, hipStream_t s, const FdctArgs& f, const typename SourceOf<SRC>::Args& src) {
   if (cs == 0)
-    hipLaunchKernelGGL((k_jpeg_fdct<SRC, 0>), grid, dim3(256), 0, s, f);
+    hipLaunchKernelGGL((k_jpeg_fdct<SRC, 0>), grid, dim3(256), 0, s, f, src);
   else if (cs == 1)
-    hipLaunchKernelGGL((k_jpeg_fdct<SRC, 1>), grid, dim3(256), 0, s, f);
+    hipLaunchKernelGGL((k_jpeg_fdct<SRC, 1>), grid, dim3(256), 0, s, f, src);
   else
-    hipLaunchKernelGGL((k_jpeg_fdct<SRC, 2>), grid, dim3(256), 0, s, f);
+    hipLaunchKernelGGL((k_jpeg_fdct<SRC, 2>), grid, dim3(256), 0, s, f, src);
+}
+
+// a tensor source: the channels are colours (coded with chroma sampling cs) or Y, Cb, Cr as they are
+template <int DT, bool PACKED>
+void launch_fdct_tensor(bool yuv, int cs, dim3 grid, hipStream_t s, const FdctArgs& f, const TensorArgs& src) {
+  if (yuv)
+    hipLaunchKernelGGL((k_jpeg_fdct<tensor_src(DT, PACKED, true), 0>), grid, dim3(256), 0, s, f, src);
+  else
+    launch_fdct<tensor_src(DT, PACKED, false)>(cs, grid, s, f, src);
+}
+
+template <int DT>
+void launch_fdct_tensor(bool packed, bool yuv, int cs, dim3 grid, hipStream_t s, const FdctArgs& f,
+                        const TensorArgs& src) {
+  if (packed)
+    launch_fdct_tensor<DT, true>(yuv, cs, grid, s, f, src);
+  else
+    launch_fdct_tensor<DT, false>(yuv, cs, grid, s, f, src);
+}
+
+// what the surface and the tensor entry points share: everything but the arguments' checks and the first launch
+struct JpegLaunch {
+  FdctArgs f;
+  HuffArgs hf;
+  AsmArgs as;
+  int cs;      // chroma sampling of an RGB source: 0 = 1x1, 1 = 2x1, 2 = 2x2
+  dim3 fgrid;
+};
+
+int jpeg_launch_prepare(const char* fn, int n, const JpegGeom& g, const vali_jpeg_params* params, void* workspace,
+                        size_t ws_bytes, uint8_t* d_out, size_t out_stride, JpegLaunch* l) {
+  if ((((uintptr_t)workspace) & 255) != 0)
+    return fail(VALI_ERR_INVALID_ARG, "%s: workspace not 256-byte aligned", fn);
+  if (ws_bytes < jpeg_ws_bytes(g, n))
+    return fail(VALI_ERR_INVALID_ARG, "%s: workspace below vali_jpeg_workspace_size", fn);
+  if (out_stride < (size_t)g.nseg * (g.slot + 2))
+    return fail(VALI_ERR_INVALID_ARG, "%s: out_stride below vali_jpeg_stream_capacity", fn);
+  u8* ws = (u8*)workspace;
+  FdctArgs& f = l->f;
+  f = {};
+  f.coef = (int16_t*)ws;
+  f.H = g.H, f.V = g.V, f.HV = g.H * g.V, f.bpm = g.bpm, f.mcux = g.mcux, f.nblocks = g.nblocks;
+  for (int c = 0; c < 3; ++c)
+    f.cw[c] = g.cw[c], f.ch[c] = g.ch[c], f.bw[c] = g.bw[c], f.bh[c] = g.bh[c];
+  for (int t = 0; t < 2; ++t)
+    for (int k = 0; k < 64; ++k)
+      reciprocal(params->qtable[t][k], &f.recip[t][k], &f.corr_shift[t][k]);
+  l->hf = {(const int16_t*)ws, (u32*)(ws + g.len_at), ws + g.slot_at, g.nblocks, g.nseg, g.bpm, g.H * g.V,
+           g.bps, (u32)g.slot};
+  l->as = {(const u32*)(ws + g.len_at), (const u32*)(ws + g.off_at), ws + g.slot_at, d_out, out_stride, g.nseg,
+           (u32)g.slot};
+  // a subsampled RGB source: workgroups of whole MCUs (fdct_subsampled)
+  l->cs = jpeg_is_rgb(params->format) ? g.H * g.V / 2 : 0;
+  const int per_wg = l->cs ? 256 / g.bpm * g.bpm : 256;
+  l->fgrid = dim3((g.nblocks + per_wg - 1) / per_wg, n);
+  return VALI_OK;
+}
+
+// k_jpeg_huff, k_jpeg_offsets, k_jpeg_assemble, after the source's k_jpeg_fdct
+int jpeg_launch_rest(const char* fn, int n, const JpegLaunch& l, uint32_t* d_sizes, hipStream_t s) {
+  // VALI_LAUNCH_CHECK's message under the entry point's name
+  hipError_t e;
+  hipLaunchKernelGGL(k_jpeg_huff, dim3(l.hf.nseg, n), dim3(64), 0, s, l.hf);
+  if ((e = hipGetLastError()) != hipSuccess)
+    return fail(VALI_ERR_RUNTIME, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
+  hipLaunchKernelGGL(k_jpeg_offsets, dim3(n), dim3(256), 0, s, l.as.seglen, (u32*)l.as.segoff, (u32*)d_sizes,
+                     l.hf.nseg);
+  if ((e = hipGetLastError()) != hipSuccess)
+    return fail(VALI_ERR_RUNTIME, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
+  hipLaunchKernelGGL(k_jpeg_assemble, dim3(l.hf.nseg, n), dim3(256), 0, s, l.as);
+  if ((e = hipGetLastError()) != hipSuccess)
+    return fail(VALI_ERR_RUNTIME, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
+  return VALI_OK;
 }
 
 } // namespace
@@ -872,56 +1150,88 @@ int vali_jpeg_encode_batch(const vali_surface* d_src, int n, int width, int heig
   int rc = jpeg_geom(__func__, n, width, height, params, &g);
   if (rc != VALI_OK)
     return rc;
-  VALI_REQUIRE((((uintptr_t)workspace) & 255) == 0, "workspace not 256-byte aligned");
-  VALI_REQUIRE(ws_bytes >= jpeg_ws_bytes(g, n), "workspace below vali_jpeg_workspace_size");
-  VALI_REQUIRE(out_stride >= (size_t)g.nseg * (g.slot + 2), "out_stride below vali_jpeg_stream_capacity");
+  JpegLaunch l;
+  rc = jpeg_launch_prepare(__func__, n, g, params, workspace, ws_bytes, d_out, out_stride, &l);
+  if (rc != VALI_OK)
+    return rc;
   if (n == 0)
     return VALI_OK;
 
-  u8* ws = (u8*)workspace;
-  FdctArgs f = {};
-  f.d_src = d_src;
-  f.coef = (int16_t*)ws;
-  f.H = g.H, f.V = g.V, f.HV = g.H * g.V, f.bpm = g.bpm, f.mcux = g.mcux, f.nblocks = g.nblocks;
-  for (int c = 0; c < 3; ++c)
-    f.cw[c] = g.cw[c], f.ch[c] = g.ch[c], f.bw[c] = g.bw[c], f.bh[c] = g.bh[c];
-  for (int t = 0; t < 2; ++t)
-    for (int k = 0; k < 64; ++k)
-      reciprocal(params->qtable[t][k], &f.recip[t][k], &f.corr_shift[t][k]);
-  HuffArgs hf = {(const int16_t*)ws, (u32*)(ws + g.len_at), ws + g.slot_at, g.nblocks, g.nseg, g.bpm, g.H * g.V,
-                 g.bps, (u32)g.slot};
-  AsmArgs as = {(const u32*)(ws + g.len_at), (const u32*)(ws + g.off_at), ws + g.slot_at, d_out, out_stride, g.nseg,
-                (u32)g.slot};
-
   hipStream_t s = as_stream(stream);
   VALI_ENTRY(s);
-  // a subsampled RGB source: workgroups of whole MCUs (fdct_subsampled)
-  const int cs = jpeg_is_rgb(format) ? g.H * g.V / 2 : 0;  // 0 = 1x1, 1 = 2x1, 2 = 2x2
-  const int per_wg = cs ? 256 / g.bpm * g.bpm : 256;
-  const dim3 fgrid((g.nblocks + per_wg - 1) / per_wg, n);
   switch (format) {
   case VALI_FMT_RGB:
-    launch_fdct<SRC_RGB>(cs, fgrid, s, f);
+    launch_fdct<SRC_RGB>(l.cs, l.fgrid, s, l.f, {d_src});
     break;
   case VALI_FMT_BGR:
-    launch_fdct<SRC_BGR>(cs, fgrid, s, f);
+    launch_fdct<SRC_BGR>(l.cs, l.fgrid, s, l.f, {d_src});
     break;
   case VALI_FMT_RGB_PLANAR:
-    launch_fdct<SRC_RGB_PLANAR>(cs, fgrid, s, f);
+    launch_fdct<SRC_RGB_PLANAR>(l.cs, l.fgrid, s, l.f, {d_src});
     break;
   default:
-    hipLaunchKernelGGL((k_jpeg_fdct<SRC_YUV, 0>), fgrid, dim3(256), 0, s, f);
+    hipLaunchKernelGGL((k_jpeg_fdct<SRC_YUV, 0>), l.fgrid, dim3(256), 0, s, l.f, SurfIn<SRC_YUV>::Args{d_src});
     break;
   }
   VALI_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_jpeg_huff, dim3(g.nseg, n), dim3(64), 0, s, hf);
+  return jpeg_launch_rest(__func__, n, l, d_sizes, s);
+}
+
+int vali_jpeg_encode_tensor(const vali_tensor_src* src, const float scale[3], const float offset[3],
+                            const vali_jpeg_params* params, void* workspace, size_t ws_bytes, uint8_t* d_out,
+                            size_t out_stride, uint32_t* d_sizes, vali_stream_t stream) {
+  VALI_REQUIRE(src && scale && offset && params && workspace && d_out && d_sizes, "null argument");
+  VALI_REQUIRE(src->data, "null tensor data");
+  VALI_REQUIRE(src->dtype >= VALI_DTYPE_F32 && src->dtype <= VALI_DTYPE_U8,
+               "dtype must be VALI_DTYPE_F32, _F16, _BF16 or _U8");
+  VALI_REQUIRE(src->packed == 0 || src->packed == 1, "packed must be 0 or 1");
+  VALI_REQUIRE(src->n >= 1 && src->n <= 65535, "batch size out of range (1..65535)");
+  VALI_REQUIRE(src->width >= 1 && src->height >= 1 && src->width <= 65535 && src->height <= 65535,
+               "size outside 1..65535");
+  VALI_REQUIRE(src->stride_n > 0 && src->stride_y > 0 && (src->packed || src->stride_c > 0),
+               "strides must be positive");
+  VALI_REQUIRE(src->stride_y >= (int64_t)src->width * (src->packed ? 3 : 1), "stride_y is shorter than a row");
+  const uintptr_t esize = src->dtype == VALI_DTYPE_F32 ? 4 : src->dtype == VALI_DTYPE_U8 ? 1 : 2;
+  VALI_REQUIRE(((uintptr_t)src->data & (esize - 1)) == 0, "data is not aligned to its element");
+  for (int c = 0; c < 3; ++c)
+    VALI_REQUIRE(std::isfinite(scale[c]) && std::isfinite(offset[c]), "scale and offset must be finite");
+  // the channels are colours, or Y, Cb, Cr as they are: a tensor has no subsampled planes
+  if (!jpeg_is_rgb(params->format) && params->format != VALI_FMT_YUV444)
+    return fail(VALI_ERR_UNSUPPORTED, "%s: format %d cannot name the channels of a tensor", __func__, params->format);
+  const int n = src->n;
+  JpegGeom g;
+  int rc = jpeg_geom(__func__, n, src->width, src->height, params, &g);
+  if (rc != VALI_OK)
+    return rc;
+  JpegLaunch l;
+  rc = jpeg_launch_prepare(__func__, n, g, params, workspace, ws_bytes, d_out, out_stride, &l);
+  if (rc != VALI_OK)
+    return rc;
+  TensorArgs ta = {};
+  ta.t = *src;
+  for (int c = 0; c < 3; ++c)
+    ta.scale[c] = scale[c], ta.offset[c] = offset[c];
+  ta.swap_rb = params->format == VALI_FMT_BGR;
+  const bool yuv = params->format == VALI_FMT_YUV444, packed = src->packed != 0;
+
+  hipStream_t s = as_stream(stream);
+  VALI_ENTRY(s);
+  switch (src->dtype) {
+  case VALI_DTYPE_F32:
+    launch_fdct_tensor<VALI_DTYPE_F32>(packed, yuv, l.cs, l.fgrid, s, l.f, ta);
+    break;
+  case VALI_DTYPE_F16:
+    launch_fdct_tensor<VALI_DTYPE_F16>(packed, yuv, l.cs, l.fgrid, s, l.f, ta);
+    break;
+  case VALI_DTYPE_BF16:
+    launch_fdct_tensor<VALI_DTYPE_BF16>(packed, yuv, l.cs, l.fgrid, s, l.f, ta);
+    break;
+  default:
+    launch_fdct_tensor<VALI_DTYPE_U8>(packed, yuv, l.cs, l.fgrid, s, l.f, ta);
+    break;
+  }
   VALI_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_jpeg_offsets, dim3(n), dim3(256), 0, s, (const u32*)(ws + g.len_at), (u32*)(ws + g.off_at),
-                     (u32*)d_sizes, g.nseg);
-  VALI_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_jpeg_assemble, dim3(g.nseg, n), dim3(256), 0, s, as);
-  VALI_LAUNCH_CHECK();
-  return VALI_OK;
+  return jpeg_launch_rest(__func__, n, l, d_sizes, s);
 }
 
 } // extern "C"

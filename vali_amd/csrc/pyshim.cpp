@@ -53,6 +53,10 @@ struct TensorDst {
   vali_tensor_dst t;
 };
 
+struct TensorSrc {
+  vali_tensor_src t;
+};
+
 struct JpegParams {
   vali_jpeg_params p;
 };
@@ -545,6 +549,7 @@ PYBIND11_MODULE(_vali_shim, m) {
   m.attr("DTYPE_F32") = (int)VALI_DTYPE_F32;
   m.attr("DTYPE_F16") = (int)VALI_DTYPE_F16;
   m.attr("DTYPE_BF16") = (int)VALI_DTYPE_BF16;
+  m.attr("DTYPE_U8") = (int)VALI_DTYPE_U8;
   m.def("nv12_preproc_roi_tensor",
         [](uintptr_t d_src, uintptr_t d_roi, const TensorDst& dst, const PreprocParams& p, bool pad,
            const std::array<uint8_t, 3>& pad_rgb, uintptr_t stream) {
@@ -612,6 +617,28 @@ PYBIND11_MODULE(_vali_shim, m) {
            size_t ws_bytes, uintptr_t d_out, size_t out_stride, uintptr_t d_sizes, uintptr_t stream) {
           return vali_jpeg_encode_batch((const vali_surface*)P(d_src), n, width, height, format, &j.p, P(workspace),
                                         ws_bytes, (uint8_t*)P(d_out), out_stride, (uint32_t*)P(d_sizes), P(stream));
+        },
+        py::call_guard<py::gil_scoped_release>());
+
+  // the batch tensor the encoder reads: the arguments of TensorDst; vali_jpeg_encode_tensor judges it
+  py::class_<TensorSrc>(m, "TensorSrc")
+      .def(py::init([](uintptr_t data, int dtype, int packed, int n, int width, int height, int64_t stride_n,
+                       int64_t stride_c, int64_t stride_y) {
+        TensorSrc d;
+        std::memset(&d.t, 0, sizeof(d.t));
+        d.t.data = P(data);
+        d.t.dtype = dtype; d.t.packed = packed;
+        d.t.n = n; d.t.width = width; d.t.height = height;
+        d.t.stride_n = stride_n; d.t.stride_c = stride_c; d.t.stride_y = stride_y;
+        return d;
+      }));
+  m.attr("TENSOR_SRC_SIZE") = sizeof(vali_tensor_src);
+  m.def("jpeg_encode_tensor",
+        [](const TensorSrc& src, const std::array<float, 3>& scale, const std::array<float, 3>& offset,
+           const JpegParams& j, uintptr_t workspace, size_t ws_bytes, uintptr_t d_out, size_t out_stride,
+           uintptr_t d_sizes, uintptr_t stream) {
+          return vali_jpeg_encode_tensor(&src.t, scale.data(), offset.data(), &j.p, P(workspace), ws_bytes,
+                                         (uint8_t*)P(d_out), out_stride, (uint32_t*)P(d_sizes), P(stream));
         },
         py::call_guard<py::gil_scoped_release>());
 

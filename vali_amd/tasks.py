@@ -996,33 +996,35 @@ class RoiBatch:
 
 # DLPack dtype (code, bits) -> (name, enum vali_dtype): kDLFloat = 2, kDLBfloat = 4
 _TENSOR_DTYPES = {(2, 32): ("float32", 0), (2, 16): ("float16", 1), (4, 16): ("bfloat16", 2)}
+# ... and what the JPEG encoder also reads: kDLUInt = 1
+_TENSOR_SRC_DTYPES = dict(_TENSOR_DTYPES)
+_TENSOR_SRC_DTYPES[(1, 8)] = ("uint8", 3)
 
 
-def tensor_layout(shape, strides, code, bits):
-    """Classify a destination tensor from its DLPack view, without a device: ("planar" | "packed", dtype name).
-    `shape` is the logical (N, 3, H, W), `strides` are in elements.  planar: x stride 1 (contiguous tensors and every
-    slice that keeps rows contiguous); packed: c stride 1 and x stride 3 (channels last).  ValueError, naming what is
-    wrong, for everything else."""
+def _layout(who, dtypes, shape, strides, code, bits):
+    """the rules tensor_layout and tensor_src_layout share; `who` starts the messages"""
     shape = tuple(int(v) for v in shape)
-    dtype = _TENSOR_DTYPES.get((int(code), int(bits)))
+    dtype = dtypes.get((int(code), int(bits)))
     if dtype is None:
-        raise ValueError(f"out: the dtype must be float32, float16 or bfloat16 (DLPack code {code}, {bits} bits)")
+        names = [d[0] for d in dtypes.values()]
+        raise ValueError(f"{who}: the dtype must be {', '.join(names[:-1])} or {names[-1]} "
+                         f"(DLPack code {code}, {bits} bits)")
     if len(shape) != 4:
-        raise ValueError(f"out: need a 4-D tensor (N, 3, H, W), got {len(shape)}-D {shape}")
+        raise ValueError(f"{who}: need a 4-D tensor (N, 3, H, W), got {len(shape)}-D {shape}")
     if strides is None:
         strides = (3 * shape[2] * shape[3], shape[2] * shape[3], shape[3], 1)
     strides = tuple(int(v) for v in strides)
     if len(strides) != 4:
-        raise ValueError(f"out: {len(strides)} strides for a 4-D tensor")
+        raise ValueError(f"{who}: {len(strides)} strides for a 4-D tensor")
     n, c, h, w = shape
     if c != 3:
-        raise ValueError(f"out: need 3 channels (N, 3, H, W), got C = {c}")
+        raise ValueError(f"{who}: need 3 channels (N, 3, H, W), got C = {c}")
     if n < 1 or h < 1 or w < 1:
-        raise ValueError(f"out: empty tensor {shape}")
+        raise ValueError(f"{who}: empty tensor {shape}")
     if n > 65535:
-        raise ValueError("out: at most 65535 items")
+        raise ValueError(f"{who}: at most 65535 items")
     if any(v < 0 for v in strides):
-        raise ValueError(f"out: negative strides {strides} (a flipped view) are not supported")
+        raise ValueError(f"{who}: negative strides {strides} (a flipped view) are not supported")
     sn, sc, sy, sx = strides
     # a dimension of size 1 has no meaningful stride: give it the one its layout would have
     if sx == 1 or (w == 1 and sc != 1):
@@ -1030,57 +1032,88 @@ def tensor_layout(shape, strides, code, bits):
     elif sc == 1 and (sx == 3 or w == 1):
         layout, row = "packed", 3 * w
     else:
-        raise ValueError(f"out: strides {strides} are neither planar (x stride 1) nor channels last (c stride 1, "
+        raise ValueError(f"{who}: strides {strides} are neither planar (x stride 1) nor channels last (c stride 1, "
                          "x stride 3) -- a transposed or strided view")
     if (h > 1 and sy < row) or (layout == "planar" and sc < 1) or (n > 1 and sn < 1):
-        raise ValueError(f"out: strides {strides} of a {layout} {shape} tensor: rows overlap -- a transposed or "
+        raise ValueError(f"{who}: strides {strides} of a {layout} {shape} tensor: rows overlap -- a transposed or "
                          "broadcast view")
     return layout, dtype[0]
 
 
-def _tensor_dst(out, gpu_id):
-    """(shim.TensorDst, layout, dtype name, (n, h, w), holder) of a destination tensor on `gpu_id`"""
-    if hasattr(out, "__dlpack__"):
-        info, holder = shim.dlpack_import(out.__dlpack__())
+def tensor_layout(shape, strides, code, bits):
+    """Classify a destination tensor from its DLPack view, without a device: ("planar" | "packed", dtype name).
+    `shape` is the logical (N, 3, H, W), `strides` are in elements.  planar: x stride 1 (contiguous tensors and every
+    slice that keeps rows contiguous); packed: c stride 1 and x stride 3 (channels last).  ValueError, naming what is
+    wrong, for everything else."""
+    return _layout("out", _TENSOR_DTYPES, shape, strides, code, bits)
+
+
+def tensor_src_layout(shape, strides, code, bits):
+    """tensor_layout's rules for a tensor that is read (PyNvJpegEncoder.RunTensor): uint8 (DLPack code 1, 8 bits) is a
+    dtype too, and the messages speak of `tensor`."""
+    return _layout("tensor", _TENSOR_SRC_DTYPES, shape, strides, code, bits)
+
+
+def _tensor_view(who, layout_of, cai_types, t, gpu_id):
+    """(ptr, layout, dtype name, (n, h, w), (sn, sc, sy) in elements, holder) of a device tensor on `gpu_id`, seen
+    through __dlpack__ or __cuda_array_interface__ (`cai_types`: typestr -> (DLPack code, bits))"""
+    if hasattr(t, "__dlpack__"):
+        info, holder = shim.dlpack_import(t.__dlpack__())
         if info["lanes"] != 1:
-            raise ValueError("out: vector dtypes are not supported")
+            raise ValueError(f"{who}: vector dtypes are not supported")
         shape, strides, code, bits = tuple(info["shape"]), tuple(info["strides"]), info["code"], info["bits"]
-        layout, dtype = tensor_layout(shape, strides, code, bits)
+        layout, dtype = layout_of(shape, strides, code, bits)
         if info["device_type"] not in (int(DLDeviceType.kDLROCM), int(DLDeviceType.kDLCUDA)):
-            raise ValueError("out: the tensor must live on the GPU")
+            raise ValueError(f"{who}: the tensor must live on the GPU")
         ptr, device = int(info["ptr"]), int(info["device_id"])
-    elif hasattr(out, "__cuda_array_interface__"):
-        cai = out.__cuda_array_interface__
+    elif hasattr(t, "__cuda_array_interface__"):
+        cai = t.__cuda_array_interface__
         typestr = cai["typestr"]
-        if typestr not in ("<f4", "<f2"):
-            raise ValueError(f"out: the dtype must be float32 or float16 through __cuda_array_interface__, got {typestr}")
-        bits = 32 if typestr == "<f4" else 16
+        if typestr not in cai_types:
+            names = " or ".join(_TENSOR_SRC_DTYPES[v][0] for v in cai_types.values())
+            raise ValueError(f"{who}: the dtype must be {names} through __cuda_array_interface__, got {typestr}")
+        code, bits = cai_types[typestr]
         shape = tuple(int(v) for v in cai["shape"])
         strides = cai.get("strides")
         if strides is not None:
             if any(int(v) % (bits // 8) for v in strides):
-                raise ValueError("out: strides that are no multiple of the element size")
+                raise ValueError(f"{who}: strides that are no multiple of the element size")
             strides = tuple(int(v) // (bits // 8) for v in strides)
-        layout, dtype = tensor_layout(shape, strides, 2, bits)
+        layout, dtype = layout_of(shape, strides, code, bits)
         if strides is None:
             strides = (3 * shape[2] * shape[3], shape[2] * shape[3], shape[3], 1)
-        ptr, holder = int(cai["data"][0]), out
-        dev = getattr(out, "device", None)
+        ptr, holder = int(cai["data"][0]), t
+        dev = getattr(t, "device", None)
         device = dev.index if getattr(dev, "type", None) == "cuda" and dev.index is not None else shim.ptr_device(ptr)
     else:
-        raise ValueError("out: a device tensor with __dlpack__ or __cuda_array_interface__")
+        raise ValueError(f"{who}: a device tensor with __dlpack__ or __cuda_array_interface__")
     if device != gpu_id:
-        raise ValueError(f"out: the tensor is on device {device}, the task on {gpu_id}")
+        raise ValueError(f"{who}: the tensor is on device {device}, the task on {gpu_id}")
     n, _, h, w = shape
     sn, sc, sy, _ = strides
     row = w if layout == "planar" else 3 * w
     # strides of dimensions of size 1 are arbitrary: the kernel's addressing needs them positive and rows apart
-    sy = max(sy, row)
-    sc = max(sc, 1)
-    sn = max(sn, 1)
+    return ptr, layout, dtype, (n, h, w), (max(sn, 1), max(sc, 1), max(sy, row)), holder
+
+
+def _tensor_dst(out, gpu_id):
+    """(shim.TensorDst, layout, dtype name, (n, h, w), holder) of a destination tensor on `gpu_id`"""
+    ptr, layout, dtype, (n, h, w), (sn, sc, sy), holder = _tensor_view(
+        "out", tensor_layout, {"<f4": (2, 32), "<f2": (2, 16)}, out, gpu_id)
     code = {"float32": shim.DTYPE_F32, "float16": shim.DTYPE_F16, "bfloat16": shim.DTYPE_BF16}[dtype]
     dst = shim.TensorDst(ptr, code, 1 if layout == "packed" else 0, n, w, h, sn, sc, sy)
     return dst, layout, dtype, (n, h, w), holder
+
+
+def _tensor_src(tensor, gpu_id):
+    """(shim.TensorSrc, layout, dtype name, (n, h, w), (ptr, stride_n, stride_c, stride_y), holder) of a tensor the
+    JPEG encoder on `gpu_id` reads; strides in elements"""
+    ptr, layout, dtype, (n, h, w), (sn, sc, sy), holder = _tensor_view(
+        "tensor", tensor_src_layout, {"<f4": (2, 32), "<f2": (2, 16), "|u1": (1, 8)}, tensor, gpu_id)
+    code = {"float32": shim.DTYPE_F32, "float16": shim.DTYPE_F16, "bfloat16": shim.DTYPE_BF16,
+            "uint8": shim.DTYPE_U8}[dtype]
+    src = shim.TensorSrc(ptr, code, 1 if layout == "packed" else 0, n, w, h, sn, sc, sy)
+    return src, layout, dtype, (n, h, w), (ptr, sn, sc, sy), holder
 
 
 class _Canvas:
