@@ -412,13 +412,32 @@ VALI_API int vali_rgb_preproc_roi_tensor(const vali_surface* d_src, const vali_r
  *     zero; q from the Annex K tables scaled as jpeg_set_quality(quality, force_baseline = TRUE);
  *   - Huffman coding with the Annex K tables, a restart marker every restart_interval MCUs (DRI).
  * A file is vali_jpeg_header + the entropy data of vali_jpeg_encode_batch + EOI (FF D9).
+ *
+ * optimize = 1: every image is coded with Huffman tables built from its own symbol statistics, libjpeg's
+ * optimize_coding (tests/jpeg_optimize_model.py restates it and is pinned to Pillow's optimize=True table for table
+ * and byte for byte).  Nothing before entropy coding changes.  The counts are those of the symbols the scan codes: for
+ * tables DC 0 (Y) and DC 1 (Cb and Cr together) the size category of every DC difference, prediction restarting with
+ * every restart segment; for AC 0 and AC 1 every (run << 4 | size), ZRL and EOB; the dummy blocks of partial MCUs
+ * included.  Each table is jpeg_gen_optimal_table of its counts: a pseudo-symbol 256 of count 1; merges of the two
+ * least frequent entries (c1 the largest index among the minima, c2 the largest among the minima of the rest, the sum
+ * stays at c1); code length = depth in the merge tree; lengths above 16 limited as Annex K.2 does; one code of the
+ * longest length removed for the pseudo-symbol; HUFFVAL by length, then by value; codes as Annex C.  The counts fit 32
+ * bits: an image's output slot is addressed with 32 bits, which caps it far below 2^32 symbols.
+ * With optimize = 1 vali_jpeg_header writes only what does not depend on the pixels, SOI, APP0, DQT and SOF0, and the
+ * device writes, in front of image i's entropy data at d_out + i * out_stride, one DHT segment with the image's four
+ * tables (in the order 0x00, 0x10, 0x01, 0x11 of the plain header), DRI and SOS; d_sizes[i] counts all of it.  A file
+ * is still vali_jpeg_header + the device's bytes + EOI.  vali_jpeg_stream_capacity grows by the worst case of that
+ * prefix (440 bytes: a DHT of 4 + 4 * 17 + 12 + 12 + 162 + 162, DRI 6, SOS 14), vali_jpeg_workspace_size by each
+ * image's four histograms, four code tables and DHT parts.  Any other value of optimize is VALI_ERR_INVALID_ARG from
+ * every function that takes params; with optimize = 0 every function returns and writes what it always did.
  */
 typedef struct vali_jpeg_params {
   int32_t quality;          /* 1..100 (clamped by vali_jpeg_params_init)                           */
   int32_t format;           /* enum vali_pixel_format of the source surfaces                       */
   int32_t h_samp, v_samp;   /* luma sampling factors: 1x1 (4:4:4), 2x1 (4:2:2), 2x2 (4:2:0)        */
   int32_t restart_interval; /* MCUs per restart segment: 1 .. 64 / blocks per MCU                  */
-  int32_t reserved[3];
+  int32_t optimize;         /* 0: the Annex K Huffman tables; 1: each image's own (below)            */
+  int32_t reserved[2];
   uint8_t qtable[2][64];    /* quantisation tables in natural order: 0 luma, 1 both chroma, 1..255 */
 } vali_jpeg_params;         /* 160 bytes */
 
@@ -429,7 +448,8 @@ VALI_API int vali_jpeg_params_init(int quality, int format, vali_jpeg_params* ou
  * RGB_PLANAR (chroma is downsampled as above); for a YUV format only its own.  Everything else is
  * VALI_ERR_INVALID_ARG; a format that cannot be encoded is VALI_ERR_UNSUPPORTED */
 VALI_API int vali_jpeg_params_init_sampled(int quality, int format, int h_samp, int v_samp, vali_jpeg_params* out);
-/* host only: SOI, APP0 (JFIF), DQT, SOF0, DHT, DRI, SOS of a width x height image (1..65535) into out[0..cap),
+/* host only: SOI, APP0 (JFIF), DQT, SOF0, DHT, DRI, SOS of a width x height image (1..65535) into out[0..cap)
+ * (optimize = 1: SOI, APP0, DQT, SOF0 only; the rest comes from the device with the entropy data),
  * its length in *len.  out == NULL asks for the length only; cap < length is VALI_ERR_INVALID_ARG (*len still set) */
 VALI_API int vali_jpeg_header(int width, int height, const vali_jpeg_params* params, uint8_t* out, size_t cap,
                               size_t* len);
@@ -442,8 +462,8 @@ VALI_API int vali_jpeg_stream_capacity(int width, int height, const vali_jpeg_pa
  * (sizes as everywhere: YUV420 even width and height, YUV422 even width; an RGB source takes any size at any sampling).  Image i's entropy data, restart markers
  * included, header and EOI not, goes to d_out + i * out_stride (out_stride >= vali_jpeg_stream_capacity), its
  * length in bytes to d_sizes[i] (device memory).  workspace: ws_bytes >= vali_jpeg_workspace_size, device memory,
- * 256-byte aligned.  Four launches in stream order; nothing is allocated and nothing synchronises, so the call
- * can be captured into a graph.
+ * 256-byte aligned.  Four launches in stream order (optimize = 1: a memset of the histograms and six launches);
+ * nothing is allocated and nothing synchronises, so the call can be captured into a graph.
  */
 VALI_API int vali_jpeg_encode_batch(const vali_surface* d_src, int n, int width, int height, int format,
                                     const vali_jpeg_params* params, void* workspace, size_t ws_bytes, uint8_t* d_out,
@@ -463,8 +483,8 @@ VALI_API int vali_jpeg_encode_batch(const vali_surface* d_src, int n, int width,
  *   YUV444: Y, Cb, Cr, coded as they are, 1x1;  every other format: VALI_ERR_UNSUPPORTED.
  * The file never depends on the tensor's layout or dtype beyond p.  Any size, odd ones included, at every sampling.
  * Workspace, stream capacity and header: vali_jpeg_workspace_size, vali_jpeg_stream_capacity and vali_jpeg_header
- * of (src->n, src->width, src->height, params).  Output layout, d_sizes and the four launches are those of
- * vali_jpeg_encode_batch; src is a HOST struct that travels in the kernel arguments; nothing is allocated, nothing
+ * of (src->n, src->width, src->height, params).  Output layout, d_sizes and the launches (params->optimize included:
+ * everything after the first launch is shared) are those of vali_jpeg_encode_batch; src is a HOST struct that travels in the kernel arguments; nothing is allocated, nothing
  * synchronises.  VALI_ERR_INVALID_ARG, before any device is touched, for: null arguments; dtype outside 0..3 or
  * packed outside 0..1; n outside 1..65535; a size outside 1..65535; strides <= 0 or stride_y below the row's extent
  * (width, 3 * width when packed); data not aligned to its element; a non-finite scale or offset; and whatever

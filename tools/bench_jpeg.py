@@ -7,6 +7,8 @@ batch 1 / 16 / 64.  Prints one JSON line per configuration and a markdown table 
       RGB batch 16 coded 4:4:4, 4:2:2 and 4:2:0 (Context(..., subsampling=...)), hip only, the three alternating in
       one process, best of 5 Run calls each (profiles/jpeg_subsampling.md); with --quick --subsampling 420 one of them
       alone, for a profiling run
+  --optimize: every context with optimize=True (per-image Huffman tables, profiles/jpeg_optimize.md); with --sampled
+      each sampling is timed with and without it
 """
 import argparse
 import json
@@ -57,6 +59,8 @@ def sampled(a):
     surfs = [pool[i % len(pool)] for i in range(16)]
     enc = vali.PyNvJpegEncoder(a.gpu, backend="hip")
     ctxs = {s: enc.Context(90, vali.RGB, s) for s in ("444", "422", "420")}
+    if a.optimize:
+        ctxs.update({s + " optimize": enc.Context(90, vali.RGB, s, optimize=True) for s in ("444", "422", "420")})
     best, nbytes = {s: float("inf") for s in ctxs}, {}
     for s, ctx in ctxs.items():
         enc.Run(ctx, surfs)                                   # warm-up
@@ -80,6 +84,7 @@ def main():
     ap.add_argument("--sampled", action="store_true")
     ap.add_argument("--subsampling", choices=["444", "422", "420"], default=None, help="of RGB surfaces")
     ap.add_argument("--size", default=None, help="WxH instead of the default sizes")
+    ap.add_argument("--optimize", action="store_true", help="per-image Huffman tables")
     a = ap.parse_args()
     if a.sampled:
         return sampled(a)
@@ -97,10 +102,10 @@ def main():
                 surfs = [pool[i % len(pool)] for i in range(n)]
                 for backend in backends:
                     enc = vali.PyNvJpegEncoder(a.gpu, backend=backend)
-                    ctx = enc.Context(90, fmt, a.subsampling if fmt == vali.RGB else None)
+                    ctx = enc.Context(90, fmt, a.subsampling if fmt == vali.RGB else None, optimize=a.optimize)
                     reps = 10 if backend == "hip" else (3 if n == 1 else 1)
                     t, nbytes = run(enc, ctx, surfs, reps)
-                    r = {"size": f"{w}x{h}", "format": fmt.name, "batch": n, "backend": backend,
+                    r = {"size": f"{w}x{h}", "format": fmt.name, "batch": n, "backend": backend, "optimize": a.optimize,
                          "ms_per_call": round(t * 1e3, 3), "images_per_s": round(n / t, 1),
                          "mean_file_kib": round(nbytes / n / 1024, 1)}
                     rows.append(r)

@@ -735,10 +735,15 @@ class NvJpegEncodeContext:
     # JpegInfo.sampling string -> luma sampling factors, in the order of PIL's `subsampling` values 0, 1, 2
     _SAMPLINGS = {"444": (1, 1), "422": (2, 1), "420": (2, 2)}
 
-    def __init__(self, compression: int = 100, pixel_format: PixelFormat = F.RGB, subsampling: Optional[str] = None):
+    def __init__(self, compression: int = 100, pixel_format: PixelFormat = F.RGB, subsampling: Optional[str] = None,
+                 optimize: bool = False):
         """subsampling: None (RGB, BGR and RGB_PLANAR are coded 4:4:4, a YUV format with its own sampling), or "444",
         "422" or "420" for RGB, BGR and RGB_PLANAR: chroma is then downsampled as libjpeg-turbo does by default.  A YUV
-        format takes its own sampling only."""
+        format takes its own sampling only.
+        optimize: every file gets Huffman tables built from its own symbol statistics (libjpeg's optimize_coding)
+        instead of the Annex K tables: the same pixels in fewer bytes, for one more pass over the coefficients."""
+        if not isinstance(optimize, (bool, np.bool_)):
+            raise ValueError(f"optimize must be a bool, not {optimize!r}")
         fmt = PixelFormat(pixel_format)
         if fmt not in self._SUBSAMPLING:
             raise ValueError("unsupported pixel format")            # std::invalid_argument, :123
@@ -750,6 +755,7 @@ class NvJpegEncodeContext:
         elif subsampling != own and fmt not in (F.RGB, F.BGR, F.RGB_PLANAR):
             raise ValueError(f"{fmt.name} surfaces are coded {own}: their chroma planes are taken as they are")
         self._compression, self._format, self._subsampling = int(compression), fmt, subsampling
+        self._optimize = bool(optimize)
 
     def Compression(self) -> int:
         return self._compression
@@ -760,6 +766,10 @@ class NvJpegEncodeContext:
     def Subsampling(self) -> str:
         """the sampling of the files: "444", "422" or "420" """
         return self._subsampling
+
+    def Optimize(self) -> bool:
+        """whether every file carries Huffman tables of its own"""
+        return self._optimize
 
 
 _TENSOR_ESIZE = {"float32": 4, "float16": 2, "bfloat16": 2, "uint8": 1}
@@ -809,7 +819,10 @@ class PyNvJpegEncoder:
       Every surface of one size goes into one launch; the header (cached per size, format, quality and sampling) and
       EOI are added on the host.  RGB, BGR and RGB_PLANAR surfaces are coded 4:4:4, or 4:2:2 / 4:2:0 with
       `Context(..., subsampling="422" / "420")`.  The files decode to what the "cpu" backend's files decode to (the encoder definition is
-      libjpeg's); they differ in bytes only by the restart markers the GPU coder needs (DRI)."""
+      libjpeg's); they differ in bytes only by the restart markers the GPU coder needs (DRI).
+      `Context(..., optimize=True)`: every file is coded with Huffman tables built on the GPU from its own symbol
+      counts (libjpeg's jpeg_gen_optimal_table); its DHT then comes from the device with the entropy data.  The "cpu"
+      backend passes optimize=True to Pillow."""
 
     BACKENDS = ("cpu", "hip")
 
@@ -837,8 +850,8 @@ class PyNvJpegEncoder:
         return self._backend
 
     def Context(self, compression: int, pixel_format: PixelFormat,
-                subsampling: Optional[str] = None) -> NvJpegEncodeContext:
-        return NvJpegEncodeContext(compression, pixel_format, subsampling)
+                subsampling: Optional[str] = None, optimize: bool = False) -> NvJpegEncodeContext:
+        return NvJpegEncodeContext(compression, pixel_format, subsampling, optimize)
 
     def _image(self, fmt: PixelFormat, w: int, h: int, host: np.ndarray):
         from PIL import Image
@@ -876,7 +889,8 @@ class PyNvJpegEncoder:
             out = io.BytesIO()
             q = max(1, min(100, context.Compression()))
             self._image(surf.Format, surf.Width, surf.Height, host).save(
-                out, format="JPEG", quality=q, subsampling=list(NvJpegEncodeContext._SAMPLINGS).index(context.Subsampling()))
+                out, format="JPEG", quality=q, subsampling=list(NvJpegEncodeContext._SAMPLINGS).index(context.Subsampling()),
+                optimize=context.Optimize())
             buffers.append(np.frombuffer(out.getvalue(), np.uint8).copy())
         return buffers, TaskExecInfo.SUCCESS
 
@@ -900,19 +914,19 @@ class PyNvJpegEncoder:
         if fmt not in (F.RGB, F.BGR, F.RGB_PLANAR, F.YUV444) or not (1 <= w <= 65535 and 1 <= h <= 65535):
             return [], TaskExecInfo.FAIL
         q = max(1, min(100, context.Compression()))
-        samp = context.Subsampling()
+        samp, opt = context.Subsampling(), context.Optimize()
         if self._backend == "hip":
-            params = self._jpeg_params(q, fmt, samp)
+            params = self._jpeg_params(q, fmt, samp, opt)
             ws, out, d_sizes, cap = self._buffers(n, w, h, params)
             rc = shim.jpeg_encode_tensor(src, scale, offset, params, ws, self._ws_bytes, out, cap, d_sizes, self._stream)
             if rc != 0:
                 return [], TaskExecInfo.FAIL
-            buffers = self._fetch(n, self._header(w, h, fmt, q, samp), out, cap, d_sizes)
+            buffers = self._fetch(n, self._header(w, h, fmt, q, samp, opt), out, cap, d_sizes)
             del holder                              # the tensor was kept alive until the final synchronisation
             return buffers, TaskExecInfo.SUCCESS
-        return self._run_tensor_cpu(fmt, q, samp, layout, dtype, (n, h, w), where, scale, offset)
+        return self._run_tensor_cpu(fmt, q, samp, layout, dtype, (n, h, w), where, scale, offset, opt)
 
-    def _run_tensor_cpu(self, fmt, q, samp, layout, dtype, shape, where, scale, offset) -> Tuple[list, TaskExecInfo]:
+    def _run_tensor_cpu(self, fmt, q, samp, layout, dtype, shape, where, scale, offset, opt=False) -> Tuple[list, TaskExecInfo]:
         """rows to the host with pitched copies, the definition's pixels with numpy, then Pillow as `Run`"""
         import io
 
@@ -937,22 +951,25 @@ class PyNvJpegEncoder:
                 p = p.transpose(2, 0, 1)
             out = io.BytesIO()
             self._image(fmt, w, h, np.ascontiguousarray(p).reshape(-1)).save(
-                out, format="JPEG", quality=q, subsampling=list(NvJpegEncodeContext._SAMPLINGS).index(samp))
+                out, format="JPEG", quality=q, subsampling=list(NvJpegEncodeContext._SAMPLINGS).index(samp), optimize=opt)
             buffers.append(np.frombuffer(out.getvalue(), np.uint8).copy())
         return buffers, TaskExecInfo.SUCCESS
 
     # ---- hip backend ----------------------------------------------------------------------------------------------------
-    def _jpeg_params(self, quality: int, fmt: PixelFormat, samp: str):
-        key = (quality, int(fmt), samp)
+    def _jpeg_params(self, quality: int, fmt: PixelFormat, samp: str, opt: bool = False):
+        key = (quality, int(fmt), samp, opt)
         if key not in self._params:
             h_samp, v_samp = NvJpegEncodeContext._SAMPLINGS[samp]
-            self._params[key] = shim.jpeg_params_init_sampled(quality, int(fmt), h_samp, v_samp)
+            params = shim.jpeg_params_init_sampled(quality, int(fmt), h_samp, v_samp)
+            params.optimize = int(opt)
+            self._params[key] = params
         return self._params[key]
 
-    def _header(self, w: int, h: int, fmt: PixelFormat, quality: int, samp: str) -> np.ndarray:
-        key = (w, h, int(fmt), quality, samp)
+    def _header(self, w: int, h: int, fmt: PixelFormat, quality: int, samp: str, opt: bool = False) -> np.ndarray:
+        """what the host puts in front of the device's bytes; with optimize the DHT, DRI and SOS are among those"""
+        key = (w, h, int(fmt), quality, samp, opt)
         if key not in self._headers:
-            self._headers[key] = np.frombuffer(shim.jpeg_header(w, h, self._jpeg_params(quality, fmt, samp)), np.uint8)
+            self._headers[key] = np.frombuffer(shim.jpeg_header(w, h, self._jpeg_params(quality, fmt, samp, opt)), np.uint8)
         return self._headers[key]
 
     def _grow(self, name: str, need: int) -> int:
@@ -977,8 +994,8 @@ class PyNvJpegEncoder:
             if (fmt == F.YUV420 and (w | h) & 1) or (fmt == F.YUV422 and w & 1):
                 return [], TaskExecInfo.FAIL
         q = max(1, min(100, context.Compression()))
-        samp = context.Subsampling()
-        params = self._jpeg_params(q, fmt, samp)
+        samp, opt = context.Subsampling(), context.Optimize()
+        params = self._jpeg_params(q, fmt, samp, opt)
         groups = {}
         for i, surf in enumerate(surfaces):
             groups.setdefault((surf.Width, surf.Height), []).append(i)
@@ -992,7 +1009,7 @@ class PyNvJpegEncoder:
                 rc = shim.jpeg_encode_batch(d_src, n, w, h, int(fmt), params, ws, self._ws_bytes, out, cap, d_sizes, s)
                 if rc != 0:
                     return [], TaskExecInfo.FAIL
-                files = self._fetch(n, self._header(w, h, fmt, q, samp), out, cap, d_sizes)
+                files = self._fetch(n, self._header(w, h, fmt, q, samp, opt), out, cap, d_sizes)
             finally:
                 shim.mem_free(g, d_src)
             for k, i in enumerate(idx):

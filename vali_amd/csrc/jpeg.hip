@@ -17,6 +17,18 @@
 //                    worst-case slot; its length goes to the length array.
 //   k_jpeg_offsets   workgroup = one image: exclusive scan of (segment length + 2 bytes of RST) -> offsets, size.
 //   k_jpeg_assemble  workgroup = one segment: copy it and its RST marker to the image's output slot.
+//
+// optimize = 1 (per-image Huffman tables, libjpeg's jpeg_gen_optimal_table; tests/jpeg_optimize_model.py restates it):
+// a memset of the histograms and two more launches between k_jpeg_fdct and k_jpeg_huff,
+//   k_jpeg_hist      walks the coefficients as k_jpeg_huff does (wave = segment, lane = block, code_block in its
+//                    counting mode) and counts every symbol into an LDS histogram (ds_add_u32); the non-zero bins
+//                    of a workgroup then go to the image's four 256-bin histograms with global atomic adds.
+//   k_jpeg_tables    wave = one table of one image: the merges of the Huffman construction with the 257 counts in
+//                    registers (the two smallest by a wave reduction that carries the index), code lengths, the
+//                    16-bit limit of Annex K.2, HUFFVAL order and the Annex C codes -> the table k_jpeg_huff codes
+//                    with, and the table's bytes of the DHT segment.
+// k_jpeg_huff then codes with the image's tables, k_jpeg_offsets starts every image after its DHT + DRI + SOS, and
+// k_jpeg_assemble writes those in front of the entropy data.
 #include <cmath>
 #include <cstring>
 #include <type_traits>
@@ -101,6 +113,14 @@ constexpr int kBlockBytes = 208;
 constexpr int kSegBlocks = 64;
 constexpr int kHuffWords = kSegBlocks * kBlockBytes / 4 + 2;  // LDS bit buffer (+ padding word, + spill word)
 
+// optimize = 1: what the device writes in front of an image's entropy data, at most: DHT (marker, length, four tables
+// of class byte + BITS + at most 12 / 162 values: DC sizes 0..11, AC runs 0..15 x sizes 1..10 + ZRL + EOB), DRI, SOS
+constexpr int kDriSosBytes = 6 + 14;
+constexpr int kPrefixMax = 4 + 4 * 17 + 12 + 12 + 162 + 162 + kDriSosBytes;
+constexpr int kDhtSlot = 288;       // workspace bytes of one table's part of the DHT: 17 + 256 values, rounded up
+constexpr int kHistWaves = 4;       // waves of a k_jpeg_hist workgroup
+constexpr int kHistSegsPerWave = 4; // restart segments each of them counts (profiles/jpeg_optimize.md)
+
 // ---- geometry ------------------------------------------------------------------------------------------------------------
 struct JpegGeom {
   int H, V, bpm, R, bps;          // luma sampling, blocks per MCU, MCUs / blocks per segment
@@ -108,7 +128,14 @@ struct JpegGeom {
   int cw[3], ch[3], bw[3], bh[3]; // component size in samples / real blocks
   size_t slot;                    // bytes of one segment slot
   size_t coef_bytes, len_at, off_at, slot_at;  // workspace layout of a batch
+  int optimize;                                // per-image Huffman tables:
+  size_t prefix;                               //   worst case of DHT + DRI + SOS in front of the entropy data
+  size_t hist_at, codes_at, dht_at, dhtlen_at; //   histograms, code tables, DHT parts and their lengths
+  size_t ws_bytes;
 };
+
+// one image's output slot: every segment's worst case and its RST marker, after the worst case of the prefix
+inline size_t jpeg_capacity(const JpegGeom& g) { return g.prefix + (size_t)g.nseg * (g.slot + 2); }
 
 int jpeg_sampling(int format, int* H, int* V) {
   switch (format) {
@@ -159,6 +186,8 @@ int jpeg_geom(const char* fn, int n, int w, int h, const vali_jpeg_params* p, Jp
     return fail(VALI_ERR_INVALID_ARG, "%s: %d x %d: 4:2:0 needs an even width and height, 4:2:2 an even width", fn,
                 w, h);
   const int bpm = H * V + 2;
+  if (p->optimize != 0 && p->optimize != 1)
+    return fail(VALI_ERR_INVALID_ARG, "%s: optimize must be 0 or 1, not %d", fn, p->optimize);
   if (p->restart_interval < 1 || p->restart_interval * bpm > kSegBlocks)
     return fail(VALI_ERR_INVALID_ARG, "%s: restart interval %d outside 1..%d", fn, p->restart_interval,
                 kSegBlocks / bpm);
@@ -182,18 +211,26 @@ int jpeg_geom(const char* fn, int n, int w, int h, const vali_jpeg_params* p, Jp
     g->bh[c] = (g->ch[c] + 7) / 8;
   }
   g->slot = (size_t)2 * g->bps * kBlockBytes;
+  g->optimize = p->optimize;
+  g->prefix = p->optimize ? kPrefixMax : 0;
   // one image's output slot must stay addressable with 32-bit offsets
-  if ((size_t)g->nseg * (g->slot + 2) > 0xFFFFFFFFull)
+  if (jpeg_capacity(*g) > 0xFFFFFFFFull)
     return fail(VALI_ERR_INVALID_ARG, "%s: %d x %d is too large for one output slot", fn, w, h);
   const size_t nn = (size_t)(n > 0 ? n : 1);
   g->coef_bytes = align256(nn * g->nblocks * 128);
   g->len_at = g->coef_bytes;
   g->off_at = g->len_at + align256(nn * g->nseg * 4);
   g->slot_at = g->off_at + align256(nn * g->nseg * 4);
+  g->ws_bytes = g->slot_at + nn * g->nseg * g->slot;
+  if (g->optimize) {
+    g->hist_at = align256(g->ws_bytes);
+    g->codes_at = g->hist_at + nn * 4 * 256 * sizeof(u32);
+    g->dht_at = g->codes_at + nn * 4 * 256 * sizeof(u32);
+    g->dhtlen_at = g->dht_at + align256(nn * 4 * kDhtSlot);
+    g->ws_bytes = g->dhtlen_at + align256(nn * 4 * sizeof(u32));
+  }
   return VALI_OK;
 }
-
-size_t jpeg_ws_bytes(const JpegGeom& g, int n) { return g.slot_at + (size_t)(n > 0 ? n : 1) * g.nseg * g.slot; }
 
 // ---- k_jpeg_fdct -----------------------------------------------------------------------------------------------------
 struct FdctArgs {
@@ -699,15 +736,7 @@ __global__ void __launch_bounds__(256) k_jpeg_fdct(const FdctArgs a, const typen
     dst[i] = make_uint4(out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]);
 }
 
-// ---- k_jpeg_huff -----------------------------------------------------------------------------------------------------
-struct HuffArgs {
-  const int16_t* coef;
-  u32* seglen;  // image i, segment s: [i * nseg + s]
-  u8* slots;    // slot bytes per segment, same order
-  int nblocks, nseg, bpm, HV, bps;
-  u32 slot;
-};
-
+// ---- entropy coding: what k_jpeg_hist and k_jpeg_huff share -------------------------------------------------------------
 __device__ __forceinline__ int nbits(int v) { return v ? 32 - __clz(abs(v)) : 0; }
 
 // OR `len` (1..32) bits of `code` into the big-endian bit stream at bit `pos`: one or two ds_or_b32
@@ -729,13 +758,27 @@ __device__ __forceinline__ u32 wave_incl_scan(u32 v, int lane) {
   return v;
 }
 
-// EMIT = false: returns the bits of the block; true: writes them at bit `pos`
-template <bool EMIT>
-__device__ __forceinline__ u32 code_block(const int* z, int diff, const u32* dc, const u32* ac, u32* buf, u32 pos) {
+// What code_block does with the symbols of a block: BLOCK_BITS returns their bits, BLOCK_EMIT writes them at bit `pos`,
+// BLOCK_COUNT counts them (dc and ac are then the histograms of the block's tables, and nothing is read from them)
+enum BlockMode { BLOCK_BITS = 0, BLOCK_EMIT = 1, BLOCK_COUNT = 2 };
+
+// the table entry of `sym`; BLOCK_COUNT: one more of it, and no entry
+template <int MODE>
+__device__ __forceinline__ u32 symbol(u32* table, int sym) {
+  if (MODE == BLOCK_COUNT) {
+    atomicAdd(&table[sym], 1u);
+    return 0;
+  }
+  return table[sym];
+}
+
+template <int MODE>
+__device__ __forceinline__ u32 code_block(const int* z, int diff, u32* dc, u32* ac, u32* buf, u32 pos) {
+  constexpr bool EMIT = MODE == BLOCK_EMIT;
   u32 n = 0;
   {
     const int s = nbits(diff);
-    const u32 e = dc[s];
+    const u32 e = symbol<MODE>(dc, s);
     const int len = (int)(e & 0xFF) + s;
     if (EMIT)
       put_bits(buf, pos, ((e >> 8) << s) | ((u32)(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1)), len);
@@ -748,13 +791,13 @@ __device__ __forceinline__ u32 code_block(const int* z, int diff, const u32* dc,
     if (v) {
       int run = k - last - 1;
       for (; run > 15; run -= 16) {
-        const u32 e = ac[0xF0];
+        const u32 e = symbol<MODE>(ac, 0xF0);
         if (EMIT)
           put_bits(buf, pos + n, e >> 8, (int)(e & 0xFF));
         n += e & 0xFF;
       }
       const int s = nbits(v);
-      const u32 e = ac[(run << 4) | s];
+      const u32 e = symbol<MODE>(ac, (run << 4) | s);
       const int len = (int)(e & 0xFF) + s;
       if (EMIT)
         put_bits(buf, pos + n, ((e >> 8) << s) | ((u32)(v < 0 ? v - 1 : v) & ((1u << s) - 1)), len);
@@ -763,7 +806,7 @@ __device__ __forceinline__ u32 code_block(const int* z, int diff, const u32* dc,
     }
   }
   if (last < 63) {
-    const u32 e = ac[0];
+    const u32 e = symbol<MODE>(ac, 0);
     if (EMIT)
       put_bits(buf, pos + n, e >> 8, (int)(e & 0xFF));
     n += e & 0xFF;
@@ -771,21 +814,13 @@ __device__ __forceinline__ u32 code_block(const int* z, int diff, const u32* dc,
   return n;
 }
 
-__global__ void __launch_bounds__(64) k_jpeg_huff(const HuffArgs a) {
-  __shared__ u32 s_codes[4][256];
-  __shared__ u32 s_bits[kHuffWords];
-  const int lane = threadIdx.x;
-  const int seg = blockIdx.x;
-  const size_t img = blockIdx.y;
-  for (int i = lane; i < 4 * 256; i += 64)
-    s_codes[i >> 8][i & 255] = d_codes[i >> 8].e[i & 255];
-
-  const int base = seg * a.bps;
-  const int nb = min(a.bps, a.nblocks - base);
-  const bool act = lane < nb;
-  int z[64];
-  if (act) {
-    const uint4* src = (const uint4*)(a.coef + (img * a.nblocks + base + lane) * 64);
+// lane's block of a restart segment that starts at block `base` of image `img`: its 64 coefficients (zero when the
+// lane is past the segment's `nb` blocks) and its DC difference.  DC prediction comes from the previous block of the
+// same component and restarts with the segment.  Returns whether the block is a chroma block.
+__device__ __forceinline__ bool segment_block(const int16_t* coef, size_t img, int nblocks, int base, int nb, int bpm,
+                                              int HV, int lane, int* z, int* diff) {
+  if (lane < nb) {
+    const uint4* src = (const uint4*)(coef + (img * nblocks + base + lane) * 64);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const uint4 q = src[i];
@@ -801,17 +836,226 @@ __global__ void __launch_bounds__(64) k_jpeg_huff(const HuffArgs a) {
     for (int k = 0; k < 64; ++k)
       z[k] = 0;
   }
-  // DC prediction from the previous block of the same component; it restarts with the segment
-  const int p = lane % a.bpm;  // segments start on an MCU
-  const bool chroma = p >= a.HV;
-  const int prev = lane - (chroma ? a.bpm : p > 0 ? 1 : a.bpm - a.HV + 1);
+  const int p = lane % bpm;  // segments start on an MCU
+  const bool chroma = p >= HV;
+  const int prev = lane - (chroma ? bpm : p > 0 ? 1 : bpm - HV + 1);
   const int pdc = __shfl(z[0], prev < 0 ? lane : prev, 64);
-  const int diff = z[0] - (prev < 0 ? 0 : pdc);
+  *diff = z[0] - (prev < 0 ? 0 : pdc);
+  return chroma;
+}
+
+// ---- k_jpeg_hist -----------------------------------------------------------------------------------------------------
+struct HistArgs {
+  const int16_t* coef;
+  u32* hist;  // image i, table t (DHT order), symbol v: [(i * 4 + t) * 256 + v], zero before the launch
+  int nblocks, nseg, bpm, HV, bps;
+};
+
+// Counts fit 32 bits: an image's output slot is addressed with 32 bits (jpeg_geom), a segment slot takes 416 bytes a
+// block, and a block has at most 64 symbols of one table.
+__global__ void __launch_bounds__(64 * kHistWaves) k_jpeg_hist(const HistArgs a) {
+  __shared__ u32 s_hist[4][256];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const size_t img = blockIdx.y;
+  for (int i = tid; i < 4 * 256; i += 64 * kHistWaves)
+    s_hist[i >> 8][i & 255] = 0;
+  __syncthreads();
+  const int seg0 = (blockIdx.x * kHistWaves + wid) * kHistSegsPerWave;
+  const int seg1 = min(seg0 + kHistSegsPerWave, a.nseg);
+  for (int seg = seg0; seg < seg1; ++seg) {  // wave-uniform
+    const int base = seg * a.bps;
+    const int nb = min(a.bps, a.nblocks - base);
+    int z[64], diff;
+    const bool chroma = segment_block(a.coef, img, a.nblocks, base, nb, a.bpm, a.HV, lane, z, &diff);
+    if (lane < nb)
+      code_block<BLOCK_COUNT>(z, diff, s_hist[chroma ? 2 : 0], s_hist[chroma ? 3 : 1], nullptr, 0);
+  }
+  __syncthreads();
+  u32* g = a.hist + img * (4 * 256);
+  for (int i = tid; i < 4 * 256; i += 64 * kHistWaves) {
+    const u32 c = s_hist[i >> 8][i & 255];
+    if (c)
+      atomicAdd(&g[i], c);  // integer adds: the sum does not depend on their order
+  }
+}
+
+// ---- k_jpeg_tables ---------------------------------------------------------------------------------------------------
+struct TablesArgs {
+  const u32* hist;
+  u32* codes;   // symbol -> (code << 8) | length, 0 for a symbol the image does not have: what k_jpeg_huff reads
+  u8* dht;      // table (i * 4 + t): kDhtSlot bytes: class << 4 | id, BITS, HUFFVAL
+  u32* dhtlen;  // and how many of them: 17 + number of values
+};
+
+// libjpeg's jpeg_gen_optimal_table.  Symbol v lives in lane v % 64, register v / 64; symbol 256, in lane 0, is the
+// pseudo-symbol of count 1 that keeps the all-ones code free.  Each merge joins the two least frequent live entries:
+// c1 is the largest index among the minima, c2 the largest among the minima of the rest, which is the order of the key
+// (count << 9 | 511 - index); the sum stays at c1.  Every symbol remembers the entry its subtree is summed in, so that
+// a merge deepens all symbols of both subtrees at once: the code length is the depth in the merge tree.
+__global__ void __launch_bounds__(64) k_jpeg_tables(const TablesArgs a) {
+  constexpr int kMaxLen = 257;  // no code of 257 symbols is deeper than 256
+  __shared__ u32 s_len[kMaxLen + 1];          // codes of each length
+  __shared__ u32 s_first[18], s_start[18];    // Annex C: first code of a length, and its place in HUFFVAL
+  const int lane = threadIdx.x;
+  const int t = blockIdx.x;
+  const size_t tab = (size_t)blockIdx.y * 4 + t;
+  const u32* h = a.hist + tab * 256;
+  constexpr uint64_t kNone = ~0ull;
+
+  u32 f[5];
+  int grp[5], len[5];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    f[j] = j < 4 ? h[lane + 64 * j] : lane == 0 ? 1u : 0u;
+    grp[j] = lane + 64 * j;
+    len[j] = 0;
+  }
+  for (int i = lane; i <= kMaxLen; i += 64)
+    s_len[i] = 0;
+
+  for (;;) {
+    // the two smallest keys of the lane, then of the wave
+    uint64_t k1 = kNone, k2 = kNone;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      const uint64_t key = f[j] ? ((uint64_t)f[j] << 9) | (u32)(511 - (lane + 64 * j)) : kNone;
+      k2 = min(k2, max(k1, key));
+      k1 = min(k1, key);
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint64_t o1 = __shfl_xor(k1, d, 64), o2 = __shfl_xor(k2, d, 64);
+      k2 = min(max(k1, o1), min(k2, o2));
+      k1 = min(k1, o1);
+    }
+    if (k2 == kNone)  // one entry left: wave-uniform
+      break;
+    const int c1 = 511 - (int)(k1 & 511), c2 = 511 - (int)(k2 & 511);
+    const u32 v2 = (u32)(k2 >> 9);
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      const int idx = lane + 64 * j;
+      f[j] = idx == c1 ? f[j] + v2 : idx == c2 ? 0u : f[j];
+      if (grp[j] == c1 || grp[j] == c2) {
+        grp[j] = c1;
+        ++len[j];
+      }
+    }
+  }
+
+  // BITS before limiting (the pseudo-symbol included) and the place of every symbol in HUFFVAL: by length, then by
+  // value.  A length's symbols are found by ballots, register by register: that is their order by value.
+  int maxlen = 0;
+#pragma unroll
+  for (int j = 0; j < 5; ++j)
+    maxlen = max(maxlen, len[j]);
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1)
+    maxlen = max(maxlen, __shfl_xor(maxlen, d, 64));
+  const int pseudo = __shfl(len[4], 0, 64);
+  const uint64_t below = (1ull << lane) - 1;
+  int pos[4] = {0, 0, 0, 0};
+  u32 nvals = 0;
+  for (int l = 1; l <= maxlen; ++l) {
+    u32 n = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint64_t m = __ballot(len[j] == l);
+      if (len[j] == l)
+        pos[j] = (int)(nvals + n) + __popcll(m & below);
+      n += (u32)__popcll(m);
+    }
+    if (lane == 0)
+      s_len[l] = n + (pseudo == l ? 1u : 0u);
+    nvals += n;
+  }
+  __syncthreads();
+
+  if (lane == 0) {
+    // Annex K.2, figure K.3 (jchuff): no code longer than 16 bits
+    for (int i = maxlen; i > 16; --i) {
+      while (s_len[i] > 0) {
+        int j = i - 2;
+        while (j > 0 && s_len[j] == 0)
+          --j;
+        s_len[i] -= 2;
+        s_len[i - 1] += 1;
+        s_len[j + 1] += 2;
+        s_len[j] -= 1;
+      }
+    }
+    int i = min(maxlen, 16);
+    while (i > 0 && s_len[i] == 0)
+      --i;
+    if (i > 0)
+      s_len[i] -= 1;  // the pseudo-symbol's code
+    u32 code = 0, start = 0;
+    for (int l = 1; l <= 16; ++l) {
+      s_first[l] = code;
+      s_start[l] = start;
+      code = (code + s_len[l]) << 1;
+      start += s_len[l];
+    }
+    s_start[17] = start;
+  }
+  __syncthreads();
+
+  u8* dht = a.dht + tab * kDhtSlot;
+  u32* codes = a.codes + tab * 256;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    u32 e = 0;
+    if (len[j] > 0) {
+      const u32 p = (u32)pos[j];
+      for (int l = 1; l <= 16; ++l)
+        if (p >= s_start[l] && p < s_start[l + 1])
+          e = ((s_first[l] + p - s_start[l]) << 8) | (u32)l;
+      dht[17 + p] = (u8)(lane + 64 * j);
+    }
+    codes[lane + 64 * j] = e;
+  }
+  if (lane == 0) {
+    dht[0] = (u8)(((t & 1) << 4) | (t >> 1));  // DHT order: 0x00, 0x10, 0x01, 0x11
+    a.dhtlen[tab] = 17 + nvals;
+  } else if (lane <= 16) {
+    dht[lane] = (u8)s_len[lane];
+  }
+}
+
+// ---- k_jpeg_huff -----------------------------------------------------------------------------------------------------
+struct HuffArgs {
+  const int16_t* coef;
+  const u32* codes;  // image i, table t (DHT order): [(i * 4 + t) * 256]; null: Annex K
+  u32* seglen;  // image i, segment s: [i * nseg + s]
+  u8* slots;    // slot bytes per segment, same order
+  int nblocks, nseg, bpm, HV, bps;
+  u32 slot;
+};
+
+__global__ void __launch_bounds__(64) k_jpeg_huff(const HuffArgs a) {
+  __shared__ u32 s_codes[4][256];
+  __shared__ u32 s_bits[kHuffWords];
+  const int lane = threadIdx.x;
+  const int seg = blockIdx.x;
+  const size_t img = blockIdx.y;
+  if (a.codes) {  // the image's own tables (optimize = 1)
+    for (int i = lane; i < 4 * 256; i += 64)
+      s_codes[i >> 8][i & 255] = a.codes[img * (4 * 256) + i];
+  } else {
+    for (int i = lane; i < 4 * 256; i += 64)
+      s_codes[i >> 8][i & 255] = d_codes[i >> 8].e[i & 255];
+  }
+
+  const int base = seg * a.bps;
+  const int nb = min(a.bps, a.nblocks - base);
+  const bool act = lane < nb;
+  int z[64], diff;
+  const bool chroma = segment_block(a.coef, img, a.nblocks, base, nb, a.bpm, a.HV, lane, z, &diff);
   __syncthreads();  // code tables
 
-  const u32* dc = s_codes[chroma ? 2 : 0];
-  const u32* ac = s_codes[chroma ? 3 : 1];
-  const u32 mine = act ? code_block<false>(z, diff, dc, ac, nullptr, 0) : 0;
+  u32* dc = s_codes[chroma ? 2 : 0];
+  u32* ac = s_codes[chroma ? 3 : 1];
+  const u32 mine = act ? code_block<BLOCK_BITS>(z, diff, dc, ac, nullptr, 0) : 0;
   const u32 incl = wave_incl_scan(mine, lane);
   const u32 total = __shfl(incl, 63, 64);
   const int nwords = (int)((total + 7) >> 5) + 2;
@@ -819,7 +1063,7 @@ __global__ void __launch_bounds__(64) k_jpeg_huff(const HuffArgs a) {
     s_bits[i] = 0;
   __syncthreads();
   if (act)
-    code_block<true>(z, diff, dc, ac, s_bits, incl - mine);
+    code_block<BLOCK_EMIT>(z, diff, dc, ac, s_bits, incl - mine);
   const u32 pad = (8 - (total & 7)) & 7;
   if (lane == 0 && pad)
     put_bits(s_bits, total, (1u << pad) - 1, (int)pad);
@@ -856,11 +1100,18 @@ __global__ void __launch_bounds__(64) k_jpeg_huff(const HuffArgs a) {
 }
 
 // ---- k_jpeg_offsets ----------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_jpeg_offsets(const u32* seglen, u32* segoff, u32* sizes, int nseg) {
+// the bytes in front of an image's entropy data when its tables are its own: DHT (marker, length, four parts), DRI, SOS
+__device__ __forceinline__ u32 dht_bytes(const u32* dhtlen, size_t img) {
+  const uint4 l = *(const uint4*)(dhtlen + img * 4);
+  return 4 + l.x + l.y + l.z + l.w;
+}
+
+__global__ void __launch_bounds__(256) k_jpeg_offsets(const u32* seglen, u32* segoff, u32* sizes, int nseg,
+                                                      const u32* dhtlen) {
   __shared__ u32 s_wave[4];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const size_t img = blockIdx.x;
-  u32 carry = 0;
+  u32 carry = dhtlen ? dht_bytes(dhtlen, img) + kDriSosBytes : 0u;
   for (int s0 = 0; s0 < nseg; s0 += 256) {
     const int s = s0 + tid;
     const u32 v = s < nseg ? seglen[img * nseg + s] + 2u : 0u;  // + RST marker
@@ -892,6 +1143,9 @@ struct AsmArgs {
   size_t out_stride;
   int nseg;
   u32 slot;
+  const u8* dht;      // optimize = 1: the parts of the image's DHT and their lengths (k_jpeg_tables); else null
+  const u32* dhtlen;
+  int restart_interval;
 };
 
 __global__ void __launch_bounds__(256) k_jpeg_assemble(const AsmArgs a) {
@@ -912,6 +1166,26 @@ __global__ void __launch_bounds__(256) k_jpeg_assemble(const AsmArgs a) {
   if (threadIdx.x == 0 && seg + 1 < a.nseg) {
     dst[len] = 0xFF;
     dst[len + 1] = (u8)(0xD0 + (seg & 7));
+  }
+  if (a.dht && seg == 0) {  // the image's own DHT, then DRI and SOS as write_header lays them out
+    u8* o = a.out + img * a.out_stride;
+    u32 at = 4;
+    for (int t = 0; t < 4; ++t) {
+      const u32 n = a.dhtlen[img * 4 + t];
+      const u8* part = a.dht + (img * 4 + t) * kDhtSlot;
+      for (u32 i = threadIdx.x; i < n; i += 256)
+        o[at + i] = part[i];
+      at += n;
+    }
+    if (threadIdx.x == 0) {
+      o[0] = 0xFF, o[1] = 0xC4, o[2] = (u8)((at - 2) >> 8), o[3] = (u8)(at - 2);
+      o += at;
+      o[0] = 0xFF, o[1] = 0xDD, o[2] = 0, o[3] = 4;
+      o[4] = (u8)(a.restart_interval >> 8), o[5] = (u8)a.restart_interval;
+      o[6] = 0xFF, o[7] = 0xDA, o[8] = 0, o[9] = 12;
+      o[10] = 3, o[11] = 1, o[12] = 0x00, o[13] = 2, o[14] = 0x11, o[15] = 3, o[16] = 0x11;
+      o[17] = 0, o[18] = 63, o[19] = 0;
+    }
   }
 }
 
@@ -944,6 +1218,8 @@ size_t write_header(int w, int h, const vali_jpeg_params* p, u8* o) {
   put16(o + n, w), n += 2;
   const u8 comps[10] = {3, 1, (u8)((p->h_samp << 4) | p->v_samp), 0, 2, 0x11, 1, 3, 0x11, 1};
   memcpy(o + n, comps, 10), n += 10;
+  if (p->optimize)  // DHT, DRI and SOS come from the device, with the image's own tables
+    return n;
   int dht = 0;
   for (int t = 0; t < 4; ++t)
     dht += 17 + kHuff[t].nvals;
@@ -1014,6 +1290,8 @@ void launch_fdct_tensor(bool packed, bool yuv, int cs, dim3 grid, hipStream_t s,
 // what the surface and the tensor entry points share: everything but the arguments' checks and the first launch
 struct JpegLaunch {
   FdctArgs f;
+  HistArgs hi;   // optimize = 1 only, as tb
+  TablesArgs tb;
   HuffArgs hf;
   AsmArgs as;
   int cs;      // chroma sampling of an RGB source: 0 = 1x1, 1 = 2x1, 2 = 2x2
@@ -1024,9 +1302,9 @@ int jpeg_launch_prepare(const char* fn, int n, const JpegGeom& g, const vali_jpe
                         size_t ws_bytes, uint8_t* d_out, size_t out_stride, JpegLaunch* l) {
   if ((((uintptr_t)workspace) & 255) != 0)
     return fail(VALI_ERR_INVALID_ARG, "%s: workspace not 256-byte aligned", fn);
-  if (ws_bytes < jpeg_ws_bytes(g, n))
+  if (ws_bytes < g.ws_bytes)
     return fail(VALI_ERR_INVALID_ARG, "%s: workspace below vali_jpeg_workspace_size", fn);
-  if (out_stride < (size_t)g.nseg * (g.slot + 2))
+  if (out_stride < jpeg_capacity(g))
     return fail(VALI_ERR_INVALID_ARG, "%s: out_stride below vali_jpeg_stream_capacity", fn);
   u8* ws = (u8*)workspace;
   FdctArgs& f = l->f;
@@ -1038,10 +1316,16 @@ int jpeg_launch_prepare(const char* fn, int n, const JpegGeom& g, const vali_jpe
   for (int t = 0; t < 2; ++t)
     for (int k = 0; k < 64; ++k)
       reciprocal(params->qtable[t][k], &f.recip[t][k], &f.corr_shift[t][k]);
-  l->hf = {(const int16_t*)ws, (u32*)(ws + g.len_at), ws + g.slot_at, g.nblocks, g.nseg, g.bpm, g.H * g.V,
+  const bool opt = g.optimize != 0;
+  u32* codes = opt ? (u32*)(ws + g.codes_at) : nullptr;
+  u8* dht = opt ? ws + g.dht_at : nullptr;
+  u32* dhtlen = opt ? (u32*)(ws + g.dhtlen_at) : nullptr;
+  l->hi = {(const int16_t*)ws, opt ? (u32*)(ws + g.hist_at) : nullptr, g.nblocks, g.nseg, g.bpm, g.H * g.V, g.bps};
+  l->tb = {l->hi.hist, codes, dht, dhtlen};
+  l->hf = {(const int16_t*)ws, codes, (u32*)(ws + g.len_at), ws + g.slot_at, g.nblocks, g.nseg, g.bpm, g.H * g.V,
            g.bps, (u32)g.slot};
   l->as = {(const u32*)(ws + g.len_at), (const u32*)(ws + g.off_at), ws + g.slot_at, d_out, out_stride, g.nseg,
-           (u32)g.slot};
+           (u32)g.slot, dht, dhtlen, g.R};
   // a subsampled RGB source: workgroups of whole MCUs (fdct_subsampled)
   l->cs = jpeg_is_rgb(params->format) ? g.H * g.V / 2 : 0;
   const int per_wg = l->cs ? 256 / g.bpm * g.bpm : 256;
@@ -1049,15 +1333,27 @@ int jpeg_launch_prepare(const char* fn, int n, const JpegGeom& g, const vali_jpe
   return VALI_OK;
 }
 
-// k_jpeg_huff, k_jpeg_offsets, k_jpeg_assemble, after the source's k_jpeg_fdct
+// k_jpeg_huff, k_jpeg_offsets, k_jpeg_assemble, after the source's k_jpeg_fdct; with the image's own tables the
+// histograms are zeroed and k_jpeg_hist and k_jpeg_tables run first
 int jpeg_launch_rest(const char* fn, int n, const JpegLaunch& l, uint32_t* d_sizes, hipStream_t s) {
   // VALI_LAUNCH_CHECK's message under the entry point's name
   hipError_t e;
+  if (l.hi.hist) {
+    if ((e = hipMemsetAsync(l.hi.hist, 0, (size_t)n * 4 * 256 * sizeof(u32), s)) != hipSuccess)
+      return fail(VALI_ERR_RUNTIME, "%s: clearing the histograms failed: %s", fn, hipGetErrorString(e));
+    const int per_wg = kHistWaves * kHistSegsPerWave;
+    hipLaunchKernelGGL(k_jpeg_hist, dim3((l.hi.nseg + per_wg - 1) / per_wg, n), dim3(64 * kHistWaves), 0, s, l.hi);
+    if ((e = hipGetLastError()) != hipSuccess)
+      return fail(VALI_ERR_RUNTIME, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
+    hipLaunchKernelGGL(k_jpeg_tables, dim3(4, n), dim3(64), 0, s, l.tb);
+    if ((e = hipGetLastError()) != hipSuccess)
+      return fail(VALI_ERR_RUNTIME, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
+  }
   hipLaunchKernelGGL(k_jpeg_huff, dim3(l.hf.nseg, n), dim3(64), 0, s, l.hf);
   if ((e = hipGetLastError()) != hipSuccess)
     return fail(VALI_ERR_RUNTIME, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
   hipLaunchKernelGGL(k_jpeg_offsets, dim3(n), dim3(256), 0, s, l.as.seglen, (u32*)l.as.segoff, (u32*)d_sizes,
-                     l.hf.nseg);
+                     l.hf.nseg, l.as.dhtlen);
   if ((e = hipGetLastError()) != hipSuccess)
     return fail(VALI_ERR_RUNTIME, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
   hipLaunchKernelGGL(k_jpeg_assemble, dim3(l.hf.nseg, n), dim3(256), 0, s, l.as);
@@ -1127,7 +1423,7 @@ int vali_jpeg_workspace_size(int n, int width, int height, const vali_jpeg_param
   const int rc = jpeg_geom(__func__, n, width, height, params, &g);
   if (rc != VALI_OK)
     return rc;
-  *bytes = jpeg_ws_bytes(g, n);
+  *bytes = g.ws_bytes;
   return VALI_OK;
 }
 
@@ -1137,7 +1433,7 @@ int vali_jpeg_stream_capacity(int width, int height, const vali_jpeg_params* par
   const int rc = jpeg_geom(__func__, 1, width, height, params, &g);
   if (rc != VALI_OK)
     return rc;
-  *bytes = (size_t)g.nseg * (g.slot + 2);
+  *bytes = jpeg_capacity(g);
   return VALI_OK;
 }
 

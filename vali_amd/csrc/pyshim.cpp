@@ -573,6 +573,9 @@ PYBIND11_MODULE(_vali_shim, m) {
       .def_property_readonly("v_samp", [](const JpegParams& j) { return j.p.v_samp; })
       .def_property("restart_interval", [](const JpegParams& j) { return j.p.restart_interval; },
                     [](JpegParams& j, int r) { j.p.restart_interval = r; })
+      // 0 or 1; vali_jpeg_* validate it, not the shim
+      .def_property("optimize", [](const JpegParams& j) { return j.p.optimize; },
+                    [](JpegParams& j, int v) { j.p.optimize = v; })
       .def_property("qtable", [](const JpegParams& j) {
         std::vector<std::vector<int>> t(2, std::vector<int>(64));
         for (int i = 0; i < 2; ++i)
