@@ -503,6 +503,65 @@ VALI_API int vali_jpeg_encode_tensor(const vali_tensor_src* src, const float sca
                                      const vali_jpeg_params* params, void* workspace, size_t ws_bytes,
                                      uint8_t* d_out, size_t out_stride, uint32_t* d_sizes, vali_stream_t stream);
 
+/*
+ * Rectangles of surfaces of ANY sizes as files, in one fixed set of launches.  Item i is rectangle rois[i] of the
+ * surface d_src[i] (the same surface may stand behind any number of items); its file is byte for byte the file of
+ * vali_jpeg_encode_batch for a surface that holds a copy of the rectangle: the component's last column and row are
+ * replicated at the RECTANGLE's edge, and no sample outside it is read.  Rules (vali_jpeg_plan_rois checks them, with
+ * the item and the rule in vali_last_error()): the rectangle lies inside its surface and is 1..65535 on a side;
+ * YUV420 sources need even x, y, width, height, YUV422 even x, width; RGB, BGR, RGB_PLANAR and YUV444 take any
+ * integers at every sampling.  The rectangles are host data: an image's header and its place in the output depend on
+ * its size.
+ *
+ * vali_jpeg_plan_rois (host only) turns the rectangles into one record per item with everything the kernels look up:
+ * its geometry, where its coefficients, segments and output start, and its first workgroup in each launch (the grids
+ * are one-dimensional over the sum of the items' workgroups, each item padded to whole workgroups; a workgroup finds
+ * its item by a binary search of these fields).  The caller copies the records to the device and passes both copies
+ * to vali_jpeg_encode_rois, as vali_jpeg_decode_batch takes infos and d_infos.
+ */
+typedef struct vali_jpeg_roi {
+  int32_t x, y, width, height; /* pixels of the surface's full-resolution grid */
+} vali_jpeg_roi;               /* 16 bytes */
+
+typedef struct vali_jpeg_item {
+  int32_t x, y, width, height;        /* the rectangle                                                           */
+  int32_t mcux, mcuy;                 /* MCUs per row / per column                                               */
+  int32_t nblocks, nseg;              /* blocks (dummy blocks of partial MCUs included) and restart segments     */
+  int32_t cw[3], ch[3], bw[3], bh[3]; /* component size in samples / real blocks                                 */
+  uint32_t wg_fdct;                   /* first workgroup in k_jpeg_fdct: 256 blocks each, or whole MCUs          */
+  uint32_t wg_hist;                   /* ... in k_jpeg_hist: 16 segments each                                    */
+  uint32_t wg_seg;                    /* ... in k_jpeg_huff and k_jpeg_assemble: one segment each (= seg_first)  */
+  uint32_t check;                     /* ties the record to the params it was planned for                       */
+  uint64_t block_first;               /* coefficients: workspace + block_first * 128                             */
+  uint64_t seg_first;                 /* segment lengths and offsets: entry seg_first; slots: seg_first * slot   */
+  uint64_t out_offset;                /* the image's bytes: d_out + out_offset (vali_jpeg_stream_capacity apart) */
+  uint64_t reserved;
+} vali_jpeg_item;                     /* 128 bytes */
+
+/* host only: checks n (0..65535) rectangles against their surfaces' sizes src_w[i] x src_h[i] and params, fills
+ * items[0..n), *ws_bytes (the workspace of vali_jpeg_encode_rois) and *out_bytes (one output buffer that holds every
+ * image's vali_jpeg_stream_capacity back to back).  One image's slot stays addressable with 32 bits; the offsets
+ * between images are 64-bit.  n = 0: both sizes are 0.  VALI_ERR_INVALID_ARG for a broken rule, for what
+ * vali_jpeg_workspace_size refuses in params and sizes, and for a batch whose flattened grids would pass 2^31 - 1
+ * workgroups */
+VALI_API int vali_jpeg_plan_rois(const vali_jpeg_roi* rois, const int32_t* src_w, const int32_t* src_h, int n,
+                                 const vali_jpeg_params* params, vali_jpeg_item* items, size_t* ws_bytes,
+                                 size_t* out_bytes);
+/*
+ * d_src: DEVICE array of n descriptors of params->format, item i's surface at [i].  items / d_items: the records of
+ * vali_jpeg_plan_rois for these params, in host and in device memory.  Image i's bytes (entropy data, preceded with
+ * optimize = 1 by its DHT, DRI and SOS) go to d_out + items[i].out_offset, their length to d_sizes[i]; the header is
+ * vali_jpeg_header(items[i].width, items[i].height, params).  workspace: device memory, 256-byte aligned, ws_bytes >=
+ * the plan's; out_bytes >= the plan's.  Four launches whatever n and the sizes (optimize = 1: a memset and six);
+ * nothing is allocated and nothing synchronises, so the call can be captured into a graph.  VALI_ERR_INVALID_ARG,
+ * before any device is touched, for null arguments, a short or misaligned workspace, a short output and items that
+ * vali_jpeg_plan_rois did not make for these params.
+ */
+VALI_API int vali_jpeg_encode_rois(const vali_surface* d_src, const vali_jpeg_item* items,
+                                   const vali_jpeg_item* d_items, int n, const vali_jpeg_params* params,
+                                   void* workspace, size_t ws_bytes, uint8_t* d_out, size_t out_bytes,
+                                   uint32_t* d_sizes, vali_stream_t stream);
+
 /* ---- JPEG: baseline sequential decoder ----------------------------------------------------
  *
  * Definition: libjpeg-turbo's default decompression, bit for bit (tests/jpeg_decode_model.py restates it):

@@ -18,7 +18,8 @@ offline.  What IS provided so pipelines written against python_vali keep running
                  ndarray -> upload -> kernel -> download.  It is NOT a CPU code path.
 * PyNvJpegEncoder -- the reference's JPEG encoder API: backend="cpu" (default) downloads and compresses with Pillow;
                  backend="hip" encodes baseline JPEG on the GPU (vali_jpeg_encode_batch).  RunTensor encodes a
-                 (N, 3, H, W) float32 / float16 / bfloat16 / uint8 tensor as it is (vali_jpeg_encode_tensor).
+                 (N, 3, H, W) float32 / float16 / bfloat16 / uint8 tensor as it is (vali_jpeg_encode_tensor).  RunRoi
+                 encodes rectangles of surfaces of any sizes in one set of launches (vali_jpeg_encode_rois).
 * PyNvJpegDecoder -- baseline JPEG decoded on the GPU into Surfaces (vali_jpeg_decode_batch): RGB / BGR / RGB_PLANAR / Y
                  from any supported file, YUV444 / YUV422 / YUV420 / NV12 from files of that sampling.
 * PyNvEncoder  -- the reference's video encoder API (src/python_vali/src/PyNvEncoder.cpp:388-630) as "download + CPU
@@ -28,6 +29,7 @@ offline.  What IS provided so pipelines written against python_vali keep running
 """
 from __future__ import annotations
 
+import operator
 import os
 from typing import Optional, Tuple
 
@@ -772,6 +774,28 @@ class NvJpegEncodeContext:
         return self._optimize
 
 
+# vali_jpeg_item (include/vali_hip.h) as numpy reads the records of shim.jpeg_plan_rois
+_JPEG_ITEM = np.dtype([("x", "<i4"), ("y", "<i4"), ("width", "<i4"), ("height", "<i4"), ("mcux", "<i4"), ("mcuy", "<i4"),
+                       ("nblocks", "<i4"), ("nseg", "<i4"), ("cw", "<i4", 3), ("ch", "<i4", 3), ("bw", "<i4", 3),
+                       ("bh", "<i4", 3), ("wg_fdct", "<u4"), ("wg_hist", "<u4"), ("wg_seg", "<u4"), ("check", "<u4"),
+                       ("block_first", "<u8"), ("seg_first", "<u8"), ("out_offset", "<u8"), ("reserved", "<u8")])
+
+
+def _crop_host(fmt: PixelFormat, sw: int, sh: int, host: np.ndarray, x: int, y: int, w: int, h: int) -> np.ndarray:
+    """rectangle (x, y, w, h) of a downloaded sw x sh surface, in the host layout of a w x h surface of `fmt`"""
+    if fmt in (F.RGB, F.BGR):
+        return np.ascontiguousarray(host.reshape(sh, sw, 3)[y:y + h, x:x + w]).reshape(-1)
+    if fmt == F.RGB_PLANAR:
+        return np.ascontiguousarray(host.reshape(3, sh, sw)[:, y:y + h, x:x + w]).reshape(-1)
+    dx, dy = (1, 1) if fmt == F.YUV444 else (2, 1) if fmt == F.YUV422 else (2, 2)
+    cw, ch = sw // dx, sh // dy
+    planes = [host[:sw * sh].reshape(sh, sw)[y:y + h, x:x + w]]
+    for c in range(2):
+        plane = host[sw * sh + c * cw * ch: sw * sh + (c + 1) * cw * ch].reshape(ch, cw)
+        planes.append(plane[y // dy:(y + h) // dy, x // dx:(x + w) // dx])
+    return np.concatenate([p.reshape(-1) for p in planes])
+
+
 _TENSOR_ESIZE = {"float32": 4, "float16": 2, "bfloat16": 2, "uint8": 1}
 
 
@@ -822,7 +846,9 @@ class PyNvJpegEncoder:
       libjpeg's); they differ in bytes only by the restart markers the GPU coder needs (DRI).
       `Context(..., optimize=True)`: every file is coded with Huffman tables built on the GPU from its own symbol
       counts (libjpeg's jpeg_gen_optimal_table); its DHT then comes from the device with the entropy data.  The "cpu"
-      backend passes optimize=True to Pillow."""
+      backend passes optimize=True to Pillow.
+    `RunRoi(context, surfaces, rects)`: one file per rectangle of surfaces of any sizes, in one set of launches
+    (vali_jpeg_encode_rois); each file is the file of `Run` on a copy of the rectangle."""
 
     BACKENDS = ("cpu", "hip")
 
@@ -840,8 +866,8 @@ class PyNvJpegEncoder:
         self._stream = HipResMgr.Instance().GetStream(self._gpu_id)
         self._down = PySurfaceDownloader(self._gpu_id, self._stream)
         # hip backend: device buffers owned by the encoder, grown on demand; parameters and headers cached
-        self._ws = self._out = self._sizes = None
-        self._ws_bytes = self._out_bytes = self._sizes_bytes = 0
+        self._ws = self._out = self._sizes = self._roi = None
+        self._ws_bytes = self._out_bytes = self._sizes_bytes = self._roi_bytes = 0
         self._params = {}
         self._headers = {}
 
@@ -889,6 +915,85 @@ class PyNvJpegEncoder:
             out = io.BytesIO()
             q = max(1, min(100, context.Compression()))
             self._image(surf.Format, surf.Width, surf.Height, host).save(
+                out, format="JPEG", quality=q, subsampling=list(NvJpegEncodeContext._SAMPLINGS).index(context.Subsampling()),
+                optimize=context.Optimize())
+            buffers.append(np.frombuffer(out.getvalue(), np.uint8).copy())
+        return buffers, TaskExecInfo.SUCCESS
+
+    def RunRoi(self, context: NvJpegEncodeContext, surfaces, rects=None) -> Tuple[list, TaskExecInfo]:
+        """One file per rectangle, out of surfaces of any sizes: file i is byte for byte what `Run(context, [s])`
+        returns for a surface `s` that holds a copy of rectangle i of `surfaces[i]` -- the crop is never made.  The
+        same surface may appear any number of times.  All files or none, as `Run`.
+        `rects`: None, or one entry per surface: None (the whole surface) or (x, y, w, h) in pixels, inside the
+        surface, 1..65535 on a side.  YUV420 surfaces need even x, y, w, h and YUV422 even x, w; RGB, BGR, RGB_PLANAR
+        and YUV444 take any integers at every `subsampling`.  A wrong rectangle is a ValueError that names the item
+        and the rule, raised before anything is launched; a None or empty surface, or one of another format, gives
+        ([], FAIL).
+        "hip": one plan on the host, one upload, one set of launches whatever the number and the sizes of the
+        rectangles (vali_jpeg_encode_rois), two synchronisations.  "cpu": every surface is downloaded once and the
+        crops are made on the host.
+        The rectangles are host data: a file's header and its place in the output depend on its size, so boxes that
+        live in GPU memory have to come to the host first."""
+        surfaces = list(surfaces)
+        n = len(surfaces)
+        if rects is None:
+            rects = [None] * n
+        rects = list(rects)
+        if len(rects) != n:
+            raise ValueError(f"RunRoi: {len(rects)} rectangles for {n} surfaces")
+        boxes = []
+        for i, r in enumerate(rects):               # what can be said without the surface
+            if r is None:
+                boxes.append(None)
+                continue
+            try:
+                box = tuple(operator.index(v) for v in r)
+            except TypeError as exc:
+                raise ValueError(f"RunRoi: item {i}: a rectangle is None or four integers (x, y, w, h), not {r!r}") from exc
+            if len(box) != 4:
+                raise ValueError(f"RunRoi: item {i}: a rectangle is None or four integers (x, y, w, h), not {r!r}")
+            x, y, w, h = box
+            if not (1 <= w <= 65535 and 1 <= h <= 65535):
+                raise ValueError(f"RunRoi: item {i}: rectangle of {w} x {h}: a side must be 1..65535")
+            if x < 0 or y < 0:
+                raise ValueError(f"RunRoi: item {i}: rectangle {box} starts outside its surface")
+            boxes.append(box)
+        fmt = context.Format()
+        for surf in surfaces:                       # all or nothing, as Run
+            if surf is None or surf.IsEmpty or surf.Format != fmt:
+                return [], TaskExecInfo.FAIL
+            if (fmt == F.YUV420 and (surf.Width | surf.Height) & 1) or (fmt == F.YUV422 and surf.Width & 1):
+                return [], TaskExecInfo.FAIL
+        for i, surf in enumerate(surfaces):
+            if boxes[i] is None:
+                boxes[i] = (0, 0, surf.Width, surf.Height)
+            x, y, w, h = boxes[i]
+            if not (1 <= w <= 65535 and 1 <= h <= 65535):
+                raise ValueError(f"RunRoi: item {i}: rectangle of {w} x {h}: a side must be 1..65535")
+            if x + w > surf.Width or y + h > surf.Height:
+                raise ValueError(f"RunRoi: item {i}: rectangle {boxes[i]} does not lie inside its "
+                                 f"{surf.Width} x {surf.Height} surface")
+            if (fmt == F.YUV420 and (x | y | w | h) & 1) or (fmt == F.YUV422 and (x | w) & 1):
+                raise ValueError(f"RunRoi: item {i}: rectangle {boxes[i]}: YUV420 needs even x, y, w and h, "
+                                 "YUV422 an even x and w")
+        if n == 0:
+            return [], TaskExecInfo.SUCCESS
+        if self._backend == "hip":
+            return self._run_roi_hip(context, surfaces, boxes)
+        import io
+
+        q = max(1, min(100, context.Compression()))
+        hosts, buffers = {}, []
+        for surf, (x, y, w, h) in zip(surfaces, boxes):
+            host = hosts.get(id(surf))
+            if host is None:                        # every surface comes down once
+                host = np.zeros(surf.HostSize, np.uint8)
+                ok, _ = self._down.Run(surf, host)
+                if not ok:
+                    return [], TaskExecInfo.FAIL
+                hosts[id(surf)] = host
+            out = io.BytesIO()
+            self._image(fmt, w, h, _crop_host(fmt, surf.Width, surf.Height, host, x, y, w, h)).save(
                 out, format="JPEG", quality=q, subsampling=list(NvJpegEncodeContext._SAMPLINGS).index(context.Subsampling()),
                 optimize=context.Optimize())
             buffers.append(np.frombuffer(out.getvalue(), np.uint8).copy())
@@ -1016,26 +1121,61 @@ class PyNvJpegEncoder:
                 buffers[i] = files[k]
         return buffers, TaskExecInfo.SUCCESS
 
+    def _run_roi_hip(self, context: NvJpegEncodeContext, surfaces: list, boxes: list) -> Tuple[list, TaskExecInfo]:
+        n = len(surfaces)
+        fmt, q = context.Format(), max(1, min(100, context.Compression()))
+        samp, opt = context.Subsampling(), context.Optimize()
+        params = self._jpeg_params(q, fmt, samp, opt)
+        rois = np.array(boxes, np.int32).reshape(n, 4)
+        src_w = np.array([s.Width for s in surfaces], np.int32)
+        src_h = np.array([s.Height for s in surfaces], np.int32)
+        items, ws_bytes, out_bytes = shim.jpeg_plan_rois(rois, src_w, src_h, params)
+        # [records | descriptors]: one host-to-device copy into a buffer the encoder keeps
+        isz, dsz = shim.JPEG_ITEM_SIZE, shim.SURFACE_DESC_SIZE
+        blob = np.empty(n * (isz + dsz), np.uint8)
+        blob[:n * isz] = np.frombuffer(items, np.uint8)
+        descs = {}
+        for k, surf in enumerate(surfaces):
+            d = descs.get(id(surf))
+            if d is None:
+                d = descs[id(surf)] = np.frombuffer(surf.desc().tobytes(), np.uint8)
+            blob[n * isz + k * dsz:n * isz + (k + 1) * dsz] = d
+        ws, out, d_sizes = self._grow("ws", ws_bytes), self._grow("out", out_bytes), self._grow("sizes", 4 * n)
+        d_blob = self._grow("roi", blob.size)
+        g, s = self._gpu_id, self._stream
+        shim.memcpy2d_async(g, d_blob, blob.size, blob.ctypes.data, blob.size, blob.size, 1, 0, s)
+        rc = shim.jpeg_encode_rois(d_blob + n * isz, items, d_blob, n, params, ws, self._ws_bytes, out, self._out_bytes,
+                                   d_sizes, s)
+        if rc != 0:
+            shim.stream_sync(g, s)                  # the upload reads blob
+            return [], TaskExecInfo.FAIL
+        rec = np.frombuffer(items, _JPEG_ITEM)
+        hdrs = [self._header(int(w), int(h), fmt, q, samp, opt) for w, h in zip(rec["width"], rec["height"])]
+        return self._fetch(n, hdrs, out, [int(o) for o in rec["out_offset"]], d_sizes), TaskExecInfo.SUCCESS
+
     def _buffers(self, n: int, w: int, h: int, params):
         """(workspace, output, sizes, output stride) of a launch over n images of w x h: the encoder's own buffers"""
         ws_bytes = shim.jpeg_workspace_size(n, w, h, params)
         cap = shim.jpeg_stream_capacity(w, h, params)
         return self._grow("ws", ws_bytes), self._grow("out", n * cap), self._grow("sizes", 4 * n), cap
 
-    def _fetch(self, n: int, hdr: np.ndarray, out: int, cap: int, d_sizes: int) -> list:
+    def _fetch(self, n: int, hdr, out: int, cap, d_sizes: int) -> list:
         """the n files of a launch: the sizes, then one exact D2H copy per image, between its header and EOI;
-        synchronises the encoder's stream twice"""
+        synchronises the encoder's stream twice.  hdr / cap: one header and the images' distance in `out`, or a
+        header and an offset per image"""
         g, s = self._gpu_id, self._stream
+        hdrs = hdr if isinstance(hdr, list) else [hdr] * n
+        offsets = cap if isinstance(cap, list) else [k * cap for k in range(n)]
         sizes = np.zeros(n, np.uint32)
         shim.memcpy2d_async(g, sizes.ctypes.data, 4 * n, d_sizes, 4 * n, 4 * n, 1, 1, s)
         shim.stream_sync(g, s)
         files = []
         for k in range(n):
-            size = int(sizes[k])
+            size, hdr = int(sizes[k]), hdrs[k]
             buf = np.empty(hdr.size + size + 2, np.uint8)
             buf[:hdr.size] = hdr
             buf[-2:] = (0xFF, 0xD9)
-            shim.memcpy2d_async(g, buf.ctypes.data + hdr.size, size, out + k * cap, size, size, 1, 1, s)
+            shim.memcpy2d_async(g, buf.ctypes.data + hdr.size, size, out + offsets[k], size, size, 1, 1, s)
             files.append(buf)
         shim.stream_sync(g, s)
         return files

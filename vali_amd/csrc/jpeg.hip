@@ -29,6 +29,14 @@
 //                    with, and the table's bytes of the DHT segment.
 // k_jpeg_huff then codes with the image's tables, k_jpeg_offsets starts every image after its DHT + DRI + SOS, and
 // k_jpeg_assemble writes those in front of the entropy data.
+//
+// Regions of surfaces of any sizes (vali_jpeg_encode_rois): the same launches, each as a one-dimensional grid over the
+// sum of the images' workgroups.  vali_jpeg_plan_rois lays the images out on the host, one vali_jpeg_item each: its
+// geometry, where its coefficients, segments and output start, and its first workgroup in every launch.  A workgroup
+// of k_jpeg_fdct_roi / _hist_roi / _huff_roi / _assemble_roi finds its item by a binary search of that field with
+// blockIdx.x, which is scalar work, and then runs the body it shares with the uniform kernel; k_jpeg_offsets_roi and
+// k_jpeg_tables are per image anyway.  The loader starts at the rectangle's origin and counts, and replicates, rows and
+// columns in the rectangle (SurfIn::item_at).
 #include <cmath>
 #include <cstring>
 #include <type_traits>
@@ -169,6 +177,39 @@ bool jpeg_sampling_ok(int format, int h_samp, int v_samp) {
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// what of g depends on the image's size; H, V, bpm and R are set
+void jpeg_image_geom(int w, int h, JpegGeom* g) {
+  const int H = g->H, V = g->V;
+  g->mcux = (w + 8 * H - 1) / (8 * H);
+  g->mcuy = (h + 8 * V - 1) / (8 * V);
+  const long long nmcu = (long long)g->mcux * g->mcuy;
+  g->nblocks = (int)(nmcu * g->bpm);
+  g->nseg = (int)((nmcu + g->R - 1) / g->R);
+  for (int c = 0; c < 3; ++c) {
+    const int hs = c ? 1 : H, vs = c ? 1 : V;
+    g->cw[c] = (w * hs + H - 1) / H;
+    g->ch[c] = (h * vs + V - 1) / V;
+    g->bw[c] = (g->cw[c] + 7) / 8;
+    g->bh[c] = (g->ch[c] + 7) / 8;
+  }
+}
+
+// the workspace of n images that hold `blocks` blocks and `segs` segments together
+void jpeg_layout(size_t n, size_t blocks, size_t segs, JpegGeom* g) {
+  g->coef_bytes = align256(blocks * 128);
+  g->len_at = g->coef_bytes;
+  g->off_at = g->len_at + align256(segs * 4);
+  g->slot_at = g->off_at + align256(segs * 4);
+  g->ws_bytes = g->slot_at + segs * g->slot;
+  if (g->optimize) {
+    g->hist_at = align256(g->ws_bytes);
+    g->codes_at = g->hist_at + n * 4 * 256 * sizeof(u32);
+    g->dht_at = g->codes_at + n * 4 * 256 * sizeof(u32);
+    g->dhtlen_at = g->dht_at + align256(n * 4 * kDhtSlot);
+    g->ws_bytes = g->dhtlen_at + align256(n * 4 * sizeof(u32));
+  }
+}
+
 // checks params and sizes; fills g (workspace layout for a batch of n)
 int jpeg_geom(const char* fn, int n, int w, int h, const vali_jpeg_params* p, JpegGeom* g) {
   if (!p)
@@ -198,18 +239,7 @@ int jpeg_geom(const char* fn, int n, int w, int h, const vali_jpeg_params* p, Jp
   if (n < 0 || n > 65535)
     return fail(VALI_ERR_INVALID_ARG, "%s: batch size out of range (0..65535)", fn);
   g->H = H, g->V = V, g->bpm = bpm, g->R = p->restart_interval, g->bps = g->R * bpm;
-  g->mcux = (w + 8 * H - 1) / (8 * H);
-  g->mcuy = (h + 8 * V - 1) / (8 * V);
-  const long long nmcu = (long long)g->mcux * g->mcuy;
-  g->nblocks = (int)(nmcu * bpm);
-  g->nseg = (int)((nmcu + g->R - 1) / g->R);
-  for (int c = 0; c < 3; ++c) {
-    const int hs = c ? 1 : H, vs = c ? 1 : V;
-    g->cw[c] = (w * hs + H - 1) / H;
-    g->ch[c] = (h * vs + V - 1) / V;
-    g->bw[c] = (g->cw[c] + 7) / 8;
-    g->bh[c] = (g->ch[c] + 7) / 8;
-  }
+  jpeg_image_geom(w, h, g);
   g->slot = (size_t)2 * g->bps * kBlockBytes;
   g->optimize = p->optimize;
   g->prefix = p->optimize ? kPrefixMax : 0;
@@ -217,19 +247,48 @@ int jpeg_geom(const char* fn, int n, int w, int h, const vali_jpeg_params* p, Jp
   if (jpeg_capacity(*g) > 0xFFFFFFFFull)
     return fail(VALI_ERR_INVALID_ARG, "%s: %d x %d is too large for one output slot", fn, w, h);
   const size_t nn = (size_t)(n > 0 ? n : 1);
-  g->coef_bytes = align256(nn * g->nblocks * 128);
-  g->len_at = g->coef_bytes;
-  g->off_at = g->len_at + align256(nn * g->nseg * 4);
-  g->slot_at = g->off_at + align256(nn * g->nseg * 4);
-  g->ws_bytes = g->slot_at + nn * g->nseg * g->slot;
-  if (g->optimize) {
-    g->hist_at = align256(g->ws_bytes);
-    g->codes_at = g->hist_at + nn * 4 * 256 * sizeof(u32);
-    g->dht_at = g->codes_at + nn * 4 * 256 * sizeof(u32);
-    g->dhtlen_at = g->dht_at + align256(nn * 4 * kDhtSlot);
-    g->ws_bytes = g->dhtlen_at + align256(nn * 4 * sizeof(u32));
-  }
+  jpeg_layout(nn, nn * g->nblocks, nn * g->nseg, g);
   return VALI_OK;
+}
+
+// ---- regions of surfaces of any sizes: the plan -----------------------------------------------------------------------
+// what the items before item i add up to: where item i starts in every area and every flattened grid
+struct RoiTotals {
+  uint64_t blocks, segs, out, wg_fdct, wg_hist;
+};
+
+// blocks of one k_jpeg_fdct workgroup: 256, or the whole MCUs of a subsampled RGB source
+int fdct_blocks_per_wg(const vali_jpeg_params* p, const JpegGeom& g) {
+  return jpeg_is_rgb(p->format) && g.H * g.V > 1 ? 256 / g.bpm * g.bpm : 256;
+}
+
+// what of params a plan depends on, beyond what the records themselves hold
+u32 roi_check(const vali_jpeg_params* p) {
+  return 0x4A524F49u ^ (u32)p->format ^ (u32)p->h_samp << 8 ^ (u32)p->v_samp << 12 ^ (u32)p->optimize << 16 ^
+         (u32)p->restart_interval << 20;
+}
+
+// The record of rectangle r (1..65535 on a side), the next after the items that add up to *t; g holds the params'
+// part.  False when its output slot or a flattened grid would pass what 32 bits address.
+bool roi_item(const vali_jpeg_roi& r, const vali_jpeg_params* p, JpegGeom* g, RoiTotals* t, vali_jpeg_item* it) {
+  jpeg_image_geom(r.width, r.height, g);
+  if (jpeg_capacity(*g) > 0xFFFFFFFFull)
+    return false;
+  memset(it, 0, sizeof(*it));
+  it->x = r.x, it->y = r.y, it->width = r.width, it->height = r.height;
+  it->mcux = g->mcux, it->mcuy = g->mcuy, it->nblocks = g->nblocks, it->nseg = g->nseg;
+  for (int c = 0; c < 3; ++c)
+    it->cw[c] = g->cw[c], it->ch[c] = g->ch[c], it->bw[c] = g->bw[c], it->bh[c] = g->bh[c];
+  it->wg_fdct = (u32)t->wg_fdct, it->wg_hist = (u32)t->wg_hist, it->wg_seg = (u32)t->segs;
+  it->check = roi_check(p);
+  it->block_first = t->blocks, it->seg_first = t->segs, it->out_offset = t->out;
+  const int per_wg = fdct_blocks_per_wg(p, *g), per_hist = kHistWaves * kHistSegsPerWave;
+  t->blocks += (uint64_t)g->nblocks;
+  t->segs += (uint64_t)g->nseg;
+  t->out += jpeg_capacity(*g);
+  t->wg_fdct += (uint64_t)((g->nblocks + per_wg - 1) / per_wg);
+  t->wg_hist += (uint64_t)((g->nseg + per_hist - 1) / per_hist);
+  return t->wg_fdct <= 0x7FFFFFFFull && t->segs <= 0x7FFFFFFFull;
 }
 
 // ---- k_jpeg_fdct -----------------------------------------------------------------------------------------------------
@@ -307,6 +366,21 @@ struct SurfIn {
   };
   typedef vali_surface Item;  // what a lane keeps of its image
   static __device__ __forceinline__ Item item(const Args& a, int i) { return a.d_src[i]; }
+  // The image as a rectangle with its origin at pixel (x0, y0) sees it (vali_jpeg_encode_rois): every plane starts at
+  // the origin, a subsampled chroma plane (H x V, kYuv sources) at the origin over its sampling.  Rows and columns are
+  // then counted, and replicated, in the rectangle; an origin off a dword falls to the byte path of load_row_*.
+  static __device__ __forceinline__ Item item_at(const Args& a, int i, int x0, int y0, int H, int V) {
+    Item s = a.d_src[i];
+    const int bpp = SRC == SRC_RGB || SRC == SRC_BGR ? 3 : 1;
+    const void *p0 = s.plane[0], *p1 = s.plane[1], *p2 = s.plane[2];
+    s.plane[0] = (void*)((const u8*)p0 + (size_t)y0 * s.pitch[0] + bpp * x0);
+    if (SRC == SRC_RGB_PLANAR || SRC == SRC_YUV) {
+      const int cx = kYuv ? x0 / H : x0, cy = kYuv ? y0 / V : y0;
+      s.plane[1] = (void*)((const u8*)p1 + (size_t)cy * s.pitch[1] + cx);
+      s.plane[2] = (void*)((const u8*)p2 + (size_t)cy * s.pitch[2] + cx);
+    }
+    return s;
+  }
   static __device__ __forceinline__ void rgb_row(const Args&, const Item& s, int y, int x0, int cw, int R[8], int G[8],
                                                  int B[8]) {
     if (SRC == SRC_RGB_PLANAR) {
@@ -598,10 +672,58 @@ __device__ __forceinline__ void load_quadrant(const typename IN::Args& src, cons
 // and Cr samples of its quadrant of the MCU to the MCU's two chroma lanes through LDS; a chroma lane that loaded its own
 // 16 x 8 or 16 x 16 pixels would do so while the luma lanes of its wave wait.  A workgroup holds whole MCUs (the last
 // 256 % BPM lanes idle); the order of the blocks in the workspace stays the MCU-interleaved scan order.
-// The source's own arguments travel beside FdctArgs: `a` stays a plain kernel argument that nothing takes the address
-// of, so its tables are read where they are used.
-template <int SRC, int CS>
-__global__ void __launch_bounds__(256) k_jpeg_fdct(const FdctArgs a, const typename SourceOf<SRC>::Args src) {
+// The source's own arguments travel beside FdctArgs: nothing takes the address of `a`, so its tables are read where they
+// are used (fdct_args below).
+//
+// k_jpeg_fdct_roi (vali_jpeg_encode_rois): the grid is one-dimensional over the workgroups of images of any sizes, and a
+// workgroup reads what it works on from the record of the item that blockIdx.x falls in, into FdctWork: scalars, not
+// the record, since whatever stays live across the 64 ints of the block must sit in SGPRs.  In k_jpeg_fdct the image is
+// blockIdx.y and its geometry the launch's, and FdctWork only names what the kernel arguments hold.  The two kernels
+// share fdct_block.
+struct FdctWork {
+  int img;        // the image's descriptor / tensor item
+  int wg;         // the workgroup's place among the image's
+  int16_t* coef;  // the image's coefficients
+  int mcux, nblocks, cw0, cw1, ch0, ch1, bw0, bw1, bh0, bh1;
+};
+
+// the lane's image: as it is, or as the item's rectangle sees it
+template <class IN, bool ROI>
+__device__ __forceinline__ typename IN::Item fdct_item(const typename IN::Args& src, int img, int x0, int y0, int H,
+                                                       int V) {
+  if constexpr (ROI)
+    return IN::item_at(src, img, x0, y0, H, V);
+  else
+    return IN::item(src, img);
+}
+
+// The item whose workgroups hold workgroup `wg`: the last one whose first workgroup (field FIRST, ascending, [0] = 0) is
+// <= wg.  wg is blockIdx.x, the same for every lane, so the search and everything read from the record stay scalar.
+template <u32 vali_jpeg_item::*FIRST>
+__device__ __forceinline__ int find_item(const vali_jpeg_item* __restrict__ items, int n, u32 wg) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (items[mid].*FIRST <= wg)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+// The kernel's FdctArgs where the dispatch put them: FdctArgs is the FIRST argument of k_jpeg_fdct and k_jpeg_fdct_roi, so
+// it starts the kernel argument segment, and fdct_block reads it there, each field and table entry where it is used,
+// as a kernel does with an argument that nothing takes the address of.  Handed `a` by reference or by value, fdct_block
+// had all 256 table entries loaded up front, and every instantiation spilled 220..380 SGPRs.
+typedef const FdctArgs __attribute__((address_space(4))) * FdctArgsPtr;
+__device__ __forceinline__ FdctArgsPtr fdct_args() { return (FdctArgsPtr)__builtin_amdgcn_kernarg_segment_ptr(); }
+
+// One block of workgroup g.wg of the image g names: load, FDCT, quantisation, zigzag.  (rx, ry): ROI, the rectangle's
+// origin in its surface.
+template <int SRC, int CS, bool ROI>
+__device__ __forceinline__ void fdct_block(FdctArgsPtr a, const typename SourceOf<SRC>::Args& src, const FdctWork& g,
+                                           int rx, int ry) {
   using IN = SourceOf<SRC>;
   static_assert(CS == 0 || !IN::kYuv, "YUV sources bring their own chroma");
   int d[64];
@@ -611,17 +733,17 @@ __global__ void __launch_bounds__(256) k_jpeg_fdct(const FdctArgs a, const typen
     using SG = SubGeom<CS>;
     __shared__ u32 s_c[SG::MPW * SG::STRIDE];
     const int ml = threadIdx.x / SG::BPM, p = threadIdx.x - ml * SG::BPM;
-    gb = blockIdx.x * (SG::MPW * SG::BPM) + threadIdx.x;
-    const bool act = ml < SG::MPW && gb < a.nblocks;
-    const int mcu = blockIdx.x * SG::MPW + ml;
-    const int mx = mcu % a.mcux, my = mcu / a.mcux;
+    gb = g.wg * (SG::MPW * SG::BPM) + threadIdx.x;
+    const bool act = ml < SG::MPW && gb < g.nblocks;
+    const int mcu = g.wg * SG::MPW + ml;
+    const int mx = mcu % g.mcux, my = mcu / g.mcux;
     c = p < SG::HV ? 0 : p - SG::HV + 1;
     dummy = false;  // a chroma block of an MCU is always real: mcux = bw[1], mcuy = bh[1]
     if (act && c == 0) {
-      const typename IN::Item s = IN::item(src, blockIdx.y);
-      const int w = a.cw[0], h = a.ch[0];
+      const typename IN::Item s = fdct_item<IN, ROI>(src, g.img, rx, ry, a->H, a->V);
+      const int w = g.cw0, h = g.ch0;
       const int bx = mx * 2 + (p & 1), by = my * SG::V + (p >> 1);
-      dummy = bx >= a.bw[0] || by >= a.bh[0];
+      dummy = bx >= g.bw0 || by >= g.bh0;
       u32 cq[2][SG::NQ];
       // A dummy block codes the block whose DC it copies (jccoefct: the block to its left, for a dummy row the last block
       // of the row above in this MCU) but still owns the chroma of its own quadrant, and at 4:2:0 the bottom blocks
@@ -630,14 +752,14 @@ __global__ void __launch_bounds__(256) k_jpeg_fdct(const FdctArgs a, const typen
       const bool own = dummy || (CS == 2 && by * 8 + 8 > h);
       u32 cown[2][SG::NQ] = {};
       if (own)
-        load_quadrant<IN, CS, false, true, true>(src, s, bx * 8, by * 8, w, h, a.ch[1], d, cown);
+        load_quadrant<IN, CS, false, true, true>(src, s, bx * 8, by * 8, w, h, g.ch1, d, cown);
       int lx = bx, ly = by;
-      if (by >= a.bh[0]) {
+      if (by >= g.bh0) {
         lx = mx * 2 + 1;
-        ly = a.bh[0] - 1;
+        ly = g.bh0 - 1;
       }
-      lx = min(lx, a.bw[0] - 1);
-      load_quadrant<IN, CS, true, true, false>(src, s, lx * 8, ly * 8, w, h, a.ch[1], d, cq);
+      lx = min(lx, g.bw0 - 1);
+      load_quadrant<IN, CS, true, true, false>(src, s, lx * 8, ly * 8, w, h, g.ch1, d, cq);
       u32* o = s_c + ml * SG::STRIDE + p * SG::NQ;
 #pragma unroll
       for (int k = 0; k < 2; ++k)
@@ -661,22 +783,22 @@ __global__ void __launch_bounds__(256) k_jpeg_fdct(const FdctArgs a, const typen
         }
     }
   } else {
-    gb = blockIdx.x * 256 + threadIdx.x;
-    if (gb >= a.nblocks)
+    gb = g.wg * 256 + threadIdx.x;
+    if (gb >= g.nblocks)
       return;
-    const typename IN::Item s = IN::item(src, blockIdx.y);
-    const int mcu = gb / a.bpm, p = gb - mcu * a.bpm;
-    const int mx = mcu % a.mcux, my = mcu / a.mcux;
-    c = p < a.HV ? 0 : p - a.HV + 1;
-    int bx = c ? mx : mx * a.H + p % a.H;
-    int by = c ? my : my * a.V + p / a.H;
-    const int bw = c ? a.bw[1] : a.bw[0], bh = c ? a.bh[1] : a.bh[0];
-    const int cw = c ? a.cw[1] : a.cw[0], ch = c ? a.ch[1] : a.ch[0];
+    const typename IN::Item s = fdct_item<IN, ROI>(src, g.img, rx, ry, a->H, a->V);
+    const int mcu = gb / a->bpm, p = gb - mcu * a->bpm;
+    const int mx = mcu % g.mcux, my = mcu / g.mcux;
+    c = p < a->HV ? 0 : p - a->HV + 1;
+    int bx = c ? mx : mx * a->H + p % a->H;
+    int by = c ? my : my * a->V + p / a->H;
+    const int bw = c ? g.bw1 : g.bw0, bh = c ? g.bh1 : g.bh0;
+    const int cw = c ? g.cw1 : g.cw0, ch = c ? g.ch1 : g.ch0;
     // a dummy block of a partial MCU computes the block whose DC it copies (jccoefct): the block to its left, for a
     // dummy row the last block of the row above in this MCU -- always a real block after clamping
     dummy = bx >= bw || by >= bh;
     if (by >= bh) {
-      bx = c ? mx : mx * a.H + a.H - 1;
+      bx = c ? mx : mx * a->H + a->H - 1;
       by = bh - 1;
     }
     bx = min(bx, bw - 1);
@@ -718,8 +840,8 @@ __global__ void __launch_bounds__(256) k_jpeg_fdct(const FdctArgs a, const typen
 #pragma unroll
   for (int k = 0; k < 64; ++k) {
     const int x = d[kZigzag[k]];
-    const u32 recip = t ? a.recip[1][kZigzag[k]] : a.recip[0][kZigzag[k]];
-    const u32 cs = t ? a.corr_shift[1][kZigzag[k]] : a.corr_shift[0][kZigzag[k]];
+    const u32 recip = t ? a->recip[1][kZigzag[k]] : a->recip[0][kZigzag[k]];
+    const u32 cs = t ? a->corr_shift[1][kZigzag[k]] : a->corr_shift[0][kZigzag[k]];
     const u32 m = (u32)abs(x);
     const int q = (int)(((m + (cs & 0xFFFF)) * recip) >> (cs >> 16));
     int v = x < 0 ? -q : q;
@@ -730,10 +852,28 @@ __global__ void __launch_bounds__(256) k_jpeg_fdct(const FdctArgs a, const typen
     else
       out[k / 2] = (u32)(v & 0xFFFF);
   }
-  uint4* dst = (uint4*)(a.coef + ((size_t)blockIdx.y * a.nblocks + gb) * 64);
+  uint4* dst = (uint4*)(g.coef + (size_t)gb * 64);
 #pragma unroll
   for (int i = 0; i < 8; ++i)
     dst[i] = make_uint4(out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]);
+}
+
+
+template <int SRC, int CS>
+__global__ void __launch_bounds__(256) k_jpeg_fdct(const FdctArgs a, const typename SourceOf<SRC>::Args src) {
+  const FdctWork g = {(int)blockIdx.y, (int)blockIdx.x, a.coef + (size_t)blockIdx.y * a.nblocks * 64, a.mcux, a.nblocks,
+                      a.cw[0], a.cw[1], a.ch[0], a.ch[1], a.bw[0], a.bw[1], a.bh[0], a.bh[1]};
+  fdct_block<SRC, CS, false>(fdct_args(), src, g, 0, 0);
+}
+
+template <int SRC, int CS>
+__global__ void __launch_bounds__(256) k_jpeg_fdct_roi(const FdctArgs a, const typename SurfIn<SRC>::Args src,
+                                                       const vali_jpeg_item* __restrict__ items, int n) {
+  const int i = find_item<&vali_jpeg_item::wg_fdct>(items, n, blockIdx.x);
+  const vali_jpeg_item* it = items + i;
+  const FdctWork g = {i, (int)(blockIdx.x - it->wg_fdct), a.coef + it->block_first * 64, it->mcux, it->nblocks,
+                      it->cw[0], it->cw[1], it->ch[0], it->ch[1], it->bw[0], it->bw[1], it->bh[0], it->bh[1]};
+  fdct_block<SRC, CS, true>(fdct_args(), src, g, it->x, it->y);
 }
 
 // ---- entropy coding: what k_jpeg_hist and k_jpeg_huff share -------------------------------------------------------------
@@ -853,30 +993,45 @@ struct HistArgs {
 
 // Counts fit 32 bits: an image's output slot is addressed with 32 bits (jpeg_geom), a segment slot takes 416 bytes a
 // block, and a block has at most 64 symbols of one table.
-__global__ void __launch_bounds__(64 * kHistWaves) k_jpeg_hist(const HistArgs a) {
+// workgroup `wg` of an image of nseg segments / nblocks blocks whose coefficients are image `img` of `coef` (images
+// nblocks blocks apart); g: the image's four histograms
+__device__ __forceinline__ void hist_segments(const HistArgs& a, const int16_t* coef, size_t img, int nblocks, int nseg,
+                                              int wg, u32* g) {
   __shared__ u32 s_hist[4][256];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const size_t img = blockIdx.y;
   for (int i = tid; i < 4 * 256; i += 64 * kHistWaves)
     s_hist[i >> 8][i & 255] = 0;
   __syncthreads();
-  const int seg0 = (blockIdx.x * kHistWaves + wid) * kHistSegsPerWave;
-  const int seg1 = min(seg0 + kHistSegsPerWave, a.nseg);
+  const int seg0 = (wg * kHistWaves + wid) * kHistSegsPerWave;
+  const int seg1 = min(seg0 + kHistSegsPerWave, nseg);
   for (int seg = seg0; seg < seg1; ++seg) {  // wave-uniform
     const int base = seg * a.bps;
-    const int nb = min(a.bps, a.nblocks - base);
+    const int nb = min(a.bps, nblocks - base);
     int z[64], diff;
-    const bool chroma = segment_block(a.coef, img, a.nblocks, base, nb, a.bpm, a.HV, lane, z, &diff);
+    const bool chroma = segment_block(coef, img, nblocks, base, nb, a.bpm, a.HV, lane, z, &diff);
     if (lane < nb)
       code_block<BLOCK_COUNT>(z, diff, s_hist[chroma ? 2 : 0], s_hist[chroma ? 3 : 1], nullptr, 0);
   }
   __syncthreads();
-  u32* g = a.hist + img * (4 * 256);
   for (int i = tid; i < 4 * 256; i += 64 * kHistWaves) {
     const u32 c = s_hist[i >> 8][i & 255];
     if (c)
       atomicAdd(&g[i], c);  // integer adds: the sum does not depend on their order
   }
+}
+
+__global__ void __launch_bounds__(64 * kHistWaves) k_jpeg_hist(const HistArgs a) {
+  const size_t img = blockIdx.y;
+  hist_segments(a, a.coef, img, a.nblocks, a.nseg, blockIdx.x, a.hist + img * (4 * 256));
+}
+
+// a.nblocks and a.nseg are not read: they are the item's
+__global__ void __launch_bounds__(64 * kHistWaves) k_jpeg_hist_roi(const HistArgs a,
+                                                                   const vali_jpeg_item* __restrict__ items, int n) {
+  const int i = find_item<&vali_jpeg_item::wg_hist>(items, n, blockIdx.x);
+  const vali_jpeg_item* it = items + i;
+  hist_segments(a, a.coef + it->block_first * 64, 0, it->nblocks, it->nseg, (int)(blockIdx.x - it->wg_hist),
+                a.hist + (size_t)i * (4 * 256));
 }
 
 // ---- k_jpeg_tables ---------------------------------------------------------------------------------------------------
@@ -1032,25 +1187,26 @@ struct HuffArgs {
   u32 slot;
 };
 
-__global__ void __launch_bounds__(64) k_jpeg_huff(const HuffArgs a) {
+// segment `seg` of an image of nblocks blocks whose coefficients are image `img` of `coef` (images nblocks blocks apart),
+// with the tables `codes` (null: Annex K), into the slot `out`; its length goes to *seglen
+__device__ __forceinline__ void huff_segment(const HuffArgs& a, const int16_t* coef, size_t img, int nblocks, int seg,
+                                             const u32* codes, u8* out, u32* seglen) {
   __shared__ u32 s_codes[4][256];
   __shared__ u32 s_bits[kHuffWords];
   const int lane = threadIdx.x;
-  const int seg = blockIdx.x;
-  const size_t img = blockIdx.y;
-  if (a.codes) {  // the image's own tables (optimize = 1)
+  if (codes) {  // the image's own tables (optimize = 1)
     for (int i = lane; i < 4 * 256; i += 64)
-      s_codes[i >> 8][i & 255] = a.codes[img * (4 * 256) + i];
+      s_codes[i >> 8][i & 255] = codes[i];
   } else {
     for (int i = lane; i < 4 * 256; i += 64)
       s_codes[i >> 8][i & 255] = d_codes[i >> 8].e[i & 255];
   }
 
   const int base = seg * a.bps;
-  const int nb = min(a.bps, a.nblocks - base);
+  const int nb = min(a.bps, nblocks - base);
   const bool act = lane < nb;
   int z[64], diff;
-  const bool chroma = segment_block(a.coef, img, a.nblocks, base, nb, a.bpm, a.HV, lane, z, &diff);
+  const bool chroma = segment_block(coef, img, nblocks, base, nb, a.bpm, a.HV, lane, z, &diff);
   __syncthreads();  // code tables
 
   u32* dc = s_codes[chroma ? 2 : 0];
@@ -1071,7 +1227,6 @@ __global__ void __launch_bounds__(64) k_jpeg_huff(const HuffArgs a) {
 
   // byte stuffing: 4 bytes per lane per step, 0xFF counts prefix-summed across the wave
   const u32 nbytes = (total + pad) >> 3;
-  u8* out = a.slots + (img * a.nseg + seg) * a.slot;
   u32 opos = 0;
   for (u32 b0 = 0; b0 < nbytes; b0 += 256) {
     const u32 bi = b0 + 4 * lane;
@@ -1096,7 +1251,26 @@ __global__ void __launch_bounds__(64) k_jpeg_huff(const HuffArgs a) {
     opos += min(256u, nbytes - b0) + ftot;
   }
   if (lane == 0)
-    a.seglen[img * a.nseg + seg] = opos;
+    *seglen = opos;
+}
+
+__global__ void __launch_bounds__(64) k_jpeg_huff(const HuffArgs a) {
+  const int seg = blockIdx.x;
+  const size_t img = blockIdx.y;
+  const size_t k = img * a.nseg + seg;
+  huff_segment(a, a.coef, img, a.nblocks, seg, a.codes ? a.codes + img * (4 * 256) : nullptr, a.slots + k * a.slot,
+               a.seglen + k);
+}
+
+// one workgroup per segment of every item: blockIdx.x is the segment's place in the length and slot areas as well
+// (wg_seg = seg_first).  a.nblocks and a.nseg are not read: they are the item's
+__global__ void __launch_bounds__(64) k_jpeg_huff_roi(const HuffArgs a, const vali_jpeg_item* __restrict__ items,
+                                                      int n) {
+  const int i = find_item<&vali_jpeg_item::wg_seg>(items, n, blockIdx.x);
+  const vali_jpeg_item* it = items + i;
+  const size_t k = blockIdx.x;
+  huff_segment(a, a.coef + it->block_first * 64, 0, it->nblocks, (int)(blockIdx.x - it->wg_seg),
+               a.codes ? a.codes + (size_t)i * (4 * 256) : nullptr, a.slots + k * a.slot, a.seglen + k);
 }
 
 // ---- k_jpeg_offsets ----------------------------------------------------------------------------------------------------
@@ -1106,15 +1280,13 @@ __device__ __forceinline__ u32 dht_bytes(const u32* dhtlen, size_t img) {
   return 4 + l.x + l.y + l.z + l.w;
 }
 
-__global__ void __launch_bounds__(256) k_jpeg_offsets(const u32* seglen, u32* segoff, u32* sizes, int nseg,
-                                                      const u32* dhtlen) {
+// one image: seglen and segoff are its entries, `carry` the bytes in front of its entropy data
+__device__ __forceinline__ void image_offsets(const u32* seglen, u32* segoff, u32* size, int nseg, u32 carry) {
   __shared__ u32 s_wave[4];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const size_t img = blockIdx.x;
-  u32 carry = dhtlen ? dht_bytes(dhtlen, img) + kDriSosBytes : 0u;
   for (int s0 = 0; s0 < nseg; s0 += 256) {
     const int s = s0 + tid;
-    const u32 v = s < nseg ? seglen[img * nseg + s] + 2u : 0u;  // + RST marker
+    const u32 v = s < nseg ? seglen[s] + 2u : 0u;  // + RST marker
     const u32 incl = wave_incl_scan(v, lane);
     if (lane == 63)
       s_wave[wid] = incl;
@@ -1126,12 +1298,28 @@ __global__ void __launch_bounds__(256) k_jpeg_offsets(const u32* seglen, u32* se
       chunk += s_wave[w];
     }
     if (s < nseg)
-      segoff[img * nseg + s] = carry + before + incl - v;
+      segoff[s] = carry + before + incl - v;
     carry += chunk;
     __syncthreads();
   }
   if (tid == 0)
-    sizes[img] = carry - 2u;  // no marker after the last segment
+    *size = carry - 2u;  // no marker after the last segment
+}
+
+__global__ void __launch_bounds__(256) k_jpeg_offsets(const u32* seglen, u32* segoff, u32* sizes, int nseg,
+                                                      const u32* dhtlen) {
+  const size_t img = blockIdx.x;
+  image_offsets(seglen + img * nseg, segoff + img * nseg, sizes + img, nseg,
+                dhtlen ? dht_bytes(dhtlen, img) + kDriSosBytes : 0u);
+}
+
+__global__ void __launch_bounds__(256) k_jpeg_offsets_roi(const u32* seglen, u32* segoff, u32* sizes,
+                                                          const vali_jpeg_item* __restrict__ items,
+                                                          const u32* dhtlen) {
+  const size_t img = blockIdx.x;
+  const vali_jpeg_item* it = items + img;
+  image_offsets(seglen + it->seg_first, segoff + it->seg_first, sizes + img, it->nseg,
+                dhtlen ? dht_bytes(dhtlen, img) + kDriSosBytes : 0u);
 }
 
 // ---- k_jpeg_assemble ---------------------------------------------------------------------------------------------------
@@ -1148,13 +1336,11 @@ struct AsmArgs {
   int restart_interval;
 };
 
-__global__ void __launch_bounds__(256) k_jpeg_assemble(const AsmArgs a) {
-  const int seg = blockIdx.x;
-  const size_t img = blockIdx.y;
-  const size_t k = img * a.nseg + seg;
+// segment `seg` of the nseg of image `img`, entry k of the length, offset and slot areas, into the image's bytes at `o`
+__device__ __forceinline__ void assemble_segment(const AsmArgs& a, size_t img, int seg, int nseg, size_t k, u8* o) {
   const u32 len = a.seglen[k];
   const u8* src = a.slots + k * a.slot;
-  u8* dst = a.out + img * a.out_stride + a.segoff[k];
+  u8* dst = o + a.segoff[k];
   for (u32 i = 4 * threadIdx.x; i < len; i += 4 * 256) {
     const u32 v = *(const u32*)(src + i);  // slots are 16-byte aligned and a multiple of 16 long
     const u32 n = min(4u, len - i);
@@ -1163,12 +1349,11 @@ __global__ void __launch_bounds__(256) k_jpeg_assemble(const AsmArgs a) {
       if (j < n)
         dst[i + j] = (u8)(v >> (8 * j));
   }
-  if (threadIdx.x == 0 && seg + 1 < a.nseg) {
+  if (threadIdx.x == 0 && seg + 1 < nseg) {
     dst[len] = 0xFF;
     dst[len + 1] = (u8)(0xD0 + (seg & 7));
   }
   if (a.dht && seg == 0) {  // the image's own DHT, then DRI and SOS as write_header lays them out
-    u8* o = a.out + img * a.out_stride;
     u32 at = 4;
     for (int t = 0; t < 4; ++t) {
       const u32 n = a.dhtlen[img * 4 + t];
@@ -1187,6 +1372,20 @@ __global__ void __launch_bounds__(256) k_jpeg_assemble(const AsmArgs a) {
       o[17] = 0, o[18] = 63, o[19] = 0;
     }
   }
+}
+
+__global__ void __launch_bounds__(256) k_jpeg_assemble(const AsmArgs a) {
+  const int seg = blockIdx.x;
+  const size_t img = blockIdx.y;
+  assemble_segment(a, img, seg, a.nseg, img * a.nseg + seg, a.out + img * a.out_stride);
+}
+
+// as k_jpeg_huff_roi: blockIdx.x is the segment's entry.  a.nseg and a.out_stride are not read
+__global__ void __launch_bounds__(256) k_jpeg_assemble_roi(const AsmArgs a, const vali_jpeg_item* __restrict__ items,
+                                                           int n) {
+  const int i = find_item<&vali_jpeg_item::wg_seg>(items, n, blockIdx.x);
+  const vali_jpeg_item* it = items + i;
+  assemble_segment(a, (size_t)i, (int)(blockIdx.x - it->wg_seg), it->nseg, blockIdx.x, a.out + it->out_offset);
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
@@ -1362,6 +1561,45 @@ int jpeg_launch_rest(const char* fn, int n, const JpegLaunch& l, uint32_t* d_siz
   return VALI_OK;
 }
 
+// vali_jpeg_encode_rois: the same launches over flattened grids; every workgroup looks its image up in d_items
+template <int SRC>
+void launch_fdct_roi(int cs, u32 grid, hipStream_t s, const FdctArgs& f, const vali_surface* d_src,
+                     const vali_jpeg_item* d_items, int n) {
+  const typename SurfIn<SRC>::Args src = {d_src};
+  if (cs == 0)
+    hipLaunchKernelGGL((k_jpeg_fdct_roi<SRC, 0>), dim3(grid), dim3(256), 0, s, f, src, d_items, n);
+  else if (cs == 1)
+    hipLaunchKernelGGL((k_jpeg_fdct_roi<SRC, 1>), dim3(grid), dim3(256), 0, s, f, src, d_items, n);
+  else
+    hipLaunchKernelGGL((k_jpeg_fdct_roi<SRC, 2>), dim3(grid), dim3(256), 0, s, f, src, d_items, n);
+}
+
+int jpeg_launch_rest_roi(const char* fn, int n, const JpegLaunch& l, const RoiTotals& t, const vali_jpeg_item* d_items,
+                         uint32_t* d_sizes, hipStream_t s) {
+  hipError_t e;
+  if (l.hi.hist) {
+    if ((e = hipMemsetAsync(l.hi.hist, 0, (size_t)n * 4 * 256 * sizeof(u32), s)) != hipSuccess)
+      return fail(VALI_ERR_RUNTIME, "%s: clearing the histograms failed: %s", fn, hipGetErrorString(e));
+    hipLaunchKernelGGL(k_jpeg_hist_roi, dim3((u32)t.wg_hist), dim3(64 * kHistWaves), 0, s, l.hi, d_items, n);
+    if ((e = hipGetLastError()) != hipSuccess)
+      return fail(VALI_ERR_RUNTIME, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
+    hipLaunchKernelGGL(k_jpeg_tables, dim3(4, n), dim3(64), 0, s, l.tb);
+    if ((e = hipGetLastError()) != hipSuccess)
+      return fail(VALI_ERR_RUNTIME, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
+  }
+  hipLaunchKernelGGL(k_jpeg_huff_roi, dim3((u32)t.segs), dim3(64), 0, s, l.hf, d_items, n);
+  if ((e = hipGetLastError()) != hipSuccess)
+    return fail(VALI_ERR_RUNTIME, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
+  hipLaunchKernelGGL(k_jpeg_offsets_roi, dim3(n), dim3(256), 0, s, l.as.seglen, (u32*)l.as.segoff, (u32*)d_sizes,
+                     d_items, l.as.dhtlen);
+  if ((e = hipGetLastError()) != hipSuccess)
+    return fail(VALI_ERR_RUNTIME, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
+  hipLaunchKernelGGL(k_jpeg_assemble_roi, dim3((u32)t.segs), dim3(256), 0, s, l.as, d_items, n);
+  if ((e = hipGetLastError()) != hipSuccess)
+    return fail(VALI_ERR_RUNTIME, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
+  return VALI_OK;
+}
+
 } // namespace
 } // namespace vali
 
@@ -1471,6 +1709,99 @@ int vali_jpeg_encode_batch(const vali_surface* d_src, int n, int width, int heig
   }
   VALI_LAUNCH_CHECK();
   return jpeg_launch_rest(__func__, n, l, d_sizes, s);
+}
+
+int vali_jpeg_plan_rois(const vali_jpeg_roi* rois, const int32_t* src_w, const int32_t* src_h, int n,
+                        const vali_jpeg_params* params, vali_jpeg_item* items, size_t* ws_bytes, size_t* out_bytes) {
+  VALI_REQUIRE(ws_bytes && out_bytes, "null output");
+  JpegGeom g;
+  const int rc = jpeg_geom(__func__, n, 2, 2, params, &g);  // params and n; every format takes 2 x 2
+  if (rc != VALI_OK)
+    return rc;
+  *ws_bytes = *out_bytes = 0;
+  if (n == 0)
+    return VALI_OK;
+  VALI_REQUIRE(rois && src_w && src_h && items, "null argument");
+  int fh = 1, fv = 1;  // the sampling of the SOURCE's chroma planes: a rectangle starts and ends on their samples
+  jpeg_sampling(params->format, &fh, &fv);
+  RoiTotals t = {};
+  for (int i = 0; i < n; ++i) {
+    const vali_jpeg_roi& r = rois[i];
+    if (r.width < 1 || r.height < 1 || r.width > 65535 || r.height > 65535)
+      return fail(VALI_ERR_INVALID_ARG, "%s: item %d: rectangle of %d x %d: a side must be 1..65535", __func__, i,
+                  r.width, r.height);
+    if (r.x < 0 || r.y < 0 || (long long)r.x + r.width > src_w[i] || (long long)r.y + r.height > src_h[i])
+      return fail(VALI_ERR_INVALID_ARG, "%s: item %d: rectangle (%d, %d, %d, %d) does not lie inside its %d x %d surface",
+                  __func__, i, r.x, r.y, r.width, r.height, src_w[i], src_h[i]);
+    if ((fh == 2 && ((r.x | r.width) & 1)) || (fv == 2 && ((r.y | r.height) & 1)))
+      return fail(VALI_ERR_INVALID_ARG,
+                  "%s: item %d: rectangle (%d, %d, %d, %d): YUV420 needs even x, y, width and height, YUV422 an even x "
+                  "and width",
+                  __func__, i, r.x, r.y, r.width, r.height);
+    if (!roi_item(r, params, &g, &t, &items[i]))
+      return fail(VALI_ERR_INVALID_ARG,
+                  "%s: item %d: %d x %d is too large for one output slot, or the batch for one launch", __func__, i,
+                  r.width, r.height);
+  }
+  jpeg_layout((size_t)n, t.blocks, t.segs, &g);
+  *ws_bytes = g.ws_bytes;
+  *out_bytes = t.out;
+  return VALI_OK;
+}
+
+int vali_jpeg_encode_rois(const vali_surface* d_src, const vali_jpeg_item* items, const vali_jpeg_item* d_items, int n,
+                          const vali_jpeg_params* params, void* workspace, size_t ws_bytes, uint8_t* d_out,
+                          size_t out_bytes, uint32_t* d_sizes, vali_stream_t stream) {
+  VALI_REQUIRE(d_src && items && d_items && params && workspace && d_out && d_sizes, "null argument");
+  JpegGeom g;
+  int rc = jpeg_geom(__func__, n, 2, 2, params, &g);
+  if (rc != VALI_OK)
+    return rc;
+  if (n == 0)
+    return VALI_OK;
+  // the records are the plan's: made again from their rectangles, they come out as they are
+  RoiTotals t = {};
+  for (int i = 0; i < n; ++i) {
+    const vali_jpeg_item& it = items[i];
+    const vali_jpeg_roi r = {it.x, it.y, it.width, it.height};
+    vali_jpeg_item again;
+    if (r.x < 0 || r.y < 0 || r.width < 1 || r.height < 1 || r.width > 65535 || r.height > 65535 ||
+        !roi_item(r, params, &g, &t, &again) || memcmp(&again, &it, sizeof(it)) != 0)
+      return fail(VALI_ERR_INVALID_ARG, "%s: item %d is not what vali_jpeg_plan_rois makes for these params", __func__,
+                  i);
+  }
+  jpeg_layout((size_t)n, t.blocks, t.segs, &g);
+  if ((((uintptr_t)workspace) & 255) != 0)
+    return fail(VALI_ERR_INVALID_ARG, "%s: workspace not 256-byte aligned", __func__);
+  if (ws_bytes < g.ws_bytes)
+    return fail(VALI_ERR_INVALID_ARG, "%s: workspace below the plan's ws_bytes", __func__);
+  if (out_bytes < t.out)
+    return fail(VALI_ERR_INVALID_ARG, "%s: output below the plan's out_bytes", __func__);
+  JpegLaunch l;  // the areas of the workspace and the tables; what it holds of one image's geometry is not read
+  rc = jpeg_launch_prepare(__func__, n, g, params, workspace, ws_bytes, d_out, out_bytes, &l);
+  if (rc != VALI_OK)
+    return rc;
+
+  hipStream_t s = as_stream(stream);
+  VALI_ENTRY(s);
+  const u32 grid = (u32)t.wg_fdct;
+  switch (params->format) {
+  case VALI_FMT_RGB:
+    launch_fdct_roi<SRC_RGB>(l.cs, grid, s, l.f, d_src, d_items, n);
+    break;
+  case VALI_FMT_BGR:
+    launch_fdct_roi<SRC_BGR>(l.cs, grid, s, l.f, d_src, d_items, n);
+    break;
+  case VALI_FMT_RGB_PLANAR:
+    launch_fdct_roi<SRC_RGB_PLANAR>(l.cs, grid, s, l.f, d_src, d_items, n);
+    break;
+  default:
+    hipLaunchKernelGGL((k_jpeg_fdct_roi<SRC_YUV, 0>), dim3(grid), dim3(256), 0, s, l.f, SurfIn<SRC_YUV>::Args{d_src},
+                       d_items, n);
+    break;
+  }
+  VALI_LAUNCH_CHECK();
+  return jpeg_launch_rest_roi(__func__, n, l, t, d_items, d_sizes, s);
 }
 
 int vali_jpeg_encode_tensor(const vali_tensor_src* src, const float scale[3], const float offset[3],

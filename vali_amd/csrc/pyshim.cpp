@@ -623,6 +623,34 @@ PYBIND11_MODULE(_vali_shim, m) {
         },
         py::call_guard<py::gil_scoped_release>());
 
+  // regions of surfaces of any sizes: rois is an (n, 4) int32 array of (x, y, width, height), src_w / src_h int32
+  // arrays of the surfaces' sizes; the records come back as one bytes blob of n * JPEG_ITEM_SIZE (numpy reads it
+  // with a structured dtype), to be copied to the device and passed back as they are
+  m.attr("JPEG_ITEM_SIZE") = (int)sizeof(vali_jpeg_item);
+  m.def("jpeg_plan_rois", [](py::buffer rois, py::buffer src_w, py::buffer src_h, const JpegParams& j) {
+    const py::buffer_info r = rois.request(), w = src_w.request(), h = src_h.request();
+    const size_t n = (size_t)w.size;
+    if (r.itemsize != 4 || w.itemsize != 4 || h.itemsize != 4 || (size_t)r.size != 4 * n || (size_t)h.size != n)
+      throw py::value_error("jpeg_plan_rois: rois must be (n, 4) int32, src_w and src_h n int32 each");
+    std::string items(n * sizeof(vali_jpeg_item), '\0');
+    size_t ws = 0, out = 0;
+    check(vali_jpeg_plan_rois((const vali_jpeg_roi*)r.ptr, (const int32_t*)w.ptr, (const int32_t*)h.ptr, (int)n, &j.p,
+                              (vali_jpeg_item*)&items[0], &ws, &out),
+          "vali_jpeg_plan_rois");
+    return py::make_tuple(py::bytes(items), ws, out);
+  });
+  m.def("jpeg_encode_rois",
+        [](uintptr_t d_src, py::buffer items, uintptr_t d_items, int n, const JpegParams& j, uintptr_t workspace,
+           size_t ws_bytes, uintptr_t d_out, size_t out_bytes, uintptr_t d_sizes, uintptr_t stream) {
+          const py::buffer_info it = items.request();
+          if ((size_t)(it.size * it.itemsize) != (size_t)n * sizeof(vali_jpeg_item))
+            throw py::value_error("jpeg_encode_rois: items must hold n records of JPEG_ITEM_SIZE bytes");
+          py::gil_scoped_release rel;
+          return vali_jpeg_encode_rois((const vali_surface*)P(d_src), (const vali_jpeg_item*)it.ptr,
+                                       (const vali_jpeg_item*)P(d_items), n, &j.p, P(workspace), ws_bytes,
+                                       (uint8_t*)P(d_out), out_bytes, (uint32_t*)P(d_sizes), P(stream));
+        });
+
   // the batch tensor the encoder reads: the arguments of TensorDst; vali_jpeg_encode_tensor judges it
   py::class_<TensorSrc>(m, "TensorSrc")
       .def(py::init([](uintptr_t data, int dtype, int packed, int n, int width, int height, int64_t stride_n,
