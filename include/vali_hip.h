@@ -503,6 +503,46 @@ VALI_API int vali_jpeg_encode_tensor(const vali_tensor_src* src, const float sca
                                      const vali_jpeg_params* params, void* workspace, size_t ws_bytes,
                                      uint8_t* d_out, size_t out_stride, uint32_t* d_sizes, vali_stream_t stream);
 
+/* ---- batch tensor -> video frames: the way back from a network's output ---------------------
+ *
+ * One (N, 3, H, W) tensor -> N 8-bit surfaces of W x H, one launch.  src: as vali_jpeg_encode_tensor takes it (HOST
+ * struct, float32 / float16 / bfloat16 / uint8, planar or channels last, strides in elements).  d_dst: DEVICE array of
+ * src->n descriptors of dst_format.  bgr: 0 = tensor channels are R, G, B; 1 = B, G, R.
+ * For item i and pixel (x, y):
+ *   p[c] = clamp(rint(fl32(fl32(e[c] * scale[c]) + offset[c])), 0, 255), NaN -> 0, ties to even, never a fused
+ *          multiply-add: the words, and the code, of vali_jpeg_encode_tensor; scale and offset belong to TENSOR channel
+ *          c; R, G, B are then named by bgr.
+ *   VALI_FMT_RGB, VALI_FMT_RGB_PLANAR   the bytes R, G, B; params may be NULL
+ *   VALI_FMT_YUV444   o_k = fmaf(m[k][2], B, fmaf(m[k][1], G, fmaf(m[k][0], R, m[k][3]))), m = params->rgb2yuv; each
+ *                     value is sat_u8(rint(o_k))
+ *   VALI_FMT_YUV420   Y as above; chroma = sat_u8(rint(((o00 + o01) + (o10 + o11)) * 0.25f)) over the UN-ROUNDED values
+ *                     of the 2 x 2 block, in exactly that association: byte for byte what vali_convert RGB -> YUV420
+ *                     writes for an RGB surface that holds p
+ *   VALI_FMT_NV12     the YUV420 values with U and V interleaved in plane 1
+ * NV12 and YUV420 need even W and H; the others take any size, 1 x 1 included.  The destinations may be pitched and may
+ * be views at any address and pitch: misaligned ones take a slower store path with the same bytes.  Only the W x H
+ * image area of each plane is written.
+ * VALI_ERR_INVALID_ARG, before any device is touched, for: null src, scale, offset or d_dst; null params with a YUV
+ * destination; everything vali_jpeg_encode_tensor refuses in src, scale and offset; bgr outside 0..1; an odd size for a
+ * 4:2:0 destination.  VALI_ERR_UNSUPPORTED for every other dst_format.  Nothing is allocated and nothing synchronises,
+ * so the call can be captured into a graph.
+ *
+ * The BT.709 matrices python_vali's PySurfacePostprocessor passes (this project's own definition: the reference has no
+ * RGB -> YUV call for BT.709).  Kr = 0.2126, Kb = 0.0722, Kg = 1 - Kr - Kb; full range Y (Kr, Kg, Kb, 0),
+ * Cb (-Kr / (2 (1 - Kb)), -Kg / (2 (1 - Kb)), 0.5, 128), Cr (0.5, -Kg / (2 (1 - Kr)), -Kb / (2 (1 - Kr)), 128); MPEG
+ * range: the Y row x 219 / 255 with offset 16, the chroma rows x 224 / 255 with offset 128.  Each constant is computed
+ * in double and rounded to float32 once:
+ *   full range   Y   0.2125999927520752    0.7152000069618225    0.0722000002861023      0
+ *                Cb -0.11457210779190063  -0.38542789220809937   0.5                   128
+ *                Cr  0.5                  -0.454152911901474    -0.0458470918238163    128
+ *   MPEG range   Y   0.18258588016033173   0.6142305731773376    0.062007058411836624   16
+ *                Cb -0.10064373165369034  -0.3385719656944275    0.43921568989753723   128
+ *                Cr  0.43921568989753723  -0.39894217252731323  -0.040273524820804596  128
+ */
+VALI_API int vali_tensor_to_surfaces(const vali_tensor_src* src, const float scale[3], const float offset[3], int bgr,
+                                     const vali_surface* d_dst, int dst_format, const vali_cvt_params* params,
+                                     vali_stream_t stream);
+
 /*
  * Rectangles of surfaces of ANY sizes as files, in one fixed set of launches.  Item i is rectangle rois[i] of the
  * surface d_src[i] (the same surface may stand behind any number of items); its file is byte for byte the file of

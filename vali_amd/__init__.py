@@ -18,8 +18,8 @@ if not _BUILDING:
     from .runtime import CudaStreamEvent, GetNumGpus, HipResMgr, StreamCapture
     from .surface import Surface, SurfacePlane
     from .buffer import CudaBuffer
-    from .tasks import (PySurfaceConverter, PySurfacePreprocessor, PySurfaceResizer, PySurfaceRotator, PySurfaceUD,
-                        RoiBatch, SurfaceBatch, TensorBatch, letterbox_rect)
+    from .tasks import (FrameBatch, PySurfaceConverter, PySurfacePostprocessor, PySurfacePreprocessor, PySurfaceResizer,
+                        PySurfaceRotator, PySurfaceUD, RoiBatch, SurfaceBatch, TensorBatch, letterbox_rect)
     from .pipeline import BatchedFramePipeline, broadcast_coefficients, shard_frames
     from .transfer import PyFrameUploader, PySurfaceDownloader
     from . import tuning

@@ -673,6 +673,16 @@ PYBIND11_MODULE(_vali_shim, m) {
         },
         py::call_guard<py::gil_scoped_release>());
 
+  // the same tensor into 8-bit surfaces: d_dst is a device array of descriptors (descs_upload); params may be None for
+  // RGB destinations
+  m.def("tensor_to_surfaces",
+        [](const TensorSrc& src, const std::array<float, 3>& scale, const std::array<float, 3>& offset, int bgr,
+           uintptr_t d_dst, int dst_format, const CvtParams* p, uintptr_t stream) {
+          return vali_tensor_to_surfaces(&src.t, scale.data(), offset.data(), bgr, (const vali_surface*)P(d_dst),
+                                         dst_format, p ? &p->p : nullptr, P(stream));
+        },
+        py::call_guard<py::gil_scoped_release>());
+
   // ---- JPEG decoder: host-side parser and sizes, then the batched decoder --------------------------------------
   py::class_<JpegInfo>(m, "JpegInfo")
       .def_property_readonly("width", [](const JpegInfo& j) { return j.f.width; })

@@ -1168,6 +1168,156 @@ class TensorBatch:
 
 
 # ---- PySurfaceRotator --------------------------------------------------------------------
+# ---- PySurfacePostprocessor: a batch tensor back into video frames ----------------------------------
+def _f32(v: float) -> float:
+    """a double rounded to float32 once"""
+    import struct
+
+    return struct.unpack("<f", struct.pack("<f", v))[0]
+
+
+def _bt709_rgb2yuv(mpeg: bool):
+    """BT.709 RGB -> YCbCr (include/vali_hip.h spells the formulas and the numbers out): Kr = 0.2126, Kb = 0.0722; full
+    range, or the Y row x 219 / 255 + 16 and the chroma rows x 224 / 255 + 128; computed in double, rounded once."""
+    kr, kb = 0.2126, 0.0722
+    kg = 1.0 - kr - kb
+    rows = ((kr, kg, kb), (-kr / (2 * (1 - kb)), -kg / (2 * (1 - kb)), 0.5), (0.5, -kg / (2 * (1 - kr)), -kb / (2 * (1 - kr))))
+    ys, cs, y0 = (219.0 / 255.0, 224.0 / 255.0, 16.0) if mpeg else (1.0, 1.0, 0.0)
+    return tuple(tuple(_f32(v * (ys if k == 0 else cs)) for v in row) + ((y0 if k == 0 else 128.0),)
+                 for k, row in enumerate(rows))
+
+
+RGB2YUV_BT709_JPEG = _bt709_rgb2yuv(False)
+RGB2YUV_BT709_MPEG = _bt709_rgb2yuv(True)
+
+
+class FrameBatch:
+    """One (N, 3, H, W) tensor and the N surfaces it is written into: the destination descriptors uploaded once
+    (PySurfacePostprocessor.PrepareTensorBatch).  Keeps the tensor and the surfaces alive."""
+
+    def __init__(self, gpu_id: int, stream: int, tensor, dsts: Sequence[Surface]):
+        self.src, self.layout, self.dtype, (n, h, w), _, holder = _tensor_src(tensor, gpu_id)
+        dsts = list(dsts)
+        if len(dsts) != n:
+            raise ValueError(f"FrameBatch: {len(dsts)} surfaces for a tensor of {n} items")
+        fmt = None
+        for i, d in enumerate(dsts):
+            if d is None or d.IsEmpty:
+                raise ValueError(f"FrameBatch: surface {i} is empty")
+            if d.Format not in PySurfacePostprocessor._DST:
+                raise ValueError(f"FrameBatch: surface {i} has format {d.Format!r}; supported: "
+                                 f"{', '.join(f.name for f in PySurfacePostprocessor._DST)}")
+            if fmt is not None and d.Format != fmt:
+                raise ValueError(f"FrameBatch: surface {i} has format {d.Format!r}, surface 0 {fmt!r}: one format per batch")
+            fmt = d.Format
+            if (d.Width, d.Height) != (w, h):
+                raise ValueError(f"FrameBatch: surface {i} is {d.Width}x{d.Height}, the tensor's items are {w}x{h}: "
+                                 "the sizes must be equal (no resizing on the way out)")
+            if fmt in (F.NV12, F.YUV420) and (w | h) & 1:
+                raise ValueError(f"FrameBatch: surface {i}: {fmt.name} is 4:2:0 and needs an even width and height, "
+                                 f"got {w}x{h}")
+            dev = getattr(d, "DeviceId", gpu_id)
+            if dev != gpu_id:
+                raise ValueError(f"FrameBatch: surface {i} is on device {dev}, the task on {gpu_id}")
+        if is_capturing(gpu_id, stream):
+            raise RuntimeError("FrameBatch: cannot be created while the stream is capturing -- PrepareTensorBatch() "
+                               "before the StreamCapture block and Keep() the batch with the capture")
+        self.gpu_id = gpu_id
+        self._stream = stream
+        self.n = n
+        self.size = (w, h)
+        self.dst_format = fmt
+        self.tensor = tensor
+        self._keep = (tensor, holder, dsts)
+        self.d_dst = shim.descs_upload(gpu_id, [d.desc() for d in dsts], stream)
+
+    def __len__(self):
+        return self.n
+
+    def __del__(self):
+        p = getattr(self, "d_dst", 0)
+        if p:
+            try:    # a launch issued on the batch's stream may still be reading the array
+                shim.stream_sync(self.gpu_id, self._stream)
+            except Exception:
+                pass
+            try:
+                shim.mem_free(self.gpu_id, p)
+            except Exception:
+                pass
+            self.d_dst = 0
+
+
+class PySurfacePostprocessor(_SurfaceTask):
+    """One (N, 3, H, W) tensor -> N NV12, YUV420, YUV444, RGB or RGB_PLANAR surfaces of W x H, ONE launch
+    (vali_tensor_to_surfaces): the way from a network's output back to what PyNvEncoder, the resizer, the rotator and the
+    JPEG encoder take.  The mirror image of PySurfacePreprocessor.RunTensorBatch.
+
+    The reference has no such task.  It is DEFINED as the chain it replaces and is byte-identical to it
+    (tests/test_gpu_postproc.py):
+
+        p = torch.nan_to_num(x.float() * scale + offset, nan=0.0).round().clamp(0, 255).to(torch.uint8)
+        per item: Surface.from_dlpack(p as H x W x 3, RGB) -> PySurfaceConverter RGB -> YUV420 [-> NV12] / YUV444 / RGB_PLANAR
+
+    `tensor`: float32, float16, bfloat16 or uint8 through `__dlpack__` or `__cuda_array_interface__`; contiguous, a slice
+    that keeps rows contiguous, or channels last (the rules and messages of PyNvJpegEncoder.RunTensor).
+    `scale`, `offset`: a number or three, per TENSOR channel; scale=None is 255 for the float dtypes, 1 for uint8.
+    `channels`: "RGB" or "BGR", the order of the tensor's channels.
+    `cc_ctx`: None or BT_601 + JPEG -> nppiRGBToYUV's matrix, BT_601 + MPEG -> nppiRGBToYCbCr's (the two PySurfaceConverter
+    uses); BT_709 + JPEG / MPEG -> RGB2YUV_BT709_JPEG / _MPEG, this project's own (the reference has no RGB -> YUV call
+    for BT.709); anything else: (False, UNSUPPORTED_FMT_CONV_PARAMS), nothing is launched.  Ignored for RGB destinations.
+    """
+
+    _DST = (F.NV12, F.YUV420, F.YUV444, F.RGB, F.RGB_PLANAR)
+    _MATRICES = {
+        (ColorSpace.BT_601, ColorRange.JPEG): RGB2YUV_NPP_YUV,
+        (ColorSpace.BT_601, ColorRange.MPEG): RGB2YUV_NPP_YCBCR,
+        (ColorSpace.BT_709, ColorRange.JPEG): RGB2YUV_BT709_JPEG,
+        (ColorSpace.BT_709, ColorRange.MPEG): RGB2YUV_BT709_MPEG,
+    }
+
+    @staticmethod
+    def SupportedFormats() -> List[PixelFormat]:
+        """every destination format the task writes"""
+        return list(PySurfacePostprocessor._DST)
+
+    @staticmethod
+    def Matrix(cc_ctx=None):
+        """the RGB -> YUV rows (kR, kG, kB, offset) of Y, U, V that `cc_ctx` selects, or None if it selects none"""
+        space, rng = _space_range(cc_ctx, ColorSpace.BT_601, ColorRange.JPEG)
+        return PySurfacePostprocessor._MATRICES.get((space, rng))
+
+    def PrepareTensorBatch(self, tensor, dsts: Sequence[Surface]) -> FrameBatch:
+        return FrameBatch(self._gpu_id, self._stream, tensor, dsts)
+
+    def RunTensorBatchAsync(self, batch: FrameBatch, scale=None, offset=0.0, cc_ctx=None,
+                            channels: str = "RGB") -> Tuple[bool, TaskExecInfo]:
+        """One launch over the items of `batch`."""
+        from .codecs import _triple
+
+        if not isinstance(batch, FrameBatch):
+            raise ValueError("RunTensorBatch: pass a FrameBatch (PrepareTensorBatch)")
+        if channels not in ("RGB", "BGR"):
+            raise ValueError(f"channels: 'RGB' or 'BGR', got {channels!r}")
+        offset = _triple("offset", offset)
+        scale = _triple("scale", (1.0 if batch.dtype == "uint8" else 255.0) if scale is None else scale)
+        params = None
+        if batch.dst_format in (F.NV12, F.YUV420, F.YUV444):
+            m = self.Matrix(cc_ctx)
+            if m is None:
+                return _S_UNSUPP_CC.success, _S_UNSUPP_CC.info
+            params = _params(rgb2yuv=m)
+        d = _status(shim.tensor_to_surfaces(batch.src, scale, offset, 1 if channels == "BGR" else 0, batch.d_dst,
+                                            int(batch.dst_format), params, self._stream))
+        return d.success, d.info
+
+    def RunTensorBatch(self, batch: FrameBatch, scale=None, offset=0.0, cc_ctx=None,
+                       channels: str = "RGB") -> Tuple[bool, TaskExecInfo]:
+        r = self.RunTensorBatchAsync(batch, scale, offset, cc_ctx, channels)
+        self._sync()
+        return r
+
+
 _ROT_FORMATS = [F.Y, F.GRAY12, F.RGB, F.BGR, F.RGB_PLANAR, F.YUV420, F.YUV422, F.YUV444, F.RGB_32F,
                 F.RGB_32F_PLANAR, F.YUV444_10bit, F.YUV420_10bit]
 # format -> (driver, element size); RotateSurface::Run switch (RotateSurface.cpp:168-208)
