@@ -543,6 +543,49 @@ VALI_API int vali_tensor_to_surfaces(const vali_tensor_src* src, const float sca
                                      const vali_surface* d_dst, int dst_format, const vali_cvt_params* params,
                                      vali_stream_t stream);
 
+/* ---- marks on frames: outlines, fills and pixelation from a device-held list ---------------
+ *
+ * m marks are drawn IN PLACE onto n frames of one format (NV12, YUV420, YUV444, RGB, BGR, RGB_PLANAR; any sizes, 4:2:0
+ * even) in TWO launches, whatever m and the data.  d_marks is DEVICE memory (4-byte aligned): a detector's output is
+ * drawn without a device-to-host copy.  Marks are applied in row order; the result is what applying them one after the
+ * other gives.  A row is SKIPPED when kind is VALI_MARK_NONE or unknown, frame is outside 0..n-1, w < 1 or h < 1, arg
+ * is invalid for its kind or the rectangle does not meet its frame; every int32 value of x, y, w, h is handled
+ * (intersections are formed in 64 bits).
+ *   colour   a << 24 | r << 16 | g << 8 | b.  A sample's colour value c is r, g or b by name for RGB, BGR, RGB_PLANAR;
+ *            for the YUV formats sat_u8(rint(fmaf(m[k][2], b, fmaf(m[k][1], g, fmaf(m[k][0], r, m[k][3]))))), k = Y, U,
+ *            V, m = params->rgb2yuv: what vali_tensor_to_surfaces writes into YUV444 for that pixel
+ *   NV12, YUV420   first x0 = x & ~1, y0 = y & ~1, x1 = (x + w + 1) & ~1, y1 = (y + h + 1) & ~1 and a BOX thickness is
+ *            rounded up to even: a chroma sample is painted exactly when its four luma pixels are
+ *   VALI_MARK_FILL      every sample of every plane in rectangle ^ frame: v = (v * (255 - a) + c * a + 127) / 255
+ *   VALI_MARK_BOX       arg = thickness t >= 1: the same blend for the pixels of the UNCLIPPED rectangle outside its
+ *                       inner rectangle [x0 + t, x1 - t) x [y0 + t, y1 - t), then clipped to the frame
+ *   VALI_MARK_PIXELATE  arg = cell s in {4, 8, 16, 32}; the rectangle grows outward to the frame's s-grid and is
+ *                       clipped to the frame; per plane every sample of (cell ^ frame) becomes (sum + cnt / 2) / cnt
+ *                       over the plane's samples in (cell ^ frame); 4:2:0 chroma planes use cells of s / 2
+ * Only samples inside the image area of a plane are written, and only those a mark changed; frames and tiles no
+ * mark meets are neither read nor written.  frames is the HOST copy of the descriptors in d_frames (sizes and the
+ * launch grid come from it).  workspace: vali_annotate_workspace_size bytes of device memory, 16-byte aligned; its
+ * contents need not survive between calls.  Nothing is allocated and nothing synchronises, so the call can be captured
+ * and replayed after d_marks was rewritten in place.  n = 0 or m = 0: success, nothing is launched.
+ * VALI_ERR_INVALID_ARG, before any device is touched: null arguments (frames and d_frames with n > 0, d_marks with
+ * m > 0, params for a YUV format, workspace with n > 0); n outside 0..65535; m outside 0..4096; a frame with a null
+ * plane, a size outside 1..65535, an odd size in a 4:2:0 format, a pitch shorter than a row or a format other than
+ * `format`; a workspace that is too small or not 16-byte aligned.  VALI_ERR_UNSUPPORTED for a format outside the list.
+ */
+#define VALI_MARK_NONE 0
+#define VALI_MARK_BOX 1
+#define VALI_MARK_FILL 2
+#define VALI_MARK_PIXELATE 3
+#define VALI_MAX_MARKS 4096
+typedef struct vali_mark {
+  int32_t frame, x, y, w, h, kind, arg, colour;
+} vali_mark; /* 32 bytes */
+
+VALI_API int vali_annotate_workspace_size(int n, const vali_surface* frames, size_t* bytes);
+VALI_API int vali_annotate_batch(const vali_surface* frames, const vali_surface* d_frames, int n, int format,
+                                 const vali_mark* d_marks, int m, const vali_cvt_params* params, void* workspace,
+                                 size_t ws_bytes, vali_stream_t stream);
+
 /*
  * Rectangles of surfaces of ANY sizes as files, in one fixed set of launches.  Item i is rectangle rois[i] of the
  * surface d_src[i] (the same surface may stand behind any number of items); its file is byte for byte the file of

@@ -18,8 +18,9 @@ if not _BUILDING:
     from .runtime import CudaStreamEvent, GetNumGpus, HipResMgr, StreamCapture
     from .surface import Surface, SurfacePlane
     from .buffer import CudaBuffer
-    from .tasks import (FrameBatch, PySurfaceConverter, PySurfacePostprocessor, PySurfacePreprocessor, PySurfaceResizer,
-                        PySurfaceRotator, PySurfaceUD, RoiBatch, SurfaceBatch, TensorBatch, letterbox_rect)
+    from .tasks import (MARK_BOX, MARK_FILL, MARK_NONE, MARK_PIXELATE, AnnotateBatch, FrameBatch, PySurfaceAnnotator,
+                        PySurfaceConverter, PySurfacePostprocessor, PySurfacePreprocessor, PySurfaceResizer,
+                        PySurfaceRotator, PySurfaceUD, RoiBatch, SurfaceBatch, TensorBatch, letterbox_rect, pack_colour)
     from .pipeline import BatchedFramePipeline, broadcast_coefficients, shard_frames
     from .transfer import PyFrameUploader, PySurfaceDownloader
     from . import tuning

@@ -1,0 +1,522 @@
+// Marks on frames (vali_annotate_batch): outlines, translucent fills and pixelation drawn IN PLACE onto a batch of NV12,
+// YUV420, YUV444, RGB, BGR or RGB_PLANAR frames of any sizes, from a list of marks that lives in DEVICE memory -- the
+// step between a detector's output and PyNvEncoder / the JPEG encoder, without the device-to-host copy and the four
+// launches per box and plane of torch slice assignments.
+//
+// Definition: include/vali_hip.h ("marks on frames"); tests/annotate_model.py restates it in numpy.
+//
+// Drawing in place is deterministic without any ordering between workgroups because of cell alignment: a workgroup owns
+// one 64 x 64 luma tile of one frame, aligned to the frame's origin; pixelation cells (4 .. 32) divide 64 and sit on the
+// frame's grid, so every cell lies inside one tile.  The workgroup applies ALL marks that meet its tile, in row order, to
+// samples it holds in registers, and stores each 16-byte piece once -- and only if a mark changed it.
+//
+// Two launches, whatever m and the data:
+//   k_annotate_bin   one workgroup per frame: sanitises the rows and leaves, in the workspace, the indices of the rows
+//                    that draw on its frame, in row order (a ballot / prefix compaction).  The tiles then scan their
+//                    frame's rows, not all m: m * 32 bytes per TILE was the alternative
+//   k_annotate<FMT>  grid (tiles of the largest frame, n).  A tile whose frame has no row leaves after two scalar loads;
+//                    otherwise it culls the frame's rows against the tile into an LDS hit list (again in order) and, with
+//                    no hit, leaves without touching a pixel
+// A lane owns the same 16-byte pieces of the tile throughout (one of Y, one of interleaved UV; three of packed RGB; one
+// of each plane of the planar formats): loaded and stored as 16-byte vectors at any alignment, byte by byte only where
+// the frame's right edge cuts a piece.  Fills and outlines are therefore lane-local and need no barrier; only pixelation
+// goes through LDS (integer atomic adds into per-cell sums: the sum does not depend on the order) and is fenced by
+// barriers.  Every branch on the mark kind is workgroup-uniform; the mark records are read at a uniform index.
+#include "common.hpp"
+#include "dev_util.hpp"
+
+namespace vali {
+namespace {
+
+constexpr int kTile = 64;                               // luma pixels a side
+constexpr int kMaxMarks = VALI_MAX_MARKS;
+constexpr size_t kBinBytes = 16 + (size_t)kMaxMarks * 2;  // per frame: the count, then uint16 row indices in row order
+constexpr int kCells = (kTile / 4) * (kTile / 4) * 3;   // cell sums of a tile: 16 x 16 cells of 4, three channels
+
+enum AnnFmt : int { A_NV12 = 0, A_YUV420 = 1, A_YUV444 = 2, A_RGB = 3, A_BGR = 4, A_RGBP = 5 };
+
+constexpr bool a_is420(int f) { return f == A_NV12 || f == A_YUV420; }
+constexpr bool a_isyuv(int f) { return f == A_NV12 || f == A_YUV420 || f == A_YUV444; }
+
+// A lane's share of the tile: piece (lane + first) of plane `plane`, whose bytes interleave `nc` channels starting with
+// colour channel c0 (0, 1, 2 = Y, U, V or the format's first, second, third stored colour) at 1 >> sh samples per pixel
+struct Slot {
+  int plane, nc, sh, c0, first;
+};
+constexpr int nslots(int f) { return f == A_NV12 ? 2 : 3; }
+constexpr Slot slot_of(int f, int s) {
+  return (f == A_RGB || f == A_BGR) ? Slot{0, 3, 0, 0, s * kBlock}
+         : f == A_NV12              ? (s == 0 ? Slot{0, 1, 0, 0, 0} : Slot{1, 2, 1, 1, 0})
+         : f == A_YUV420            ? Slot{s, 1, s ? 1 : 0, s, 0}
+                                    : Slot{s, 1, 0, s, 0};
+}
+// the subsampling of colour channel c
+constexpr int chan_shift(int f, int c) { return a_is420(f) && c > 0 ? 1 : 0; }
+
+// A sanitised row: what it paints, clipped to the frame (all values in 0 .. W resp. 0 .. H)
+struct Mark {
+  int kind;
+  int x0, y0, x1, y1;      // the area it touches: rectangle ^ frame (pixelate: grown to the cell grid first)
+  int ix0, iy0, ix1, iy1;  // BOX: the inner rectangle that stays as it is (empty: all 0)
+  int cell;                // PIXELATE
+  u32 colour;
+};
+
+__device__ __forceinline__ void load_mark(const vali_mark* marks, int i, int (&r)[8]) {
+  const uint4 a = load16_u((const uint8_t*)(marks + i)), b = load16_u((const uint8_t*)(marks + i) + 16);
+  r[0] = (int)a.x, r[1] = (int)a.y, r[2] = (int)a.z, r[3] = (int)a.w;
+  r[4] = (int)b.x, r[5] = (int)b.y, r[6] = (int)b.z, r[7] = (int)b.w;
+}
+
+__device__ __forceinline__ int clampi(long long v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : (int)v; }
+
+// false: the row is skipped (the rules of include/vali_hip.h; the frame index is the caller's to check)
+__device__ __forceinline__ bool resolve_mark(const int (&r)[8], int W, int H, bool is420, Mark& m) {
+  const int kind = r[5], arg = r[6];
+  if (kind < VALI_MARK_BOX || kind > VALI_MARK_PIXELATE || r[3] < 1 || r[4] < 1)
+    return false;
+  if (kind == VALI_MARK_BOX && arg < 1)
+    return false;
+  if (kind == VALI_MARK_PIXELATE && arg != 4 && arg != 8 && arg != 16 && arg != 32)
+    return false;
+  // 64 bits: x + w and x + t overflow int32
+  long long x0 = r[1], y0 = r[2], x1 = x0 + r[3], y1 = y0 + r[4], t = arg;
+  if (is420) {
+    x0 &= ~1ll, y0 &= ~1ll, x1 = (x1 + 1) & ~1ll, y1 = (y1 + 1) & ~1ll, t = (t + 1) & ~1ll;
+  }
+  if (x0 >= W || y0 >= H || x1 <= 0 || y1 <= 0)
+    return false;
+  m.kind = kind;
+  m.colour = (u32)r[7];
+  m.x0 = clampi(x0, 0, W), m.y0 = clampi(y0, 0, H), m.x1 = clampi(x1, 0, W), m.y1 = clampi(y1, 0, H);
+  m.ix0 = m.iy0 = m.ix1 = m.iy1 = 0;
+  m.cell = 0;
+  if (kind == VALI_MARK_PIXELATE) {
+    const int s = arg;
+    m.cell = s;
+    m.x0 = m.x0 / s * s, m.y0 = m.y0 / s * s;
+    m.x1 = min((m.x1 + s - 1) / s * s, W), m.y1 = min((m.y1 + s - 1) / s * s, H);
+  } else if (kind == VALI_MARK_BOX) {
+    const int ix0 = clampi(x0 + t, 0, W), ix1 = clampi(x1 - t, 0, W);
+    const int iy0 = clampi(y0 + t, 0, H), iy1 = clampi(y1 - t, 0, H);
+    if (ix0 < ix1 && iy0 < iy1)
+      m.ix0 = ix0, m.ix1 = ix1, m.iy0 = iy0, m.iy1 = iy1;
+  }
+  return true;
+}
+
+// does the mark paint inside the tile [tx0, tx0 + 64) x [ty0, ty0 + 64) of a W x H frame
+__device__ __forceinline__ bool mark_meets_tile(const Mark& m, int tx0, int ty0, int W, int H) {
+  const int tx1 = min(tx0 + kTile, W), ty1 = min(ty0 + kTile, H);
+  if (m.x0 >= tx1 || m.x1 <= tx0 || m.y0 >= ty1 || m.y1 <= ty0)
+    return false;
+  // a tile wholly inside an outline's inner rectangle
+  return !(tx0 >= m.ix0 && tx1 <= m.ix1 && ty0 >= m.iy0 && ty1 <= m.iy1);
+}
+
+// Ordered compaction over the workgroup: the flagged lanes' values go to out[base ...] in lane order; returns the new
+// end.  Every lane of the workgroup calls it.
+__device__ __forceinline__ int compact_put(bool flag, int value, uint16_t* out, int base, int* wtot) {
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const unsigned long long b = __ballot(flag);
+  const int before = __popcll(b & ((1ull << lane) - 1ull));
+  if (lane == 0)
+    wtot[wave] = __popcll(b);
+  __syncthreads();
+  int off = base, tot = 0;
+#pragma unroll
+  for (int w = 0; w < kWavesPerBlock; ++w) {
+    const int c = wtot[w];
+    off += w < wave ? c : 0;
+    tot += c;
+  }
+  if (flag)
+    out[off + before] = (uint16_t)value;
+  __syncthreads();
+  return base + tot;
+}
+
+// ---- launch 1: the rows of each frame ---------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kBlock) k_annotate_bin(const vali_surface* __restrict__ d_frames,
+                                                         const vali_mark* __restrict__ marks, int m, int is420,
+                                                         uint8_t* __restrict__ ws) {
+  __shared__ int wtot[kWavesPerBlock];
+  const int f = blockIdx.x;
+  const int W = d_frames[f].width, H = d_frames[f].height;
+  uint8_t* bin = ws + (size_t)f * kBinBytes;
+  uint16_t* list = (uint16_t*)(bin + 16);
+  int total = 0;
+  for (int base = 0; base < m; base += kBlock) {
+    const int i = base + (int)threadIdx.x;
+    bool flag = false;
+    if (i < m) {
+      int r[8];
+      load_mark(marks, i, r);
+      Mark mk;
+      flag = r[0] == f && resolve_mark(r, W, H, is420 != 0, mk);
+    }
+    total = compact_put(flag, i, list, total, wtot);
+  }
+  if (threadIdx.x == 0)
+    *(u32*)bin = (u32)total;
+}
+
+// ---- launch 2: the tiles ----------------------------------------------------------------------------------------------
+struct AnnArgs {
+  const vali_surface* d_frames;
+  const vali_mark* marks;
+  const uint8_t* ws;
+  float m[3][4];  // rgb2yuv rows (YUV formats)
+};
+
+// what a lane keeps of one of its pieces
+struct Piece {
+  uint8_t* p;  // where it lives
+  int n;       // bytes of it inside the image area: 0 (none: the lane has no such piece) .. 16
+  int y;       // its row, in samples of its plane
+  int bx;      // its first byte within the plane's row
+  int lbx;     // ... and within the tile's row
+};
+
+// t / 255 for 0 <= t < 65536
+__device__ __forceinline__ u32 div255(u32 t) { return (t * 0x8081u) >> 23; }
+
+__device__ __forceinline__ float dot_rgb(const float (&m)[4], float r, float g, float b) {
+  return __builtin_fmaf(m[2], b, __builtin_fmaf(m[1], g, __builtin_fmaf(m[0], r, m[3])));
+}
+
+// FILL and BOX on one piece: lane-local
+template <int FMT, int S>
+__device__ __forceinline__ void blend_piece(const Piece& pc, const Mark& mk, const u32 (&col)[3], u32 alpha, u32 (&w)[4]) {
+  constexpr Slot sl = slot_of(FMT, S);
+  constexpr int nc = sl.nc, sh = sl.sh;
+  if (pc.n <= 0 || pc.y < (mk.y0 >> sh) || pc.y >= (mk.y1 >> sh))
+    return;
+  const int lo = (mk.x0 >> sh) * nc - pc.bx, hi = (mk.x1 >> sh) * nc - pc.bx;
+  if (lo >= 16 || hi <= 0)
+    return;
+  const bool inner_row = pc.y >= (mk.iy0 >> sh) && pc.y < (mk.iy1 >> sh);
+  const int ilo = inner_row ? (mk.ix0 >> sh) * nc - pc.bx : 0, ihi = inner_row ? (mk.ix1 >> sh) * nc - pc.bx : 0;
+  // the colour of byte b is c[b % nc]: packed RGB pieces start at any of the three channels
+  u32 c[3];
+  if constexpr (nc == 3) {
+    // (shifts of one packed word: a select chain over col[] becomes a table in scratch memory)
+    const u32 ch0 = (u32)pc.lbx % 3u;
+    const unsigned long long pk = (unsigned long long)(col[0] | col[1] << 8 | col[2] << 16 | col[0] << 24) |
+                                  (unsigned long long)col[1] << 32;
+    c[0] = (u32)(pk >> (8u * ch0)) & 0xffu, c[1] = (u32)(pk >> (8u * ch0 + 8u)) & 0xffu;
+    c[2] = (u32)(pk >> (8u * ch0 + 16u)) & 0xffu;
+  } else if constexpr (nc == 2) {
+    c[0] = col[sl.c0], c[1] = col[sl.c0 + 1], c[2] = 0;
+  } else {
+    c[0] = col[sl.c0], c[1] = 0, c[2] = 0;
+  }
+  const u32 ia = 255u - alpha;
+#pragma unroll
+  for (int b = 0; b < 16; ++b) {
+    const bool inside = b >= lo && b < hi && !(b >= ilo && b < ihi);
+    const u32 v = (w[b / 4] >> (8 * (b % 4))) & 0xffu;
+    const u32 nv = div255(v * ia + c[b % nc] * alpha + 127u);
+    if (inside)
+      w[b / 4] = (w[b / 4] & ~(0xffu << (8 * (b % 4)))) | (nv << (8 * (b % 4)));
+  }
+}
+
+// PIXELATE on one piece: ADD = the piece's samples go into the cell sums, !ADD = the cell means come back
+template <int FMT, int S, bool ADD>
+__device__ __forceinline__ void pixelate_piece(const Piece& pc, const Mark& mk, int lcell, u32* sums, u32 (&w)[4]) {
+  constexpr Slot sl = slot_of(FMT, S);
+  constexpr int nc = sl.nc, sh = sl.sh;
+  if (pc.n <= 0 || pc.y < (mk.y0 >> sh) || pc.y >= (mk.y1 >> sh))
+    return;
+  const int lo = (mk.x0 >> sh) * nc - pc.bx, hi = (mk.x1 >> sh) * nc - pc.bx;
+  if (lo >= 16 || hi <= 0)
+    return;
+  const int lcs = lcell - sh;                                     // log2 of the cell in this plane's samples
+  const int rowkey = ((pc.y & ((kTile >> sh) - 1)) >> lcs) * 16;  // the tile starts on a multiple of its side
+  const u32 ch0 = nc == 3 ? (u32)pc.lbx % 3u : 0u;
+#pragma unroll
+  for (int k = 0; k < nc; ++k) {
+    const int ch = nc == 3 ? (int)((ch0 + (u32)k) % 3u) : sl.c0 + k;
+    int run = -1;  // the cell whose samples `acc` holds
+    u32 acc = 0;
+#pragma unroll
+    for (int b = k; b < 16; b += nc) {
+      if (b >= lo && b < hi) {
+        const int cx = (int)((u32)(pc.lbx + b) / (u32)nc) >> lcs;
+        u32* cell = sums + ((rowkey + cx) * 3 + ch);
+        if constexpr (ADD) {
+          if (cx != run) {
+            if (run >= 0)
+              atomicAdd(sums + ((rowkey + run) * 3 + ch), acc);
+            run = cx, acc = 0;
+          }
+          acc += (w[b / 4] >> (8 * (b % 4))) & 0xffu;
+        } else {
+          w[b / 4] = (w[b / 4] & ~(0xffu << (8 * (b % 4)))) | (*cell << (8 * (b % 4)));
+        }
+      }
+    }
+    if constexpr (ADD)
+      if (run >= 0)
+        atomicAdd(sums + ((rowkey + run) * 3 + ch), acc);
+  }
+}
+
+// a lane's piece S of the tile at (tx0, ty0): where it is, how much of it the image holds, and its bytes
+template <int FMT, int S>
+__device__ __forceinline__ void load_piece(const vali_surface* d, int tid, int tx0, int ty0, int W, int H, Piece& pc,
+                                           u32 (&cur)[4], u32 (&orig)[4]) {
+  constexpr Slot sl = slot_of(FMT, S);
+  constexpr int rows = kTile >> sl.sh, row_pieces = rows * sl.nc / 16;
+  const int k = tid + sl.first;
+  const int prow = k / row_pieces, pcol = k - prow * row_pieces;
+  pc.y = (ty0 >> sl.sh) + prow;
+  pc.lbx = pcol * 16;
+  pc.bx = (tx0 >> sl.sh) * sl.nc + pc.lbx;
+  const int row_bytes = (W >> sl.sh) * sl.nc;
+  pc.n = (k < row_pieces * rows && pc.y < (H >> sl.sh)) ? max(min(row_bytes - pc.bx, 16), 0) : 0;
+  pc.p = (uint8_t*)d->plane[sl.plane] + (size_t)pc.y * (size_t)d->pitch[sl.plane] + pc.bx;
+  uint4 v = make_uint4(0u, 0u, 0u, 0u);
+  if (pc.n > 0)
+    v = load16_n(pc.p, pc.n);
+  cur[0] = orig[0] = v.x, cur[1] = orig[1] = v.y, cur[2] = orig[2] = v.z, cur[3] = orig[3] = v.w;
+}
+
+__device__ __forceinline__ void store_piece(const Piece& pc, const u32 (&cur)[4], const u32 (&orig)[4]) {
+  const bool changed = ((cur[0] ^ orig[0]) | (cur[1] ^ orig[1]) | (cur[2] ^ orig[2]) | (cur[3] ^ orig[3])) != 0u;
+  if (pc.n > 0 && changed)
+    store16_n(pc.p, make_uint4(cur[0], cur[1], cur[2], cur[3]), pc.n);
+}
+
+// once per slot of the format: a slot's layout is a template argument, so the slots are spelled out, not looped over
+#define VALI_SLOTS(CALL)   \
+  {                        \
+    CALL(0)                \
+    CALL(1)                \
+    if constexpr (NS > 2) { \
+      CALL(2)              \
+    }                      \
+  }
+
+template <int FMT>
+__global__ void __launch_bounds__(kBlock) k_annotate(const AnnArgs a) {
+  __shared__ uint16_t hits[kMaxMarks];
+  __shared__ u32 sums[kCells];
+  __shared__ int wtot[kWavesPerBlock];
+  constexpr int NS = nslots(FMT);
+  constexpr bool is420 = a_is420(FMT);
+
+  const int f = blockIdx.y;
+  const vali_surface* d = a.d_frames + f;
+  const int W = d->width, H = d->height;
+  const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile;
+  if ((int)blockIdx.x >= tiles_x * tiles_y)
+    return;  // the grid is sized for the batch's largest frame
+  const uint8_t* bin = a.ws + (size_t)f * kBinBytes;
+  const int count = (int)*(const u32*)bin;
+  if (count == 0)
+    return;  // no row draws on this frame
+  const uint16_t* list = (const uint16_t*)(bin + 16);
+  const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
+  const int tx0 = tx * kTile, ty0 = ty * kTile;
+  const int tid = threadIdx.x;
+
+  // the frame's rows that meet this tile, in row order
+  int nh = 0;
+  for (int base = 0; base < count; base += kBlock) {
+    const int i = base + tid;
+    bool flag = false;
+    int idx = 0;
+    if (i < count) {
+      idx = list[i];
+      int r[8];
+      load_mark(a.marks, idx, r);
+      Mark mk;
+      flag = resolve_mark(r, W, H, is420, mk) && mark_meets_tile(mk, tx0, ty0, W, H);
+    }
+    nh = compact_put(flag, idx, hits, nh, wtot);
+  }
+  if (nh == 0)
+    return;
+
+  // the lane's pieces
+  Piece pc[NS];
+  u32 cur[NS][4], orig[NS][4];
+#define VALI_SLOT(S) load_piece<FMT, S>(d, tid, tx0, ty0, W, H, pc[S], cur[S], orig[S]);
+  VALI_SLOTS(VALI_SLOT)
+#undef VALI_SLOT
+
+  for (int h = 0; h < nh; ++h) {
+    const int idx = __builtin_amdgcn_readfirstlane((int)hits[h]);
+    int r[8];
+    load_mark(a.marks, idx, r);
+    Mark mk;
+    if (!resolve_mark(r, W, H, is420, mk))
+      continue;
+    if (mk.kind == VALI_MARK_PIXELATE) {
+      const int lcell = 31 - __clz(mk.cell);
+      for (int j = tid; j < kCells; j += kBlock)
+        sums[j] = 0;
+      __syncthreads();
+#define VALI_SLOT(S) pixelate_piece<FMT, S, true>(pc[S], mk, lcell, sums, cur[S]);
+      VALI_SLOTS(VALI_SLOT)
+#undef VALI_SLOT
+      __syncthreads();
+      // sums -> rounded means over (cell ^ frame); entry j = (cell row * 16 + cell column) * 3 + channel
+      for (int j = tid; j < kCells; j += kBlock) {
+        const u32 sum = sums[j];
+        if (sum) {
+          const int ch = j % 3, cell = j / 3, cxl = cell & 15, cyl = cell >> 4;
+          const int sh = a_is420(FMT) && ch > 0 ? 1 : 0;
+          const int cs = mk.cell >> sh;
+          const int px0 = (tx0 >> sh) + cxl * cs, py0 = (ty0 >> sh) + cyl * cs;
+          const int cw = min(px0 + cs, W >> sh) - px0, chh = min(py0 + cs, H >> sh) - py0;
+          const u32 cnt = (u32)(cw * chh);
+          sums[j] = (sum + cnt / 2u) / cnt;  // sum > 0: the cell holds a sample of the frame, cnt >= 1
+        }
+      }
+      __syncthreads();
+#define VALI_SLOT(S) pixelate_piece<FMT, S, false>(pc[S], mk, lcell, sums, cur[S]);
+      VALI_SLOTS(VALI_SLOT)
+#undef VALI_SLOT
+      __syncthreads();  // the next pixelate mark clears the sums
+    } else {
+      const u32 alpha = mk.colour >> 24;
+      const u32 cr = (mk.colour >> 16) & 0xffu, cg = (mk.colour >> 8) & 0xffu, cb = mk.colour & 0xffu;
+      u32 col[3];
+      if constexpr (a_isyuv(FMT)) {
+        const float fr = (float)cr, fg = (float)cg, fb = (float)cb;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          col[k] = quantize_u8(dot_rgb(a.m[k], fr, fg, fb));
+      } else if constexpr (FMT == A_BGR) {
+        col[0] = cb, col[1] = cg, col[2] = cr;
+      } else {
+        col[0] = cr, col[1] = cg, col[2] = cb;
+      }
+#define VALI_SLOT(S) blend_piece<FMT, S>(pc[S], mk, col, alpha, cur[S]);
+      VALI_SLOTS(VALI_SLOT)
+#undef VALI_SLOT
+    }
+  }
+
+  // only what a mark changed goes back
+#define VALI_SLOT(S) store_piece(pc[S], cur[S], orig[S]);
+  VALI_SLOTS(VALI_SLOT)
+#undef VALI_SLOT
+}
+#undef VALI_SLOTS
+
+int ann_format(int format) {
+  switch (format) {
+  case VALI_FMT_NV12: return A_NV12;
+  case VALI_FMT_YUV420: return A_YUV420;
+  case VALI_FMT_YUV444: return A_YUV444;
+  case VALI_FMT_RGB: return A_RGB;
+  case VALI_FMT_BGR: return A_BGR;
+  case VALI_FMT_RGB_PLANAR: return A_RGBP;
+  default: return -1;
+  }
+}
+
+// the rules for the frames of a batch; *max_tiles: the tiles of the largest one
+int check_frames(const char* who, int n, const vali_surface* frames, int format, int* max_tiles) {
+  const int fmt = ann_format(format);
+  if (fmt < 0)
+    return fail(VALI_ERR_UNSUPPORTED, "%s: format %d (NV12, YUV420, YUV444, RGB, BGR, RGB_PLANAR)", who, format);
+  const int planes = (fmt == A_RGB || fmt == A_BGR) ? 1 : fmt == A_NV12 ? 2 : 3;
+  int tiles = 0;
+  for (int i = 0; i < n; ++i) {
+    const vali_surface& s = frames[i];
+    if (s.format != format)
+      return fail(VALI_ERR_INVALID_ARG, "%s: frame %d has format %d, the batch %d: one format per batch", who, i,
+                  s.format, format);
+    if (s.width < 1 || s.height < 1 || s.width > 65535 || s.height > 65535)
+      return fail(VALI_ERR_INVALID_ARG, "%s: frame %d: size %dx%d outside 1..65535", who, i, s.width, s.height);
+    if (!subsampled_sizes_ok(format, s.width, s.height))
+      return fail(VALI_ERR_INVALID_ARG, "%s: frame %d: 4:2:0 formats need an even width and height, got %dx%d", who, i,
+                  s.width, s.height);
+    for (int p = 0; p < planes; ++p) {
+      const Slot sl = slot_of(fmt, (fmt == A_RGB || fmt == A_BGR) ? 0 : p);
+      if (!s.plane[p])
+        return fail(VALI_ERR_INVALID_ARG, "%s: frame %d: plane %d is null", who, i, p);
+      if (s.pitch[p] < (s.width >> sl.sh) * sl.nc)
+        return fail(VALI_ERR_INVALID_ARG, "%s: frame %d: pitch %d of plane %d is shorter than a row", who, i, s.pitch[p], p);
+    }
+    const int t = ((s.width + kTile - 1) / kTile) * ((s.height + kTile - 1) / kTile);
+    tiles = t > tiles ? t : tiles;
+  }
+  *max_tiles = tiles;
+  return VALI_OK;
+}
+
+} // namespace
+} // namespace vali
+
+using namespace vali;
+
+extern "C" {
+
+int vali_annotate_workspace_size(int n, const vali_surface* frames, size_t* bytes) {
+  VALI_REQUIRE(bytes, "null argument");
+  VALI_REQUIRE(n >= 0 && n <= 65535, "n outside 0..65535");
+  VALI_REQUIRE(frames || n == 0, "null frames");
+  if (n > 0) {
+    int tiles = 0;
+    const int rc = check_frames(__func__, n, frames, frames[0].format, &tiles);
+    if (rc != VALI_OK)
+      return rc;
+  }
+  *bytes = (size_t)n * kBinBytes;
+  return VALI_OK;
+}
+
+int vali_annotate_batch(const vali_surface* frames, const vali_surface* d_frames, int n, int format,
+                        const vali_mark* d_marks, int m, const vali_cvt_params* params, void* workspace,
+                        size_t ws_bytes, vali_stream_t stream) {
+  VALI_REQUIRE(n >= 0 && n <= 65535, "n outside 0..65535");
+  VALI_REQUIRE(m >= 0 && m <= kMaxMarks, "m outside 0..4096");
+  VALI_REQUIRE((frames && d_frames) || n == 0, "null frames");
+  VALI_REQUIRE(d_marks || m == 0, "null marks");
+  VALI_REQUIRE(((uintptr_t)d_marks & 3u) == 0, "marks are not 4-byte aligned");
+  int tiles = 0;
+  const int rc = check_frames(__func__, n, frames, format, &tiles);
+  if (rc != VALI_OK)
+    return rc;
+  const int fmt = ann_format(format);
+  VALI_REQUIRE(params || !a_isyuv(fmt), "a YUV format needs params (rgb2yuv)");
+  VALI_REQUIRE(workspace || n == 0, "null workspace");
+  VALI_REQUIRE(((uintptr_t)workspace & 15u) == 0, "the workspace is not 16-byte aligned");
+  VALI_REQUIRE(ws_bytes >= (size_t)n * kBinBytes, "the workspace is smaller than vali_annotate_workspace_size");
+  if (n == 0 || m == 0)
+    return VALI_OK;
+
+  AnnArgs a = {};
+  a.d_frames = d_frames;
+  a.marks = d_marks;
+  a.ws = (const uint8_t*)workspace;
+  if (a_isyuv(fmt))
+    for (int k = 0; k < 3; ++k)
+      for (int j = 0; j < 4; ++j)
+        a.m[k][j] = params->rgb2yuv[k][j];
+
+  hipStream_t s = as_stream(stream);
+  VALI_ENTRY(s);
+  hipLaunchKernelGGL(k_annotate_bin, dim3(n), dim3(kBlock), 0, s, d_frames, d_marks, m, a_is420(fmt) ? 1 : 0,
+                     (uint8_t*)workspace);
+  VALI_LAUNCH_CHECK();
+  const dim3 grid(tiles, n);
+  switch (fmt) {
+  case A_NV12: hipLaunchKernelGGL(k_annotate<A_NV12>, grid, dim3(kBlock), 0, s, a); break;
+  case A_YUV420: hipLaunchKernelGGL(k_annotate<A_YUV420>, grid, dim3(kBlock), 0, s, a); break;
+  case A_YUV444: hipLaunchKernelGGL(k_annotate<A_YUV444>, grid, dim3(kBlock), 0, s, a); break;
+  case A_RGB: hipLaunchKernelGGL(k_annotate<A_RGB>, grid, dim3(kBlock), 0, s, a); break;
+  case A_BGR: hipLaunchKernelGGL(k_annotate<A_BGR>, grid, dim3(kBlock), 0, s, a); break;
+  default: hipLaunchKernelGGL(k_annotate<A_RGBP>, grid, dim3(kBlock), 0, s, a); break;
+  }
+  VALI_LAUNCH_CHECK();
+  return VALI_OK;
+}
+
+} // extern "C"

@@ -683,6 +683,27 @@ PYBIND11_MODULE(_vali_shim, m) {
         },
         py::call_guard<py::gil_scoped_release>());
 
+  // marks on frames: descs = the host copy of the descriptors in d_frames; d_marks = device rows of 8 int32
+  m.def("annotate_workspace_size", [](const std::vector<SurfaceDesc>& descs) {
+    std::vector<vali_surface> host(descs.size());
+    for (size_t i = 0; i < descs.size(); ++i)
+      host[i] = descs[i].s;
+    size_t bytes = 0;
+    check(vali_annotate_workspace_size((int)host.size(), host.data(), &bytes), "vali_annotate_workspace_size");
+    return bytes;
+  });
+  m.def("annotate_batch",
+        [](const std::vector<SurfaceDesc>& descs, uintptr_t d_frames, int format, uintptr_t d_marks, int m,
+           const CvtParams* p, uintptr_t workspace, size_t ws_bytes, uintptr_t stream) {
+          std::vector<vali_surface> host(descs.size());
+          for (size_t i = 0; i < descs.size(); ++i)
+            host[i] = descs[i].s;
+          py::gil_scoped_release nogil;
+          return vali_annotate_batch(host.data(), (const vali_surface*)P(d_frames), (int)host.size(), format,
+                                     (const vali_mark*)P(d_marks), m, p ? &p->p : nullptr, P(workspace), ws_bytes,
+                                     P(stream));
+        });
+
   // ---- JPEG decoder: host-side parser and sizes, then the batched decoder --------------------------------------
   py::class_<JpegInfo>(m, "JpegInfo")
       .def_property_readonly("width", [](const JpegInfo& j) { return j.f.width; })

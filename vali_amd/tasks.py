@@ -1318,6 +1318,218 @@ class PySurfacePostprocessor(_SurfaceTask):
         return r
 
 
+# ---- PySurfaceAnnotator: outlines, fills and pixelation from GPU-held marks ------------------------------
+MARK_NONE, MARK_BOX, MARK_FILL, MARK_PIXELATE = 0, 1, 2, 3
+MAX_MARKS = 4096
+_PIXELATE_CELLS = (4, 8, 16, 32)
+
+
+def pack_colour(r: int, g: int, b: int, a: int = 255) -> int:
+    """the int32 a mark row carries as its colour: bits a << 24 | r << 16 | g << 8 | b (negative for a >= 128)"""
+    r, g, b, a = (operator.index(v) for v in (r, g, b, a))
+    if any(not 0 <= v <= 255 for v in (r, g, b, a)):
+        raise ValueError("pack_colour: r, g, b, a in 0..255")
+    v = a << 24 | r << 16 | g << 8 | b
+    return v - (1 << 32) if v >= 1 << 31 else v
+
+
+def _host_marks(rows, sizes, is420):
+    """a host sequence of (frame, x, y, w, h, kind, arg, colour): the rules the kernel applies to a device tensor, with
+    ValueErrors where the kernel would skip the row -- except kind 0 and unknown kinds, which are skipped here too"""
+    out = []
+    for i, row in enumerate(rows):
+        try:
+            r = tuple(operator.index(v) for v in row)
+        except TypeError:
+            raise ValueError(f"marks: row {i} must be 8 integers (frame, x, y, w, h, kind, arg, colour)") from None
+        if len(r) != 8:
+            raise ValueError(f"marks: row {i} has {len(r)} values, need 8 (frame, x, y, w, h, kind, arg, colour)")
+        if any(not -(1 << 31) <= v < (1 << 31) for v in r):
+            raise ValueError(f"marks: row {i}: every value must fit an int32 (colours: pack_colour)")
+        frame, x, y, w, h, kind, arg, _ = r
+        out.append(r)
+        if kind not in (MARK_BOX, MARK_FILL, MARK_PIXELATE):
+            continue
+        if not 0 <= frame < len(sizes):
+            raise ValueError(f"marks: row {i}: frame {frame} is outside 0..{len(sizes) - 1}")
+        if w < 1 or h < 1:
+            raise ValueError(f"marks: row {i}: the rectangle is {w}x{h}; width and height must be at least 1")
+        if kind == MARK_BOX and arg < 1:
+            raise ValueError(f"marks: row {i}: MARK_BOX needs a thickness of at least 1, got {arg}")
+        if kind == MARK_PIXELATE and arg not in _PIXELATE_CELLS:
+            raise ValueError(f"marks: row {i}: MARK_PIXELATE needs a cell of 4, 8, 16 or 32, got {arg}")
+        x0, y0, x1, y1 = x, y, x + w, y + h
+        if is420:
+            x0, y0, x1, y1 = x0 & ~1, y0 & ~1, (x1 + 1) & ~1, (y1 + 1) & ~1
+        fw, fh = sizes[frame]
+        if x0 >= fw or y0 >= fh or x1 <= 0 or y1 <= 0:
+            raise ValueError(f"marks: row {i}: the rectangle ({x}, {y}, {w}, {h}) does not meet frame {frame} ({fw}x{fh})")
+    return out
+
+
+def _device_marks(marks, gpu_id):
+    """(device pointer, rows, holder) of an int32 (M, 8) contiguous device tensor: _device_rects' checks; the values are
+    the kernel's to sanitise"""
+    if hasattr(marks, "__cuda_array_interface__"):
+        cai = marks.__cuda_array_interface__
+        shape = tuple(int(v) for v in cai["shape"])
+        strides = cai.get("strides")
+        if cai["typestr"] not in ("<i4", "|i4") or len(shape) != 2 or shape[1] != 8:
+            raise ValueError(f"marks: need an int32 tensor of shape (M, 8), got {cai['typestr']} {shape}")
+        if strides is not None and (int(strides[1]) != 4 or (shape[0] > 1 and int(strides[0]) != 32)):
+            raise ValueError("marks: the tensor must be contiguous")
+        ptr, holder = int(cai["data"][0]), marks
+        dev = getattr(marks, "device", None)
+        if getattr(dev, "type", "cuda") != "cuda":
+            raise ValueError("marks: the tensor must live on the GPU")
+        device = dev.index if dev is not None and dev.index is not None else (shim.ptr_device(ptr) if ptr else gpu_id)
+    elif hasattr(marks, "__dlpack__"):
+        info, holder = shim.dlpack_import(marks.__dlpack__())
+        shape, strides = tuple(info["shape"]), tuple(info["strides"])
+        if info["code"] != 0 or info["bits"] != 32 or info["lanes"] != 1 or len(shape) != 2 or shape[1] != 8:
+            raise ValueError(f"marks: need an int32 tensor of shape (M, 8), got shape {shape}")
+        if strides[1] != 1 or (shape[0] > 1 and strides[0] != 8):
+            raise ValueError("marks: the tensor must be contiguous")
+        if info["device_type"] not in (int(DLDeviceType.kDLROCM), int(DLDeviceType.kDLCUDA)):
+            raise ValueError("marks: the tensor must live on the GPU")
+        ptr, device = int(info["ptr"]), int(info["device_id"])
+    else:
+        raise ValueError("marks: a device tensor with __cuda_array_interface__ or __dlpack__, or a sequence of 8-tuples")
+    if device != gpu_id:
+        raise ValueError(f"marks: the tensor is on device {device}, the batch on {gpu_id}")
+    if shape[0] > MAX_MARKS:
+        raise ValueError(f"marks: {shape[0]} rows; at most {MAX_MARKS} per call")
+    return ptr, shape[0], holder
+
+
+class AnnotateBatch:
+    """The frames PySurfaceAnnotator.RunBatch draws on: N >= 0 surfaces of one format, any sizes; descriptors, the
+    kernel's workspace and a staging buffer for host-side marks are set up once (PySurfaceAnnotator.PrepareBatch).
+    Keeps the surfaces alive."""
+
+    def __init__(self, gpu_id: int, stream: int, frames: Sequence[Surface]):
+        frames = list(frames)
+        fmt = None
+        for i, d in enumerate(frames):
+            if d is None or d.IsEmpty:
+                raise ValueError(f"AnnotateBatch: surface {i} is empty")
+            if d.Format not in PySurfaceAnnotator._FORMATS:
+                raise ValueError(f"AnnotateBatch: surface {i} has format {d.Format!r}; supported: "
+                                 f"{', '.join(f.name for f in PySurfaceAnnotator._FORMATS)}")
+            if fmt is not None and d.Format != fmt:
+                raise ValueError(f"AnnotateBatch: surface {i} has format {d.Format!r}, surface 0 {fmt!r}: one format per batch")
+            fmt = d.Format
+            if fmt in (F.NV12, F.YUV420) and (d.Width | d.Height) & 1:
+                raise ValueError(f"AnnotateBatch: surface {i}: {fmt.name} is 4:2:0 and needs an even width and height, "
+                                 f"got {d.Width}x{d.Height}")
+            dev = getattr(d, "DeviceId", gpu_id)
+            if dev != gpu_id:
+                raise ValueError(f"AnnotateBatch: surface {i} is on device {dev}, the task on {gpu_id}")
+        if frames and is_capturing(gpu_id, stream):
+            raise RuntimeError("AnnotateBatch: cannot be created while the stream is capturing -- PrepareBatch() "
+                               "before the StreamCapture block and Keep() the batch with the capture")
+        self.gpu_id = gpu_id
+        self._stream = stream
+        self.n = len(frames)
+        self.format = fmt
+        self.sizes = [(d.Width, d.Height) for d in frames]
+        self.descs = [d.desc() for d in frames]
+        self._keep = frames
+        self._marks_keep = None
+        self.d_frames = self.d_ws = self.d_marks = 0
+        self.ws_bytes = 0
+        if frames:
+            self.ws_bytes = shim.annotate_workspace_size(self.descs)
+            self.d_frames = shim.descs_upload(gpu_id, self.descs, stream)
+            self.d_ws = shim.mem_alloc(gpu_id, self.ws_bytes)
+            self.d_marks = shim.mem_alloc(gpu_id, MAX_MARKS * 32)
+
+    def __len__(self):
+        return self.n
+
+    def __del__(self):
+        if getattr(self, "d_frames", 0):
+            try:    # a launch issued on the batch's stream may still be reading the arrays
+                shim.stream_sync(self.gpu_id, self._stream)
+            except Exception:
+                pass
+        for name in ("d_frames", "d_ws", "d_marks"):
+            p = getattr(self, name, 0)
+            if p:
+                try:
+                    shim.mem_free(self.gpu_id, p)
+                except Exception:
+                    pass
+                setattr(self, name, 0)
+
+
+class PySurfaceAnnotator(_SurfaceTask):
+    """Outlines (MARK_BOX), filled or translucent regions (MARK_FILL) and pixelation (MARK_PIXELATE) drawn IN PLACE onto a
+    batch of NV12, YUV420, YUV444, RGB, BGR or RGB_PLANAR frames of any sizes, in two launches whatever the marks
+    (vali_annotate_batch): the step between a detector's output and PyNvEncoder or the JPEG encoder.
+
+    `marks`: an int32 (M, 8) contiguous GPU tensor (`__dlpack__` or `__cuda_array_interface__`), M <= 4096, rows
+    (frame, x, y, w, h, kind, arg, colour) -- its VALUES are never read on the host, so a detector's boxes are drawn
+    without a device-to-host synchronisation; a row is skipped when its kind is MARK_NONE or unknown, its frame is outside
+    the batch, w < 1 or h < 1, arg is invalid for the kind (BOX: thickness >= 1; PIXELATE: cell 4, 8, 16 or 32) or the
+    rectangle does not meet its frame.  Or a host sequence of such 8-tuples, checked here (the last four are ValueErrors)
+    and uploaded with one blocking copy on the task's stream.  Marks are applied in row order.  `colour`: pack_colour().
+    The definition, sample for sample, is in include/vali_hip.h; the reference has no such task.
+
+    `cc_ctx` picks the RGB -> YUV matrix for colours on YUV frames exactly as PySurfacePostprocessor.Matrix does; an
+    unsupported one gives (False, UNSUPPORTED_FMT_CONV_PARAMS) and nothing is launched.  Ignored for RGB formats.
+    """
+
+    _FORMATS = (F.NV12, F.YUV420, F.YUV444, F.RGB, F.BGR, F.RGB_PLANAR)
+
+    @staticmethod
+    def SupportedFormats() -> List[PixelFormat]:
+        return list(PySurfaceAnnotator._FORMATS)
+
+    def PrepareBatch(self, frames: Sequence[Surface]) -> AnnotateBatch:
+        return AnnotateBatch(self._gpu_id, self._stream, frames)
+
+    def RunBatchAsync(self, batch: AnnotateBatch, marks, cc_ctx=None) -> Tuple[bool, TaskExecInfo]:
+        if not isinstance(batch, AnnotateBatch):
+            raise ValueError("RunBatch: pass an AnnotateBatch (PrepareBatch)")
+        if hasattr(marks, "__cuda_array_interface__") or hasattr(marks, "__dlpack__"):
+            ptr, m, batch._marks_keep = _device_marks(marks, self._gpu_id)
+            host = None
+        else:
+            try:
+                rows = list(marks)
+            except TypeError:
+                raise ValueError("marks: a device tensor with __cuda_array_interface__ or __dlpack__, or a sequence of "
+                                 "8-tuples") from None
+            if len(rows) > MAX_MARKS:
+                raise ValueError(f"marks: {len(rows)} rows; at most {MAX_MARKS} per call")
+            host = _host_marks(rows, batch.sizes, batch.format in (F.NV12, F.YUV420))
+            ptr, m = batch.d_marks, len(host)
+        params = None
+        if batch.format in (F.NV12, F.YUV420, F.YUV444):
+            mat = PySurfacePostprocessor.Matrix(cc_ctx)
+            if mat is None:
+                return _S_UNSUPP_CC.success, _S_UNSUPP_CC.info
+            params = _params(rgb2yuv=mat)
+        if batch.n == 0 or m == 0:
+            return _OK_PAIR
+        if host is not None:
+            import array
+
+            buf = array.array("i", [v for r in host for v in r])
+            src, nbytes = buf.buffer_info()[0], 32 * m
+            shim.memcpy2d_async(self._gpu_id, ptr, nbytes, src, nbytes, nbytes, 1, 0, self._stream)
+            shim.stream_sync(self._gpu_id, self._stream)      # `buf` goes with this call
+        d = _status(shim.annotate_batch(batch.descs, batch.d_frames, int(batch.format), ptr, m, params, batch.d_ws,
+                                        batch.ws_bytes, self._stream))
+        return d.success, d.info
+
+    def RunBatch(self, batch: AnnotateBatch, marks, cc_ctx=None) -> Tuple[bool, TaskExecInfo]:
+        r = self.RunBatchAsync(batch, marks, cc_ctx)
+        self._sync()
+        return r
+
+
 _ROT_FORMATS = [F.Y, F.GRAY12, F.RGB, F.BGR, F.RGB_PLANAR, F.YUV420, F.YUV422, F.YUV444, F.RGB_32F,
                 F.RGB_32F_PLANAR, F.YUV444_10bit, F.YUV420_10bit]
 # format -> (driver, element size); RotateSurface::Run switch (RotateSurface.cpp:168-208)
