@@ -571,11 +571,31 @@ VALI_API int vali_tensor_to_surfaces(const vali_tensor_src* src, const float sca
  * m > 0, params for a YUV format, workspace with n > 0); n outside 0..65535; m outside 0..4096; a frame with a null
  * plane, a size outside 1..65535, an odd size in a 4:2:0 format, a pitch shorter than a row or a format other than
  * `format`; a workspace that is too small or not 16-byte aligned.  VALI_ERR_UNSUPPORTED for a format outside the list.
+ *
+ * Stamps (vali_annotate_batch_atlas): labels, logos and ready-made masks from a COVERAGE ATLAS, one 8-bit plane
+ * (VALI_FMT_Y) in device memory, AW x AH with both in 1..65535, at any address and pitch, given per call as a HOST
+ * vali_surface that travels in the kernel arguments.
+ *   VALI_MARK_STAMP     arg = the stamp's origin in the atlas, u = arg & 0xffff, v = (arg >> 16) & 0xffff; w x h is its
+ *                       size on the frame and in the atlas (1:1, no resampling).  With dx = px - x, dy = py - y (64 bits)
+ *                       the coverage of frame pixel (px, py) is cov = atlas[v + dy][u + dx] if 0 <= dx < w, 0 <= dy < h,
+ *                       u + dx < AW and v + dy < AH, else 0: a rectangle that runs off the atlas reads as zero there, and
+ *                       no byte outside the atlas's AW x AH area is ever read.  The weight k of a sample is cov(px, py)
+ *                       for full-resolution channels and (cov(2cx, 2cy) + cov(2cx + 1, 2cy) + cov(2cx, 2cy + 1) +
+ *                       cov(2cx + 1, 2cy + 1) + 2) >> 2 for the 4:2:0 chroma sample (cx, cy); a STAMP rectangle is NOT
+ *                       snapped to even coordinates.  With a the colour's alpha, a_eff = (k * a + 127) / 255 and
+ *                       v = (v * (255 - a_eff) + c * a_eff + 127) / 255, c as for FILL: k = 255 is FILL's sample bit
+ *                       for bit, k = 0 leaves the sample as it is (and unwritten).
+ * A STAMP row is skipped when the call has no atlas (the kind is then unknown), w < 1 or h < 1, u >= AW or v >= AH, the
+ * frame is outside the batch or the rectangle does not meet its frame.  Stamps are applied in row order among the other
+ * kinds.  atlas may be NULL: the call is then vali_annotate_batch, and vali_annotate_batch is that call.  In addition
+ * VALI_ERR_INVALID_ARG, before any device is touched, for an atlas that is not VALI_FMT_Y, has a null plane, a size outside
+ * 1..65535 or a pitch shorter than a row.  The workspace, the two launches and every other rule are unchanged.
  */
 #define VALI_MARK_NONE 0
 #define VALI_MARK_BOX 1
 #define VALI_MARK_FILL 2
 #define VALI_MARK_PIXELATE 3
+#define VALI_MARK_STAMP 4
 #define VALI_MAX_MARKS 4096
 typedef struct vali_mark {
   int32_t frame, x, y, w, h, kind, arg, colour;
@@ -585,6 +605,10 @@ VALI_API int vali_annotate_workspace_size(int n, const vali_surface* frames, siz
 VALI_API int vali_annotate_batch(const vali_surface* frames, const vali_surface* d_frames, int n, int format,
                                  const vali_mark* d_marks, int m, const vali_cvt_params* params, void* workspace,
                                  size_t ws_bytes, vali_stream_t stream);
+VALI_API int vali_annotate_batch_atlas(const vali_surface* frames, const vali_surface* d_frames, int n, int format,
+                                       const vali_mark* d_marks, int m, const vali_surface* atlas,
+                                       const vali_cvt_params* params, void* workspace, size_t ws_bytes,
+                                       vali_stream_t stream);
 
 /*
  * Rectangles of surfaces of ANY sizes as files, in one fixed set of launches.  Item i is rectangle rois[i] of the

@@ -18,9 +18,10 @@ if not _BUILDING:
     from .runtime import CudaStreamEvent, GetNumGpus, HipResMgr, StreamCapture
     from .surface import Surface, SurfacePlane
     from .buffer import CudaBuffer
-    from .tasks import (MARK_BOX, MARK_FILL, MARK_NONE, MARK_PIXELATE, AnnotateBatch, FrameBatch, PySurfaceAnnotator,
-                        PySurfaceConverter, PySurfacePostprocessor, PySurfacePreprocessor, PySurfaceResizer,
-                        PySurfaceRotator, PySurfaceUD, RoiBatch, SurfaceBatch, TensorBatch, letterbox_rect, pack_colour)
+    from .tasks import (MARK_BOX, MARK_FILL, MARK_NONE, MARK_PIXELATE, MARK_STAMP, AnnotateBatch, FrameBatch, LabelAtlas,
+                        PySurfaceAnnotator, PySurfaceConverter, PySurfacePostprocessor, PySurfacePreprocessor,
+                        PySurfaceResizer, PySurfaceRotator, PySurfaceUD, RoiBatch, SurfaceBatch, TensorBatch,
+                        letterbox_rect, pack_colour, pack_uv, render_labels)
     from .pipeline import BatchedFramePipeline, broadcast_coefficients, shard_frames
     from .transfer import PyFrameUploader, PySurfaceDownloader
     from . import tuning

@@ -14,7 +14,8 @@
 //   k_annotate_bin   one workgroup per frame: sanitises the rows and leaves, in the workspace, the indices of the rows
 //                    that draw on its frame, in row order (a ballot / prefix compaction).  The tiles then scan their
 //                    frame's rows, not all m: m * 32 bytes per TILE was the alternative
-//   k_annotate<FMT>  grid (tiles of the largest frame, n).  A tile whose frame has no row leaves after two scalar loads;
+//   k_annotate<FMT, STAMPS>
+//                    grid (tiles of the largest frame, n).  A tile whose frame has no row leaves after two scalar loads;
 //                    otherwise it culls the frame's rows against the tile into an LDS hit list (again in order) and, with
 //                    no hit, leaves without touching a pixel
 // A lane owns the same 16-byte pieces of the tile throughout (one of Y, one of interleaved UV; three of packed RGB; one
@@ -22,6 +23,11 @@
 // the frame's right edge cuts a piece.  Fills and outlines are therefore lane-local and need no barrier; only pixelation
 // goes through LDS (integer atomic adds into per-cell sums: the sum does not depend on the order) and is fenced by
 // barriers.  Every branch on the mark kind is workgroup-uniform; the mark records are read at a uniform index.
+//
+// Stamps (vali_annotate_batch_atlas, VALI_MARK_STAMP) blend the mark's colour with a per-pixel weight from a coverage
+// atlas: lane-local like FILL (stamp_piece), the lane reads the coverage bytes its pieces need straight from the atlas,
+// which is small, re-read by many tiles and therefore served by the L2.  k_annotate<FMT, true> holds that path; a call
+// without an atlas launches k_annotate<FMT, false>, which is the kernel as it was before stamps existed.
 #include "common.hpp"
 #include "dev_util.hpp"
 
@@ -61,6 +67,13 @@ struct Mark {
   int cell;                // PIXELATE
   u32 colour;
 };
+// STAMP (kept apart from Mark, which the kernel without stamps resolves too): the pixels that have coverage,
+// rectangle ^ atlas ^ frame, NOT snapped on 4:2:0 frames (the Mark's x0 .. y1 are, for culling); frame pixel (px, py)
+// reads atlas[py + oy][px + ox]
+struct Stamp {
+  int rx0, ry0, rx1, ry1;
+  int ox, oy;
+};
 
 __device__ __forceinline__ void load_mark(const vali_mark* marks, int i, int (&r)[8]) {
   const uint4 a = load16_u((const uint8_t*)(marks + i)), b = load16_u((const uint8_t*)(marks + i) + 16);
@@ -70,10 +83,11 @@ __device__ __forceinline__ void load_mark(const vali_mark* marks, int i, int (&r
 
 __device__ __forceinline__ int clampi(long long v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : (int)v; }
 
-// false: the row is skipped (the rules of include/vali_hip.h; the frame index is the caller's to check)
-__device__ __forceinline__ bool resolve_mark(const int (&r)[8], int W, int H, bool is420, Mark& m) {
+// false: the row is skipped (the rules of include/vali_hip.h; the frame index is the caller's to check).  AW x AH: the
+// atlas, 0 x 0 without one -- VALI_MARK_STAMP is then an unknown kind
+__device__ __forceinline__ bool resolve_mark(const int (&r)[8], int W, int H, bool is420, int AW, int AH, Mark& m) {
   const int kind = r[5], arg = r[6];
-  if (kind < VALI_MARK_BOX || kind > VALI_MARK_PIXELATE || r[3] < 1 || r[4] < 1)
+  if (kind < VALI_MARK_BOX || kind > (AW > 0 ? VALI_MARK_STAMP : VALI_MARK_PIXELATE) || r[3] < 1 || r[4] < 1)
     return false;
   if (kind == VALI_MARK_BOX && arg < 1)
     return false;
@@ -81,6 +95,13 @@ __device__ __forceinline__ bool resolve_mark(const int (&r)[8], int W, int H, bo
     return false;
   // 64 bits: x + w and x + t overflow int32
   long long x0 = r[1], y0 = r[2], x1 = x0 + r[3], y1 = y0 + r[4], t = arg;
+  if (AW > 0 && kind == VALI_MARK_STAMP) {
+    const int u = arg & 0xffff, v = (arg >> 16) & 0xffff;
+    if (u >= AW || v >= AH)
+      return false;
+    // beyond the atlas the coverage is zero: the rectangle ends where the atlas does
+    x1 = min(x1, x0 + (AW - u)), y1 = min(y1, y0 + (AH - v));
+  }
   if (is420) {
     x0 &= ~1ll, y0 &= ~1ll, x1 = (x1 + 1) & ~1ll, y1 = (y1 + 1) & ~1ll, t = (t + 1) & ~1ll;
   }
@@ -103,6 +124,15 @@ __device__ __forceinline__ bool resolve_mark(const int (&r)[8], int W, int H, bo
       m.ix0 = ix0, m.ix1 = ix1, m.iy0 = iy0, m.iy1 = iy1;
   }
   return true;
+}
+
+// a STAMP row that resolve_mark let through
+__device__ __forceinline__ void resolve_stamp(const int (&r)[8], int W, int H, int AW, int AH, Stamp& st) {
+  const int u = r[6] & 0xffff, v = (r[6] >> 16) & 0xffff;
+  // 32 bits do: a rectangle that meets its frame starts above -65535, and the atlas ends it within 65535 pixels
+  const int x0 = r[1], y0 = r[2], x1 = x0 + min(r[3], AW - u), y1 = y0 + min(r[4], AH - v);
+  st.rx0 = min(max(x0, 0), W), st.ry0 = min(max(y0, 0), H), st.rx1 = min(max(x1, 0), W), st.ry1 = min(max(y1, 0), H);
+  st.ox = u - x0, st.oy = v - y0;
 }
 
 // does the mark paint inside the tile [tx0, tx0 + 64) x [ty0, ty0 + 64) of a W x H frame
@@ -139,7 +169,7 @@ __device__ __forceinline__ int compact_put(bool flag, int value, uint16_t* out, 
 // ---- launch 1: the rows of each frame ---------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kBlock) k_annotate_bin(const vali_surface* __restrict__ d_frames,
                                                          const vali_mark* __restrict__ marks, int m, int is420,
-                                                         uint8_t* __restrict__ ws) {
+                                                         int AW, int AH, uint8_t* __restrict__ ws) {
   __shared__ int wtot[kWavesPerBlock];
   const int f = blockIdx.x;
   const int W = d_frames[f].width, H = d_frames[f].height;
@@ -153,7 +183,7 @@ __global__ void __launch_bounds__(kBlock) k_annotate_bin(const vali_surface* __r
       int r[8];
       load_mark(marks, i, r);
       Mark mk;
-      flag = r[0] == f && resolve_mark(r, W, H, is420 != 0, mk);
+      flag = r[0] == f && resolve_mark(r, W, H, is420 != 0, AW, AH, mk);
     }
     total = compact_put(flag, i, list, total, wtot);
   }
@@ -167,6 +197,11 @@ struct AnnArgs {
   const vali_mark* marks;
   const uint8_t* ws;
   float m[3][4];  // rgb2yuv rows (YUV formats)
+};
+// the coverage atlas of a call that has one (k_annotate<FMT, true>): w x h bytes, rows `pitch` apart; without: all 0
+struct StampAtlas {
+  const uint8_t* p;
+  int pitch, w, h;
 };
 
 // what a lane keeps of one of its pieces
@@ -185,6 +220,25 @@ __device__ __forceinline__ float dot_rgb(const float (&m)[4], float r, float g, 
   return __builtin_fmaf(m[2], b, __builtin_fmaf(m[1], g, __builtin_fmaf(m[0], r, m[3])));
 }
 
+// the colour of byte b of a piece is c[b % nc]: packed RGB pieces start at any of the three channels
+template <int FMT, int S>
+__device__ __forceinline__ void piece_colours(int lbx, const u32 (&col)[3], u32 (&c)[3]) {
+  constexpr Slot sl = slot_of(FMT, S);
+  constexpr int nc = sl.nc;
+  if constexpr (nc == 3) {
+    // (shifts of one packed word: a select chain over col[] becomes a table in scratch memory)
+    const u32 ch0 = (u32)lbx % 3u;
+    const unsigned long long pk = (unsigned long long)(col[0] | col[1] << 8 | col[2] << 16 | col[0] << 24) |
+                                  (unsigned long long)col[1] << 32;
+    c[0] = (u32)(pk >> (8u * ch0)) & 0xffu, c[1] = (u32)(pk >> (8u * ch0 + 8u)) & 0xffu;
+    c[2] = (u32)(pk >> (8u * ch0 + 16u)) & 0xffu;
+  } else if constexpr (nc == 2) {
+    c[0] = col[sl.c0], c[1] = col[sl.c0 + 1], c[2] = 0;
+  } else {
+    c[0] = col[sl.c0], c[1] = 0, c[2] = 0;
+  }
+}
+
 // FILL and BOX on one piece: lane-local
 template <int FMT, int S>
 __device__ __forceinline__ void blend_piece(const Piece& pc, const Mark& mk, const u32 (&col)[3], u32 alpha, u32 (&w)[4]) {
@@ -197,20 +251,8 @@ __device__ __forceinline__ void blend_piece(const Piece& pc, const Mark& mk, con
     return;
   const bool inner_row = pc.y >= (mk.iy0 >> sh) && pc.y < (mk.iy1 >> sh);
   const int ilo = inner_row ? (mk.ix0 >> sh) * nc - pc.bx : 0, ihi = inner_row ? (mk.ix1 >> sh) * nc - pc.bx : 0;
-  // the colour of byte b is c[b % nc]: packed RGB pieces start at any of the three channels
   u32 c[3];
-  if constexpr (nc == 3) {
-    // (shifts of one packed word: a select chain over col[] becomes a table in scratch memory)
-    const u32 ch0 = (u32)pc.lbx % 3u;
-    const unsigned long long pk = (unsigned long long)(col[0] | col[1] << 8 | col[2] << 16 | col[0] << 24) |
-                                  (unsigned long long)col[1] << 32;
-    c[0] = (u32)(pk >> (8u * ch0)) & 0xffu, c[1] = (u32)(pk >> (8u * ch0 + 8u)) & 0xffu;
-    c[2] = (u32)(pk >> (8u * ch0 + 16u)) & 0xffu;
-  } else if constexpr (nc == 2) {
-    c[0] = col[sl.c0], c[1] = col[sl.c0 + 1], c[2] = 0;
-  } else {
-    c[0] = col[sl.c0], c[1] = 0, c[2] = 0;
-  }
+  piece_colours<FMT, S>(pc.lbx, col, c);
   const u32 ia = 255u - alpha;
 #pragma unroll
   for (int b = 0; b < 16; ++b) {
@@ -222,7 +264,137 @@ __device__ __forceinline__ void blend_piece(const Piece& pc, const Mark& mk, con
   }
 }
 
-// PIXELATE on one piece: ADD = the piece's samples go into the cell sums, !ADD = the cell means come back
+// ---- STAMP: lane-local like FILL, the weight of every sample comes from the atlas --------------------------------------
+// the n low bytes of a quad word, n clamped to 0 .. 8
+__device__ __forceinline__ unsigned long long low_bytes(int n) {
+  return n <= 0 ? 0ull : n >= 8 ? ~0ull : (1ull << (8 * n)) - 1ull;
+}
+
+// the 16 bytes (lo, hi) moved by d bytes, |d| < 16, towards the higher bytes (d > 0) or the lower; zeros come in
+__device__ __forceinline__ void shift_bytes(unsigned long long& lo, unsigned long long& hi, int d) {
+  const u32 n = 8u * (u32)(d < 0 ? -d : d);
+  if (d > 0) {
+    if (n >= 64u)
+      hi = lo << (n - 64u), lo = 0ull;
+    else
+      hi = hi << n | lo >> (64u - n), lo <<= n;
+  } else if (d < 0) {
+    if (n >= 64u)
+      lo = hi >> (n - 64u), hi = 0ull;
+    else
+      lo = lo >> n | hi << (64u - n), hi >>= n;
+  }
+}
+
+// The coverage of the N (16, or 6 for a packed RGB piece) frame pixels X .. X + N - 1 of frame row py, a byte each, zero
+// where the stamp has none.  ONE vector load of 16 (N = 6: 8) bytes: the window slides into the atlas row where the
+// pixels hang over its ends and the bytes are moved back in registers (labels start at the atlas's column 0, so the
+// first piece of every stamp row hangs over).  An atlas narrower than the window is read byte by byte.  No byte outside
+// the atlas's area is read either way.  (mk.rx0 .. mk.ry1 end with the atlas.)
+template <int N>
+__device__ __forceinline__ void load_cov(const StampAtlas& t, const Stamp& mk, int X, int py, u32 (&cv)[N == 16 ? 4 : 2]) {
+  constexpr int NW = N == 16 ? 4 : 2;
+#pragma unroll
+  for (int k = 0; k < NW; ++k)
+    cv[k] = 0u;
+  const int lo = max(mk.rx0 - X, 0), hi = min(mk.rx1 - X, N);
+  if (py < mk.ry0 || py >= mk.ry1 || lo >= hi)
+    return;
+  const int s = X + mk.ox;  // the atlas column under pixel X: in -N + 1 .. aw - 1, as some pixel has coverage
+  const uint8_t* row = t.p + (size_t)(py + mk.oy) * (size_t)t.pitch;
+  unsigned long long q0 = 0ull, q1 = 0ull;
+  if (t.w >= 4 * NW) {
+    const int sw = min(max(s, 0), t.w - 4 * NW);
+    if constexpr (N == 16) {
+      const v4u32 q = gload_u<v4u32>(row + sw);
+      q0 = (unsigned long long)q.x | (unsigned long long)q.y << 32, q1 = (unsigned long long)q.z | (unsigned long long)q.w << 32;
+    } else {
+      const v2u32 q = gload_u<v2u32>(row + sw);
+      q0 = (unsigned long long)q.x | (unsigned long long)q.y << 32;
+    }
+    shift_bytes(q0, q1, sw - s);
+  } else {
+    for (int k = lo; k < hi; ++k) {  // (rolled: shifts, not an indexed register array)
+      const unsigned long long b = gload<uint8_t>(row + (s + k));
+      if (k < 8)
+        q0 |= b << (8 * k);
+      else
+        q1 |= b << (8 * (k - 8));
+    }
+  }
+  q0 &= low_bytes(hi) & ~low_bytes(lo);
+  cv[0] = (u32)q0, cv[1] = (u32)(q0 >> 32);
+  if constexpr (N == 16) {
+    q1 &= low_bytes(hi - 8) & ~low_bytes(lo - 8);
+    cv[2] = (u32)q1, cv[3] = (u32)(q1 >> 32);
+  }
+}
+
+template <int FMT, int S>
+__device__ __forceinline__ void stamp_piece(const StampAtlas& t, const Piece& pc, const Stamp& mk, const u32 (&col)[3],
+                                            u32 alpha, u32 (&w)[4]) {
+  constexpr Slot sl = slot_of(FMT, S);
+  constexpr int nc = sl.nc, sh = sl.sh;
+  // the luma pixels under the piece: `span` columns from X, 1 << sh rows from Y
+  constexpr int span = nc == 3 ? 6 : (16 / nc) << sh;
+  const int X = nc == 3 ? pc.bx / 3 : (pc.bx / nc) << sh, Y = pc.y << sh;
+  if (pc.n <= 0 || Y >= mk.ry1 || Y + (1 << sh) <= mk.ry0 || X >= mk.rx1 || X + span <= mk.rx0)
+    return;
+  u32 k[4] = {0u, 0u, 0u, 0u};  // the weight of every byte of the piece
+  if constexpr (nc == 3) {
+    // byte b belongs to pixel (ch0 + b) / 3 of the six, ch0 the channel the piece starts with: every weight three times
+    // (byte selects with constant selectors), then the 16 bytes from ch0 on -- nothing here but ch0 is the same for
+    // every mark, so nothing else is kept in registers across the marks
+    u32 cv[2];
+    load_cov<6>(t, mk, X, Y, cv);
+    if ((cv[0] | cv[1]) == 0u)
+      return;
+    const u32 ch0 = (u32)pc.bx - 3u * (u32)X;
+    const u32 e0 = __builtin_amdgcn_perm(0u, cv[0], 0x01000000u), e1 = __builtin_amdgcn_perm(0u, cv[0], 0x02020101u);
+    const u32 e2 = __builtin_amdgcn_perm(0u, cv[0], 0x03030302u), e3 = __builtin_amdgcn_perm(0u, cv[1], 0x01000000u);
+    const u32 e4 = __builtin_amdgcn_perm(0u, cv[1], 0x01010101u);
+    k[0] = __builtin_amdgcn_alignbyte(e1, e0, ch0), k[1] = __builtin_amdgcn_alignbyte(e2, e1, ch0);
+    k[2] = __builtin_amdgcn_alignbyte(e3, e2, ch0), k[3] = __builtin_amdgcn_alignbyte(e4, e3, ch0);
+  } else if constexpr (sh == 0) {
+    load_cov<16>(t, mk, X, Y, k);
+  } else {
+    // a 4:2:0 chroma sample: the rounded mean of the coverage of its four luma pixels, two 16-bit sums to a word
+#pragma unroll
+    for (int g = 0; g < span / 16; ++g) {
+      u32 r0[4], r1[4];
+      load_cov<16>(t, mk, X + 16 * g, Y, r0);
+      load_cov<16>(t, mk, X + 16 * g, Y + 1, r1);
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        const u32 sum = (r0[d] & 0xff00ffu) + ((r0[d] >> 8) & 0xff00ffu) + (r1[d] & 0xff00ffu) + ((r1[d] >> 8) & 0xff00ffu);
+        const u32 q = ((sum + 0x20002u) >> 2) & 0xff00ffu;
+        if constexpr (nc == 2)
+          k[d] = q | q << 8;  // U and V of a sample share its weight
+        else
+          k[2 * g + d / 2] |= ((q | q >> 8) & 0xffffu) << (16 * (d % 2));
+      }
+    }
+  }
+  if ((k[0] | k[1] | k[2] | k[3]) == 0u)
+    return;
+  u32 c[3];
+  piece_colours<FMT, S>(pc.lbx, col, c);
+  // per word, so that a word of weights is spent before the next is formed
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    u32 out = w[q];
+#pragma unroll
+    for (int b = 4 * q; b < 4 * q + 4; ++b) {
+      const u32 ae = div255(((k[q] >> (8 * (b % 4))) & 0xffu) * alpha + 127u);
+      const u32 v = (w[q] >> (8 * (b % 4))) & 0xffu;
+      const u32 nv = div255(v * (255u - ae) + c[b % nc] * ae + 127u);  // ae = 0: v
+      out = (out & ~(0xffu << (8 * (b % 4)))) | (nv << (8 * (b % 4)));
+    }
+    w[q] = out;
+  }
+}
+
+// PIXELATE on one piece: ADD =the piece's samples go into the cell sums, !ADD = the cell means come back
 template <int FMT, int S, bool ADD>
 __device__ __forceinline__ void pixelate_piece(const Piece& pc, const Mark& mk, int lcell, u32* sums, u32 (&w)[4]) {
   constexpr Slot sl = slot_of(FMT, S);
@@ -299,17 +471,28 @@ __device__ __forceinline__ void store_piece(const Piece& pc, const u32 (&cur)[4]
     }                      \
   }
 
-template <int FMT>
-__global__ void __launch_bounds__(kBlock) k_annotate(const AnnArgs a) {
+// STAMPS: the call has an atlas.  Without one the kernel holds no stamp path and VALI_MARK_STAMP is an unknown kind.
+// The waves per SIMD asked of the register allocator: YUV420 with stamps lands one register above the fourth wave (129)
+// and fits it when asked; everything else is left at the default of this workgroup size, one
+constexpr int min_waves(int f, bool stamps) { return stamps && f == A_YUV420 ? 4 : 1; }
+template <int FMT, bool STAMPS>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(min_waves(FMT, STAMPS), 8)))
+k_annotate(const AnnArgs a, const StampAtlas t) {
   __shared__ uint16_t hits[kMaxMarks];
   __shared__ u32 sums[kCells];
   __shared__ int wtot[kWavesPerBlock];
   constexpr int NS = nslots(FMT);
   constexpr bool is420 = a_is420(FMT);
+  const int AW = STAMPS ? t.w : 0, AH = STAMPS ? t.h : 0;
 
   const int f = blockIdx.y;
   const vali_surface* d = a.d_frames + f;
   const int W = d->width, H = d->height;
+  if constexpr (STAMPS) {
+    // (check_frames: the 64-bit forms of W and H that resolve_mark compares with then need no registers for their high
+    // halves, which this instantiation has no scalar registers left for)
+    __builtin_assume(W >= 1 && W <= 65535 && H >= 1 && H <= 65535);
+  }
   const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile;
   if ((int)blockIdx.x >= tiles_x * tiles_y)
     return;  // the grid is sized for the batch's largest frame
@@ -333,7 +516,7 @@ __global__ void __launch_bounds__(kBlock) k_annotate(const AnnArgs a) {
       int r[8];
       load_mark(a.marks, idx, r);
       Mark mk;
-      flag = resolve_mark(r, W, H, is420, mk) && mark_meets_tile(mk, tx0, ty0, W, H);
+      flag = resolve_mark(r, W, H, is420, AW, AH, mk) && mark_meets_tile(mk, tx0, ty0, W, H);
     }
     nh = compact_put(flag, idx, hits, nh, wtot);
   }
@@ -352,7 +535,7 @@ __global__ void __launch_bounds__(kBlock) k_annotate(const AnnArgs a) {
     int r[8];
     load_mark(a.marks, idx, r);
     Mark mk;
-    if (!resolve_mark(r, W, H, is420, mk))
+    if (!resolve_mark(r, W, H, is420, AW, AH, mk))
       continue;
     if (mk.kind == VALI_MARK_PIXELATE) {
       const int lcell = 31 - __clz(mk.cell);
@@ -395,9 +578,19 @@ __global__ void __launch_bounds__(kBlock) k_annotate(const AnnArgs a) {
       } else {
         col[0] = cr, col[1] = cg, col[2] = cb;
       }
-#define VALI_SLOT(S) blend_piece<FMT, S>(pc[S], mk, col, alpha, cur[S]);
-      VALI_SLOTS(VALI_SLOT)
+      if (STAMPS && mk.kind == VALI_MARK_STAMP) {
+        if constexpr (STAMPS) {
+          Stamp st;
+          resolve_stamp(r, W, H, AW, AH, st);
+#define VALI_SLOT(S) stamp_piece<FMT, S>(t, pc[S], st, col, alpha, cur[S]);
+          VALI_SLOTS(VALI_SLOT)
 #undef VALI_SLOT
+        }
+      } else {
+#define VALI_SLOT(S) blend_piece<FMT, S>(pc[S], mk, col, alpha, cur[S]);
+        VALI_SLOTS(VALI_SLOT)
+#undef VALI_SLOT
+      }
     }
   }
 
@@ -418,6 +611,14 @@ int ann_format(int format) {
   case VALI_FMT_RGB_PLANAR: return A_RGBP;
   default: return -1;
   }
+}
+
+template <int FMT>
+void launch_tiles(const dim3& grid, hipStream_t s, const AnnArgs& a, const StampAtlas& t) {
+  if (t.p)
+    hipLaunchKernelGGL((k_annotate<FMT, true>), grid, dim3(kBlock), 0, s, a, t);
+  else
+    hipLaunchKernelGGL((k_annotate<FMT, false>), grid, dim3(kBlock), 0, s, a, t);
 }
 
 // the rules for the frames of a batch; *max_tiles: the tiles of the largest one
@@ -475,6 +676,12 @@ int vali_annotate_workspace_size(int n, const vali_surface* frames, size_t* byte
 int vali_annotate_batch(const vali_surface* frames, const vali_surface* d_frames, int n, int format,
                         const vali_mark* d_marks, int m, const vali_cvt_params* params, void* workspace,
                         size_t ws_bytes, vali_stream_t stream) {
+  return vali_annotate_batch_atlas(frames, d_frames, n, format, d_marks, m, nullptr, params, workspace, ws_bytes, stream);
+}
+
+int vali_annotate_batch_atlas(const vali_surface* frames, const vali_surface* d_frames, int n, int format,
+                              const vali_mark* d_marks, int m, const vali_surface* atlas, const vali_cvt_params* params,
+                              void* workspace, size_t ws_bytes, vali_stream_t stream) {
   VALI_REQUIRE(n >= 0 && n <= 65535, "n outside 0..65535");
   VALI_REQUIRE(m >= 0 && m <= kMaxMarks, "m outside 0..4096");
   VALI_REQUIRE((frames && d_frames) || n == 0, "null frames");
@@ -489,6 +696,13 @@ int vali_annotate_batch(const vali_surface* frames, const vali_surface* d_frames
   VALI_REQUIRE(workspace || n == 0, "null workspace");
   VALI_REQUIRE(((uintptr_t)workspace & 15u) == 0, "the workspace is not 16-byte aligned");
   VALI_REQUIRE(ws_bytes >= (size_t)n * kBinBytes, "the workspace is smaller than vali_annotate_workspace_size");
+  if (atlas) {
+    VALI_REQUIRE(atlas->format == VALI_FMT_Y, "the atlas is not a VALI_FMT_Y surface");
+    VALI_REQUIRE(atlas->plane[0], "the atlas has a null plane");
+    VALI_REQUIRE(atlas->width >= 1 && atlas->height >= 1 && atlas->width <= 65535 && atlas->height <= 65535,
+                 "the atlas's size is outside 1..65535");
+    VALI_REQUIRE(atlas->pitch[0] >= atlas->width, "the atlas's pitch is shorter than a row");
+  }
   if (n == 0 || m == 0)
     return VALI_OK;
 
@@ -500,20 +714,25 @@ int vali_annotate_batch(const vali_surface* frames, const vali_surface* d_frames
     for (int k = 0; k < 3; ++k)
       for (int j = 0; j < 4; ++j)
         a.m[k][j] = params->rgb2yuv[k][j];
+  StampAtlas t = {};
+  if (atlas) {
+    t.p = (const uint8_t*)atlas->plane[0];
+    t.pitch = atlas->pitch[0], t.w = atlas->width, t.h = atlas->height;
+  }
 
   hipStream_t s = as_stream(stream);
   VALI_ENTRY(s);
-  hipLaunchKernelGGL(k_annotate_bin, dim3(n), dim3(kBlock), 0, s, d_frames, d_marks, m, a_is420(fmt) ? 1 : 0,
+  hipLaunchKernelGGL(k_annotate_bin, dim3(n), dim3(kBlock), 0, s, d_frames, d_marks, m, a_is420(fmt) ? 1 : 0, t.w, t.h,
                      (uint8_t*)workspace);
   VALI_LAUNCH_CHECK();
   const dim3 grid(tiles, n);
   switch (fmt) {
-  case A_NV12: hipLaunchKernelGGL(k_annotate<A_NV12>, grid, dim3(kBlock), 0, s, a); break;
-  case A_YUV420: hipLaunchKernelGGL(k_annotate<A_YUV420>, grid, dim3(kBlock), 0, s, a); break;
-  case A_YUV444: hipLaunchKernelGGL(k_annotate<A_YUV444>, grid, dim3(kBlock), 0, s, a); break;
-  case A_RGB: hipLaunchKernelGGL(k_annotate<A_RGB>, grid, dim3(kBlock), 0, s, a); break;
-  case A_BGR: hipLaunchKernelGGL(k_annotate<A_BGR>, grid, dim3(kBlock), 0, s, a); break;
-  default: hipLaunchKernelGGL(k_annotate<A_RGBP>, grid, dim3(kBlock), 0, s, a); break;
+  case A_NV12: launch_tiles<A_NV12>(grid, s, a, t); break;
+  case A_YUV420: launch_tiles<A_YUV420>(grid, s, a, t); break;
+  case A_YUV444: launch_tiles<A_YUV444>(grid, s, a, t); break;
+  case A_RGB: launch_tiles<A_RGB>(grid, s, a, t); break;
+  case A_BGR: launch_tiles<A_BGR>(grid, s, a, t); break;
+  default: launch_tiles<A_RGBP>(grid, s, a, t); break;
   }
   VALI_LAUNCH_CHECK();
   return VALI_OK;

@@ -694,15 +694,17 @@ PYBIND11_MODULE(_vali_shim, m) {
   });
   m.def("annotate_batch",
         [](const std::vector<SurfaceDesc>& descs, uintptr_t d_frames, int format, uintptr_t d_marks, int m,
-           const CvtParams* p, uintptr_t workspace, size_t ws_bytes, uintptr_t stream) {
+           const CvtParams* p, uintptr_t workspace, size_t ws_bytes, uintptr_t stream, const SurfaceDesc* atlas) {
           std::vector<vali_surface> host(descs.size());
           for (size_t i = 0; i < descs.size(); ++i)
             host[i] = descs[i].s;
           py::gil_scoped_release nogil;
-          return vali_annotate_batch(host.data(), (const vali_surface*)P(d_frames), (int)host.size(), format,
-                                     (const vali_mark*)P(d_marks), m, p ? &p->p : nullptr, P(workspace), ws_bytes,
-                                     P(stream));
-        });
+          return vali_annotate_batch_atlas(host.data(), (const vali_surface*)P(d_frames), (int)host.size(), format,
+                                           (const vali_mark*)P(d_marks), m, atlas ? &atlas->s : nullptr,
+                                           p ? &p->p : nullptr, P(workspace), ws_bytes, P(stream));
+        },
+        py::arg("descs"), py::arg("d_frames"), py::arg("format"), py::arg("d_marks"), py::arg("m"), py::arg("params"),
+        py::arg("workspace"), py::arg("ws_bytes"), py::arg("stream"), py::arg("atlas") = py::none());
 
   // ---- JPEG decoder: host-side parser and sizes, then the batched decoder --------------------------------------
   py::class_<JpegInfo>(m, "JpegInfo")

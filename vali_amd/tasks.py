@@ -1319,7 +1319,7 @@ class PySurfacePostprocessor(_SurfaceTask):
 
 
 # ---- PySurfaceAnnotator: outlines, fills and pixelation from GPU-held marks ------------------------------
-MARK_NONE, MARK_BOX, MARK_FILL, MARK_PIXELATE = 0, 1, 2, 3
+MARK_NONE, MARK_BOX, MARK_FILL, MARK_PIXELATE, MARK_STAMP = 0, 1, 2, 3, 4
 MAX_MARKS = 4096
 _PIXELATE_CELLS = (4, 8, 16, 32)
 
@@ -1333,9 +1333,19 @@ def pack_colour(r: int, g: int, b: int, a: int = 255) -> int:
     return v - (1 << 32) if v >= 1 << 31 else v
 
 
-def _host_marks(rows, sizes, is420):
+def pack_uv(u: int, v: int) -> int:
+    """the `arg` of a MARK_STAMP row: the stamp's origin (u, v) in the atlas, u | v << 16 as an int32"""
+    u, v = operator.index(u), operator.index(v)
+    if not (0 <= u <= 65535 and 0 <= v <= 65535):
+        raise ValueError("pack_uv: u, v in 0..65535")
+    a = u | v << 16
+    return a - (1 << 32) if a >= 1 << 31 else a
+
+
+def _host_marks(rows, sizes, is420, atlas_size=None):
     """a host sequence of (frame, x, y, w, h, kind, arg, colour): the rules the kernel applies to a device tensor, with
-    ValueErrors where the kernel would skip the row -- except kind 0 and unknown kinds, which are skipped here too"""
+    ValueErrors where the kernel would skip the row -- except kind 0 and unknown kinds, which are skipped here too.
+    MARK_STAMP is a known kind when the call has an atlas (atlas_size = (AW, AH))"""
     out = []
     for i, row in enumerate(rows):
         try:
@@ -1348,7 +1358,7 @@ def _host_marks(rows, sizes, is420):
             raise ValueError(f"marks: row {i}: every value must fit an int32 (colours: pack_colour)")
         frame, x, y, w, h, kind, arg, _ = r
         out.append(r)
-        if kind not in (MARK_BOX, MARK_FILL, MARK_PIXELATE):
+        if kind not in (MARK_BOX, MARK_FILL, MARK_PIXELATE) and not (kind == MARK_STAMP and atlas_size is not None):
             continue
         if not 0 <= frame < len(sizes):
             raise ValueError(f"marks: row {i}: frame {frame} is outside 0..{len(sizes) - 1}")
@@ -1358,8 +1368,13 @@ def _host_marks(rows, sizes, is420):
             raise ValueError(f"marks: row {i}: MARK_BOX needs a thickness of at least 1, got {arg}")
         if kind == MARK_PIXELATE and arg not in _PIXELATE_CELLS:
             raise ValueError(f"marks: row {i}: MARK_PIXELATE needs a cell of 4, 8, 16 or 32, got {arg}")
+        if kind == MARK_STAMP:
+            u, v = arg & 0xFFFF, (arg >> 16) & 0xFFFF
+            if u >= atlas_size[0] or v >= atlas_size[1]:
+                raise ValueError(f"marks: row {i}: the stamp's origin ({u}, {v}) is outside the atlas "
+                                 f"({atlas_size[0]}x{atlas_size[1]}); arg: pack_uv")
         x0, y0, x1, y1 = x, y, x + w, y + h
-        if is420:
+        if is420 and kind != MARK_STAMP:      # (a stamp is not snapped; snapping never changes the answer below)
             x0, y0, x1, y1 = x0 & ~1, y0 & ~1, (x1 + 1) & ~1, (y1 + 1) & ~1
         fw, fh = sizes[frame]
         if x0 >= fw or y0 >= fh or x1 <= 0 or y1 <= 0:
@@ -1400,6 +1415,21 @@ def _device_marks(marks, gpu_id):
     if shape[0] > MAX_MARKS:
         raise ValueError(f"marks: {shape[0]} rows; at most {MAX_MARKS} per call")
     return ptr, shape[0], holder
+
+
+def _atlas_size(atlas, gpu_id):
+    """(AW, AH) of a coverage atlas: a Surface of format Y on the task's device"""
+    fmt = getattr(atlas, "Format", None)
+    if fmt is None or not hasattr(atlas, "desc"):
+        raise ValueError(f"atlas: need a Surface of format Y, got {type(atlas).__name__}")
+    if fmt != F.Y:
+        raise ValueError(f"atlas: the surface has format {fmt!r}; a coverage atlas is one 8-bit plane, format Y")
+    if atlas.IsEmpty:
+        raise ValueError("atlas: the surface is empty")
+    dev = getattr(atlas, "DeviceId", gpu_id)
+    if dev != gpu_id:
+        raise ValueError(f"atlas: the surface is on device {dev}, the task on {gpu_id}")
+    return atlas.Width, atlas.Height
 
 
 class AnnotateBatch:
@@ -1476,6 +1506,12 @@ class PySurfaceAnnotator(_SurfaceTask):
     and uploaded with one blocking copy on the task's stream.  Marks are applied in row order.  `colour`: pack_colour().
     The definition, sample for sample, is in include/vali_hip.h; the reference has no such task.
 
+    `atlas` (RunBatch): a coverage atlas for MARK_STAMP rows -- a Surface of format Y on the task's device (Surface.Make,
+    or Surface.from_dlpack(t, vali.Y) of a uint8 (H, W) GPU tensor: a pitched view at any address).  A STAMP row blends
+    its colour into its w x h rectangle with the per-pixel weight atlas[v + dy][u + dx], (u, v) = its `arg` (pack_uv), at
+    scale 1:1; beyond the atlas the weight is zero.  Labels: render_labels / LabelAtlas.  Without an atlas kind 4 is an
+    unknown kind.  The batch keeps the atlas alive, as it keeps a marks tensor.
+
     `cc_ctx` picks the RGB -> YUV matrix for colours on YUV frames exactly as PySurfacePostprocessor.Matrix does; an
     unsupported one gives (False, UNSUPPORTED_FMT_CONV_PARAMS) and nothing is launched.  Ignored for RGB formats.
     """
@@ -1489,9 +1525,10 @@ class PySurfaceAnnotator(_SurfaceTask):
     def PrepareBatch(self, frames: Sequence[Surface]) -> AnnotateBatch:
         return AnnotateBatch(self._gpu_id, self._stream, frames)
 
-    def RunBatchAsync(self, batch: AnnotateBatch, marks, cc_ctx=None) -> Tuple[bool, TaskExecInfo]:
+    def RunBatchAsync(self, batch: AnnotateBatch, marks, cc_ctx=None, atlas=None) -> Tuple[bool, TaskExecInfo]:
         if not isinstance(batch, AnnotateBatch):
             raise ValueError("RunBatch: pass an AnnotateBatch (PrepareBatch)")
+        atlas_size = _atlas_size(atlas, self._gpu_id) if atlas is not None else None
         if hasattr(marks, "__cuda_array_interface__") or hasattr(marks, "__dlpack__"):
             ptr, m, batch._marks_keep = _device_marks(marks, self._gpu_id)
             host = None
@@ -1503,7 +1540,7 @@ class PySurfaceAnnotator(_SurfaceTask):
                                  "8-tuples") from None
             if len(rows) > MAX_MARKS:
                 raise ValueError(f"marks: {len(rows)} rows; at most {MAX_MARKS} per call")
-            host = _host_marks(rows, batch.sizes, batch.format in (F.NV12, F.YUV420))
+            host = _host_marks(rows, batch.sizes, batch.format in (F.NV12, F.YUV420), atlas_size)
             ptr, m = batch.d_marks, len(host)
         params = None
         if batch.format in (F.NV12, F.YUV420, F.YUV444):
@@ -1520,14 +1557,79 @@ class PySurfaceAnnotator(_SurfaceTask):
             src, nbytes = buf.buffer_info()[0], 32 * m
             shim.memcpy2d_async(self._gpu_id, ptr, nbytes, src, nbytes, nbytes, 1, 0, self._stream)
             shim.stream_sync(self._gpu_id, self._stream)      # `buf` goes with this call
+        batch._atlas_keep = atlas
         d = _status(shim.annotate_batch(batch.descs, batch.d_frames, int(batch.format), ptr, m, params, batch.d_ws,
-                                        batch.ws_bytes, self._stream))
+                                        batch.ws_bytes, self._stream, atlas.desc() if atlas is not None else None))
         return d.success, d.info
 
-    def RunBatch(self, batch: AnnotateBatch, marks, cc_ctx=None) -> Tuple[bool, TaskExecInfo]:
-        r = self.RunBatchAsync(batch, marks, cc_ctx)
+    def RunBatch(self, batch: AnnotateBatch, marks, cc_ctx=None, atlas=None) -> Tuple[bool, TaskExecInfo]:
+        r = self.RunBatchAsync(batch, marks, cc_ctx, atlas)
         self._sync()
         return r
+
+
+def render_labels(labels, font=None, pad: int = 1):
+    """Text labels as a coverage atlas for MARK_STAMP rows (host only; needs Pillow): returns (atlas, rects), `atlas` a
+    (H, W) uint8 numpy array and `rects` an (L, 4) int32 array of (u, v, w, h).  Each label is one strip -- its text,
+    antialiased, with `pad` pixels of zero coverage around it -- and the strips are stacked top to bottom from column 0.
+    `font`: a PIL ImageFont; None uses ImageFont.load_default(), which is built into Pillow.  Whole-label strips keep a
+    detector's class ids on the GPU: gather rects[class_id] there and build the STAMP rows with a few tensor operations."""
+    try:
+        from PIL import Image, ImageDraw, ImageFont
+    except Exception as exc:  # pragma: no cover - depends on the environment
+        raise RuntimeError(f"render_labels: Pillow (PIL) is not importable ({exc})") from exc
+    import numpy as np
+
+    labels = [str(t) for t in labels]
+    pad = operator.index(pad)
+    if pad < 0:
+        raise ValueError("render_labels: pad must be at least 0")
+    if not labels:
+        raise ValueError("render_labels: no labels")
+    if font is None:
+        font = ImageFont.load_default()
+    try:        # one height and one baseline for every label of a scalable font
+        ascent, descent = font.getmetrics()
+        line = ascent + descent
+    except AttributeError:
+        line = None
+    strips = []
+    for text in labels:
+        left, top, right, bottom = (int(v) for v in font.getbbox(text)) if text else (0, 0, 0, 0)
+        if line is not None:
+            top, bottom = min(top, 0), max(bottom, line)
+        w, h = max(right - left, 1) + 2 * pad, max(bottom - top, 1) + 2 * pad
+        img = Image.new("L", (w, h), 0)
+        if text:
+            ImageDraw.Draw(img).text((pad - left, pad - top), text, fill=255, font=font)
+        strips.append(np.asarray(img, dtype=np.uint8))
+    width = max(s.shape[1] for s in strips)
+    height = sum(s.shape[0] for s in strips)
+    if width > 65535 or height > 65535:
+        raise ValueError(f"render_labels: the atlas would be {width}x{height}; an atlas is at most 65535 on a side")
+    atlas = np.zeros((height, width), np.uint8)
+    rects = np.zeros((len(strips), 4), np.int32)
+    v = 0
+    for i, s in enumerate(strips):
+        atlas[v:v + s.shape[0], :s.shape[1]] = s
+        rects[i] = (0, v, s.shape[1], s.shape[0])
+        v += s.shape[0]
+    return atlas, rects
+
+
+class LabelAtlas:
+    """render_labels, uploaded once: `.surface` (the Y surface RunBatch takes as `atlas`), `.rects` ((L, 4) int32 numpy,
+    (u, v, w, h) of each label) and `.labels`."""
+
+    def __init__(self, gpu_id: int, labels, font=None, pad: int = 1):
+        from .transfer import PyFrameUploader
+
+        self.labels = [str(t) for t in labels]
+        atlas, self.rects = render_labels(self.labels, font, pad)
+        self.surface = Surface.Make(F.Y, atlas.shape[1], atlas.shape[0], gpu_id)
+        ok, info = PyFrameUploader(gpu_id).Run(atlas.reshape(-1), self.surface)
+        if not ok:
+            raise RuntimeError(f"LabelAtlas: the upload failed ({info})")
 
 
 _ROT_FORMATS = [F.Y, F.GRAY12, F.RGB, F.BGR, F.RGB_PLANAR, F.YUV420, F.YUV422, F.YUV444, F.RGB_32F,
