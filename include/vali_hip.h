@@ -610,6 +610,77 @@ VALI_API int vali_annotate_batch_atlas(const vali_surface* frames, const vali_su
                                        const vali_cvt_params* params, void* workspace, size_t ws_bytes,
                                        vali_stream_t stream);
 
+/* ---- detections: a detector's raw head into device-held boxes in frame pixels ---------------
+ *
+ * boxes (n, k, 4) and scores (n, k, c), float32, float16 or bfloat16 each, with any element strides >= 0 (a transposed
+ * head, a broadcast), in the coordinates of the network's input; d_rects[i] is the record vali_*_preproc_roi_tensor
+ * placed frame i with.  The call issues FOUR launches whatever the data, allocates nothing and never synchronises: it
+ * can be captured and replayed after boxes, scores and d_rects were rewritten in place.  The reference has no such task.
+ * All arithmetic is IEEE float32, one rounding per operation, never a fused multiply-add; (float) of an integer rounds
+ * to nearest; sums of two int32 are formed in 64 bits.  Per frame i, with T = max_candidates and D = max_det:
+ *   1. record   src_w, src_h, dst_w or dst_h below 1: the frame has no detections.
+ *   2. score    s = -inf, cls = 0; for c = 0..C-1, v = (float)scores[i][k][c]: if v > s then s = v, cls = c (the lowest
+ *               class wins ties, NaN never wins).  Candidate k passes when s > score_thr.
+ *   3. box      (float) of the four values; VALI_DETECT_CXCYWH: x1 = cx - w * 0.5f, x2 = cx + w * 0.5f, y likewise.
+ *               Clipped to the placement: x1 = dst_x > x1 ? dst_x : x1, x2 = dst_x + dst_w < x2 ? dst_x + dst_w : x2, y
+ *               likewise (a NaN stays a NaN).  Dropped unless all four are finite and x2 > x1 && y2 > y1.
+ *   4. order    by s descending as floats (-0.0 equals 0.0), equal scores by k ascending; the first T go on, exactly.
+ *   5. NMS      greedy in that order: j is suppressed by a KEPT earlier i when (class_agnostic || cls_i == cls_j) and
+ *               inter > iou_thr * uni, with iw = max(min(x2i, x2j) - max(x1i, x1j), 0), ih likewise, inter = iw * ih,
+ *               a = (x2 - x1) * (y2 - y1), uni = (a_i + a_j) - inter: no division.  A suppressed candidate suppresses
+ *               nothing.  The first D kept are the frame's detections, counts[i] their number.
+ *   6. pixels   sx = (float)src_w / (float)dst_w, sy likewise; X1 = floor((x1 - dst_x) * sx + src_x), X2 = ceil((x2 -
+ *               dst_x) * sx + src_x), the multiply and the add rounded separately, Y likewise; clamped to [src_x, src_x +
+ *               src_w] and [src_y, src_y + src_h]; x = X1, w = max(X2 - X1, 1), y and h likewise (the maximum only
+ *               matters where float32 cannot tell the two edges apart); values beyond int32 saturate.
+ * Outputs, int32 rows of 8, each NULL or a device array that is rewritten in full by every call:
+ *   dets   (n * D) rows; row i * D + r is detection r of frame i: frame, x, y, w, h, class, the score's float32 bits, k.
+ *          An unused row is -1, 0, 0, 0, 0, 0, 0, 0.
+ *   counts n values.
+ *   rois   (n * D) rows x, y, w, h, crop[0..3]: vali_roi records of second-stage crops whose item i * D + r has frame i as
+ *          its source; an unused row is all zero (an empty item).
+ *   marks  R * n * D vali_mark rows, R = 3 with label_rects and 1 without, R * n * D <= VALI_MAX_MARKS.  Row i * D + r:
+ *          frame, x, y, w, h, VALI_MARK_BOX, thickness, colours[class % n_colours].  With (u, v, lw, lh) =
+ *          label_rects[class], row n * D + i * D + r: frame, x, y - lh, lw, lh, VALI_MARK_FILL, 0, that colour with its
+ *          alpha replaced by label_alpha; row 2 * n * D + i * D + r: frame, x, y - lh, lw, lh, VALI_MARK_STAMP,
+ *          u | v << 16, text_colour.  Rows of an unused detection, and the label rows of a class >= n_labels, are all zero.
+ * workspace: vali_detect_workspace_size(n, k, max_candidates) bytes of device memory, 16-byte aligned (0 for sizes outside
+ * the limits); its contents need not survive between calls.
+ * VALI_ERR_INVALID_ARG, before any device is touched: null in, params, d_rects, out or workspace; a null tensor pointer, a
+ * dtype outside the three, a pointer not aligned to its element, a stride outside 0..2^40; n outside 1..1024, k outside
+ * 1..2^20, c outside 1..4096, max_candidates outside 1..1024, max_det outside 1..max_candidates, n * max_det > 65535; a
+ * score_thr or iou_thr that is not finite; an unknown box_format; a workspace that is too small or misaligned; marks
+ * without colours (or n_colours < 1), with more than 4096 rows, a thickness below 1 or a label_alpha outside 0..255.
+ */
+#define VALI_DETECT_XYXY 0
+#define VALI_DETECT_CXCYWH 1
+typedef struct vali_detect_tensor {
+  const void* data;                      /* element (0, 0, 0) */
+  int32_t dtype;                         /* VALI_DTYPE_F32, _F16 or _BF16 */
+  int32_t reserved;
+  int64_t stride_n, stride_k, stride_c;  /* in elements, >= 0 */
+} vali_detect_tensor;                    /* 40 bytes */
+typedef struct vali_detect_in {
+  vali_detect_tensor boxes, scores;      /* (n, k, 4) and (n, k, c) */
+  int32_t n, k, c, reserved;
+} vali_detect_in;                        /* 96 bytes */
+typedef struct vali_detect_params {
+  int32_t max_candidates, max_det;
+  float score_thr, iou_thr;
+  int32_t class_agnostic, box_format;
+  int32_t crop[4];                       /* rois: the placement px, py, pw, ph of every row */
+  int32_t thickness, label_alpha, text_colour, n_colours, n_labels;  /* marks */
+} vali_detect_params;                    /* 60 bytes */
+typedef struct vali_detect_out {
+  int32_t *dets, *counts, *rois, *marks; /* device memory; each may be NULL */
+  const int32_t* colours;                /* device, n_colours packed colours (marks) */
+  const int32_t* label_rects;            /* device, n_labels rows u, v, w, h, or NULL (marks) */
+} vali_detect_out;                       /* 48 bytes */
+
+VALI_API size_t vali_detect_workspace_size(int n, int k, int max_candidates);
+VALI_API int vali_detect_select(const vali_detect_in* in, const vali_detect_params* params, const vali_roi* d_rects,
+                                const vali_detect_out* out, void* d_ws, size_t ws_bytes, vali_stream_t stream);
+
 /*
  * Rectangles of surfaces of ANY sizes as files, in one fixed set of launches.  Item i is rectangle rois[i] of the
  * surface d_src[i] (the same surface may stand behind any number of items); its file is byte for byte the file of

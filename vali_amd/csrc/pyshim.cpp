@@ -706,6 +706,48 @@ PYBIND11_MODULE(_vali_shim, m) {
         py::arg("descs"), py::arg("d_frames"), py::arg("format"), py::arg("d_marks"), py::arg("m"), py::arg("params"),
         py::arg("workspace"), py::arg("ws_bytes"), py::arg("stream"), py::arg("atlas") = py::none());
 
+  // detections: boxes / scores = (ptr, dtype, stride_n, stride_k, stride_c); everything else as in the header
+  m.def("detect_workspace_size", [](int n, int k, int max_candidates) {
+    return vali_detect_workspace_size(n, k, max_candidates);
+  });
+  m.attr("DETECT_XYXY") = (int)VALI_DETECT_XYXY;
+  m.attr("DETECT_CXCYWH") = (int)VALI_DETECT_CXCYWH;
+  m.def("detect_select",
+        [](const std::array<int64_t, 5>& boxes, const std::array<int64_t, 5>& scores, int n, int k, int c,
+           int max_candidates, int max_det, float score_thr, float iou_thr, int class_agnostic, int box_format,
+           const std::array<int32_t, 4>& crop, int thickness, int label_alpha, int text_colour, int n_colours,
+           int n_labels, uintptr_t d_rects, uintptr_t dets, uintptr_t counts, uintptr_t rois, uintptr_t marks,
+           uintptr_t colours, uintptr_t label_rects, uintptr_t workspace, size_t ws_bytes, uintptr_t stream) {
+          vali_detect_in in;
+          std::memset(&in, 0, sizeof(in));
+          const auto tensor = [](const std::array<int64_t, 5>& t) {
+            vali_detect_tensor d;
+            std::memset(&d, 0, sizeof(d));
+            d.data = P((uintptr_t)t[0]);
+            d.dtype = (int32_t)t[1];
+            d.stride_n = t[2]; d.stride_k = t[3]; d.stride_c = t[4];
+            return d;
+          };
+          in.boxes = tensor(boxes);
+          in.scores = tensor(scores);
+          in.n = n; in.k = k; in.c = c;
+          vali_detect_params p;
+          std::memset(&p, 0, sizeof(p));
+          p.max_candidates = max_candidates; p.max_det = max_det;
+          p.score_thr = score_thr; p.iou_thr = iou_thr;
+          p.class_agnostic = class_agnostic; p.box_format = box_format;
+          for (int i = 0; i < 4; ++i)
+            p.crop[i] = crop[i];
+          p.thickness = thickness; p.label_alpha = label_alpha; p.text_colour = text_colour;
+          p.n_colours = n_colours; p.n_labels = n_labels;
+          vali_detect_out o;
+          o.dets = (int32_t*)P(dets); o.counts = (int32_t*)P(counts); o.rois = (int32_t*)P(rois);
+          o.marks = (int32_t*)P(marks);
+          o.colours = (const int32_t*)P(colours); o.label_rects = (const int32_t*)P(label_rects);
+          py::gil_scoped_release nogil;
+          return vali_detect_select(&in, &p, (const vali_roi*)P(d_rects), &o, P(workspace), ws_bytes, P(stream));
+        });
+
   // ---- JPEG decoder: host-side parser and sizes, then the batched decoder --------------------------------------
   py::class_<JpegInfo>(m, "JpegInfo")
       .def_property_readonly("width", [](const JpegInfo& j) { return j.f.width; })
