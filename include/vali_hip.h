@@ -681,6 +681,65 @@ VALI_API size_t vali_detect_workspace_size(int n, int k, int max_candidates);
 VALI_API int vali_detect_select(const vali_detect_in* in, const vali_detect_params* params, const vali_roi* d_rects,
                                 const vali_detect_out* out, void* d_ws, size_t ws_bytes, vali_stream_t stream);
 
+/* ---- instance masks: a segmentation head's prototypes and coefficients painted onto frames ---------------
+ *
+ * protos (n, m, hp, wp) and coeffs (n, k, m), float32, float16 or bfloat16 each (protos: x stride 1, the n, m and y
+ * strides any values >= 0; coeffs: any element strides >= 0), d_dets the (n * D) rows of vali_detect_select (frame, x, y,
+ * w, h, class, score bits, k; D = max_det) and d_rects[i] the record frame i was placed with.  The masks of the rows are
+ * blended IN PLACE onto n frames of one format (the six of vali_annotate_batch, under its rules for frames) in TWO
+ * launches whatever the data; nothing is allocated and nothing synchronises, so the call can be captured and replayed
+ * after protos, coeffs, d_dets, d_rects and the frames were rewritten in place.  The reference has no such task.
+ * All arithmetic is IEEE float32, one rounding per operation, never a fused multiply-add; (float) of an integer rounds
+ * to nearest.  Frame i is W x H with record src_x, src_y, src_w, src_h, dst_x, dst_y, dst_w, dst_h; row i * D + r:
+ *   1. skipped  when its frame field is not i, w < 1 or h < 1, k is outside 0..K-1, src_w, src_h, dst_w or dst_h is below
+ *               1, or the box [x, x + w) x [y, y + h) does not meet the frame.  Every int32 value is handled;
+ *               intersections are formed in 64 bits.
+ *   2. logits   for every prototype pixel acc = 0; for j = 0..m-1: acc = acc + (float)coeffs[i][k][j] *
+ *               (float)protos[i][j][yp][xp], the product and the sum rounded separately, in this order: L[yp][xp].
+ *   3. sample   of frame pixel px: g = (((float)px + 0.5f) - (float)src_x) * ((float)dst_w / (float)src_w) + (float)dst_x,
+ *               fx = g * ((float)wp / (float)net_w) - 0.5f, x0 = floorf(fx), tx = fx - x0; x0 is clamped to [-1, wp] as
+ *               a float and converted; ix0 = clamp(x0, 0, wp - 1), ix1 = clamp(x0 + 1, 0, wp - 1) (edge replication).
+ *               y likewise with src_y, dst_h / src_h, dst_y, hp / net_h: iy0, iy1, ty.
+ *   4. inside   top = L[iy0][ix0] + tx * (L[iy0][ix1] - L[iy0][ix0]), bot the same on row iy1, v = top + ty * (bot - top):
+ *               the pixel is in the mask when v > 0 (a NaN is never in): the logits are upsampled, then compared.
+ *   5. extent   only frame pixels inside box ^ frame can be in the mask; the box is NOT snapped on 4:2:0 frames.
+ *   6. blend    VALI_MARK_STAMP's with coverage 255 inside the mask and 0 outside: k = cov for full-resolution channels,
+ *               (the four luma coverages + 2) >> 2 for a 4:2:0 chroma sample, a_eff = (k * a + 127) / 255,
+ *               v = (v * (255 - a_eff) + c * a_eff + 127) / 255, c as for VALI_MARK_FILL (params->rgb2yuv for YUV
+ *               formats) of the colour d_colours[class mod n_colours] (the non-negative remainder), a its alpha or, with
+ *               alpha in 0..255, alpha (alpha = -1 keeps the colour's).  Samples with k = 0 stay unwritten.
+ *   7. order    the rows of a frame are applied in row order: the result is bit for bit that of
+ *               vali_annotate_batch_atlas for STAMP rows over an atlas holding each mask as 255 / 0.  Nothing outside a
+ *               plane's image area is written; frames and tiles no mask meets are neither read nor written.
+ * Limits: n 1..1024, m 1..64, hp and wp 1..1024, k 1..2^20, D 1..1024 with n * D <= 65535, net_w and net_h 1..65535.
+ * d_ws: vali_mask_workspace_size(n, max_det, hp, wp) = n * max_det * hp * wp * 4 bytes of device memory, 16-byte
+ * aligned (0 for sizes outside the limits); row i * D + r has the hp x wp float32 slot r of frame i, of which only the
+ * range its box can sample is written and read.  Its contents need not survive between calls.
+ * VALI_ERR_INVALID_ARG, before any device is touched: null frames, d_frames, in, d_dets, d_rects, d_colours or d_ws, null
+ * params for a YUV format; a null tensor pointer, a dtype outside the three, a pointer not aligned to its element, a stride
+ * outside 0..2^40; a limit above broken; n_colours < 1; alpha outside -1..255; d_dets, d_rects or d_colours not 4-byte
+ * aligned; a workspace that is too small or not 16-byte aligned; a frame that breaks vali_annotate_batch's rules.
+ * VALI_ERR_UNSUPPORTED for a format outside the six.
+ */
+typedef struct vali_mask_tensor {
+  const void* data;                      /* element (0, 0, 0, 0) */
+  int32_t dtype;                         /* VALI_DTYPE_F32, _F16 or _BF16 */
+  int32_t reserved;
+  int64_t stride_n, stride_m, stride_y;  /* in elements, >= 0; the x stride is 1 */
+} vali_mask_tensor;                      /* 40 bytes */
+typedef struct vali_mask_in {
+  vali_mask_tensor protos;               /* (n, m, hp, wp) */
+  vali_detect_tensor coeffs;             /* (n, k, m) */
+  int32_t m, hp, wp, k;
+  int32_t max_det, net_w, net_h, reserved;
+} vali_mask_in;                          /* 112 bytes */
+
+VALI_API size_t vali_mask_workspace_size(int n, int max_det, int hp, int wp);
+VALI_API int vali_mask_paint(const vali_surface* frames, const vali_surface* d_frames, int n, int format,
+                             const vali_mask_in* in, const int32_t* d_dets, const vali_roi* d_rects,
+                             const int32_t* d_colours, int n_colours, int alpha, const vali_cvt_params* params,
+                             void* d_ws, size_t ws_bytes, vali_stream_t stream);
+
 /*
  * Rectangles of surfaces of ANY sizes as files, in one fixed set of launches.  Item i is rectangle rois[i] of the
  * surface d_src[i] (the same surface may stand behind any number of items); its file is byte for byte the file of

@@ -23,6 +23,7 @@ if not _BUILDING:
                         PySurfaceResizer, PySurfaceRotator, PySurfaceUD, RoiBatch, SurfaceBatch, TensorBatch,
                         letterbox_rect, pack_colour, pack_uv, render_labels)
     from .detect import DetectionStyle, PyDetectionSelector, SelectBatch
+    from .mask import MaskBatch, PyInstanceMasker
     from .pipeline import BatchedFramePipeline, broadcast_coefficients, shard_frames
     from .transfer import PyFrameUploader, PySurfaceDownloader
     from . import tuning

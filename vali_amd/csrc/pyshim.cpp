@@ -748,6 +748,36 @@ PYBIND11_MODULE(_vali_shim, m) {
           return vali_detect_select(&in, &p, (const vali_roi*)P(d_rects), &o, P(workspace), ws_bytes, P(stream));
         });
 
+  // instance masks: protos = (ptr, dtype, stride_n, stride_m, stride_y), coeffs = (ptr, dtype, stride_n, stride_k,
+  // stride_m); descs = the host copy of the descriptors in d_frames; everything else as in the header
+  m.def("mask_workspace_size", [](int n, int max_det, int hp, int wp) {
+    return vali_mask_workspace_size(n, max_det, hp, wp);
+  });
+  m.def("mask_paint",
+        [](const std::vector<SurfaceDesc>& descs, uintptr_t d_frames, int format, const std::array<int64_t, 5>& protos,
+           const std::array<int64_t, 5>& coeffs, int mm, int hp, int wp, int k, int max_det, int net_w, int net_h,
+           uintptr_t d_dets, uintptr_t d_rects, uintptr_t d_colours, int n_colours, int alpha, const CvtParams* p,
+           uintptr_t workspace, size_t ws_bytes, uintptr_t stream) {
+          std::vector<vali_surface> host(descs.size());
+          for (size_t i = 0; i < descs.size(); ++i)
+            host[i] = descs[i].s;
+          vali_mask_in in;
+          std::memset(&in, 0, sizeof(in));
+          in.protos.data = P((uintptr_t)protos[0]);
+          in.protos.dtype = (int32_t)protos[1];
+          in.protos.stride_n = protos[2]; in.protos.stride_m = protos[3]; in.protos.stride_y = protos[4];
+          in.coeffs.data = P((uintptr_t)coeffs[0]);
+          in.coeffs.dtype = (int32_t)coeffs[1];
+          in.coeffs.stride_n = coeffs[2]; in.coeffs.stride_k = coeffs[3]; in.coeffs.stride_c = coeffs[4];
+          in.m = mm; in.hp = hp; in.wp = wp; in.k = k;
+          in.max_det = max_det; in.net_w = net_w; in.net_h = net_h;
+          py::gil_scoped_release nogil;
+          return vali_mask_paint(host.empty() ? nullptr : host.data(), (const vali_surface*)P(d_frames), (int)host.size(),
+                                 format, &in, (const int32_t*)P(d_dets), (const vali_roi*)P(d_rects),
+                                 (const int32_t*)P(d_colours), n_colours, alpha, p ? &p->p : nullptr, P(workspace),
+                                 ws_bytes, P(stream));
+        });
+
   // ---- JPEG decoder: host-side parser and sizes, then the batched decoder --------------------------------------
   py::class_<JpegInfo>(m, "JpegInfo")
       .def_property_readonly("width", [](const JpegInfo& j) { return j.f.width; })

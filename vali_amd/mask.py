@@ -1,0 +1,298 @@
+"""PyInstanceMasker: a segmentation head's prototypes and coefficients -> instance masks blended onto frames, on the GPU
+(vali_mask_paint).
+
+The mask of a detection is coeffs[k] . protos, upsampled bilinearly to the frame and thresholded at 0; the masks of the
+selector's detections are blended in place, in row order, in two launches whatever the data: no box, no class id and no
+mask is ever on the host.  The definition, sample for sample, is in include/vali_hip.h; tests/mask_model.py restates it
+in numpy.
+"""
+from __future__ import annotations
+
+import operator
+from typing import Sequence, Tuple
+
+from ._native import shim
+from .detect import _DTYPES, _CAI, _device_i32, _host_rects, _is_device
+from .enums import DLDeviceType, PixelFormat as F, TaskExecInfo
+from .runtime import is_capturing
+from .surface import Surface
+from .tasks import (PySurfaceAnnotator, PySurfacePostprocessor, _S_UNSUPP_CC, _SurfaceTask, _device_rects, _params,
+                    _status)
+
+MAX_FRAMES, MAX_PROTOS, MAX_SIDE, MAX_HEAD, MAX_DET, MAX_NET = 1024, 64, 1024, 1 << 20, 1024, 65535
+
+
+def _layout(who, dims, shape, strides, code, bits):
+    """a float32, float16 or bfloat16 view of len(dims) dimensions with element strides >= 0: (dtype code, shape, strides)"""
+    dtype = _DTYPES.get((int(code), int(bits)))
+    if dtype is None:
+        raise ValueError(f"{who}: the dtype must be float32, float16 or bfloat16 (DLPack code {code}, {bits} bits)")
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != len(dims):
+        raise ValueError(f"{who}: need a {len(dims)}-D tensor ({', '.join(dims)}), got {len(shape)}-D {shape}")
+    if strides is None:
+        strides, step = [], 1
+        for size in reversed(shape):
+            strides.insert(0, step)
+            step *= size
+    strides = tuple(int(v) for v in strides)
+    if len(strides) != len(shape):
+        raise ValueError(f"{who}: {len(strides)} strides for a {len(shape)}-D tensor")
+    if any(v < 0 for v in strides):
+        raise ValueError(f"{who}: negative strides {strides} (a flipped view) are not supported")
+    if any(v > 1 << 40 for v in strides):
+        raise ValueError(f"{who}: strides {strides} beyond 2^40 elements")
+    return dtype[1], shape, strides
+
+
+def protos_layout(shape, strides, code, bits):
+    """The rules for `protos`, without a device: (N, M, Hp, Wp) with an x stride of 1.  Returns (dtype code, shape,
+    strides); ValueError, naming what is wrong, otherwise."""
+    code, shape, strides = _layout("protos", ("N", "M", "Hp", "Wp"), shape, strides, code, bits)
+    n, m, hp, wp = shape
+    if not 1 <= n <= MAX_FRAMES:
+        raise ValueError(f"protos: N = {n} is outside 1..{MAX_FRAMES}")
+    if not 1 <= m <= MAX_PROTOS:
+        raise ValueError(f"protos: M = {m} is outside 1..{MAX_PROTOS}")
+    if not (1 <= hp <= MAX_SIDE and 1 <= wp <= MAX_SIDE):
+        raise ValueError(f"protos: Hp x Wp = {hp} x {wp} is outside 1..{MAX_SIDE}")
+    if wp > 1 and strides[3] != 1:
+        raise ValueError(f"protos: the x stride must be 1, got {strides[3]}")
+    return code, shape, strides
+
+
+def coeffs_layout(shape, strides, code, bits):
+    """The rules for `coeffs`, without a device: (N, K, M) with any element strides >= 0"""
+    code, shape, strides = _layout("coeffs", ("N", "K", "M"), shape, strides, code, bits)
+    n, k, m = shape
+    if not 1 <= n <= MAX_FRAMES:
+        raise ValueError(f"coeffs: N = {n} is outside 1..{MAX_FRAMES}")
+    if not 1 <= k <= MAX_HEAD:
+        raise ValueError(f"coeffs: K = {k} is outside 1..2^20")
+    if not 1 <= m <= MAX_PROTOS:
+        raise ValueError(f"coeffs: M = {m} is outside 1..{MAX_PROTOS}")
+    return code, shape, strides
+
+
+def mask_spec(n_frames, protos_view, coeffs_view, max_det=100, net_size=(640, 640)):
+    """What Prepare checks once the tensors are seen, without a device: views are (dtype code, shape, strides) as
+    protos_layout / coeffs_layout return them.  Returns (n, m, hp, wp, k, D, net_w, net_h)."""
+    (_, (n, m, hp, wp), _), (_, (n2, k, m2), _) = protos_view, coeffs_view
+    if n != n2 or m != m2:
+        raise ValueError(f"protos and coeffs disagree: protos are ({n}, {m}, {hp}, {wp}), coeffs ({n2}, {k}, {m2})")
+    if n_frames != n:
+        raise ValueError(f"frames: {n_frames} surfaces for tensors of N = {n}")
+    D = operator.index(max_det)
+    if not 1 <= D <= MAX_DET:
+        raise ValueError(f"max_det = {D} is outside 1..{MAX_DET}")
+    if n * D > 65535:
+        raise ValueError(f"N * max_det = {n * D} exceeds 65535")
+    try:
+        net_w, net_h = (operator.index(v) for v in net_size)
+    except (TypeError, ValueError):
+        raise ValueError("net_size: two integers (width, height) of the network's input") from None
+    if not (1 <= net_w <= MAX_NET and 1 <= net_h <= MAX_NET):
+        raise ValueError(f"net_size = ({net_w}, {net_h}) is outside 1..{MAX_NET}")
+    return n, m, hp, wp, k, D, net_w, net_h
+
+
+def paint_spec(colours, alpha):
+    """What Run checks of its host arguments: (host colours or None for a device tensor, alpha as the C ABI takes it)"""
+    a = -1
+    if alpha is not None:
+        a = operator.index(alpha)
+        if not 0 <= a <= 255:
+            raise ValueError(f"alpha = {a} is outside 0..255 (None keeps the colours' own)")
+    if _is_device(colours):
+        return None, a
+    try:
+        host = [operator.index(v) for v in colours]
+    except TypeError:
+        raise ValueError("colours: an int32 device tensor or a sequence of packed colours (pack_colour)") from None
+    if not host:
+        raise ValueError("colours: at least one colour")
+    if any(not -(1 << 31) <= v < (1 << 31) for v in host):
+        raise ValueError("colours: every colour must fit an int32 (pack_colour)")
+    return host, a
+
+
+def _view(who, layout_of, t, gpu_id):
+    """(ptr, dtype code, shape, strides, holder) of a device tensor on `gpu_id`"""
+    if hasattr(t, "__dlpack__"):
+        info, holder = shim.dlpack_import(t.__dlpack__())
+        if info["lanes"] != 1:
+            raise ValueError(f"{who}: vector dtypes are not supported")
+        code, shape, strides = layout_of(info["shape"], info["strides"], info["code"], info["bits"])
+        if info["device_type"] not in (int(DLDeviceType.kDLROCM), int(DLDeviceType.kDLCUDA)):
+            raise ValueError(f"{who}: the tensor must live on the GPU")
+        ptr, device = int(info["ptr"]), int(info["device_id"])
+    elif hasattr(t, "__cuda_array_interface__"):
+        cai = t.__cuda_array_interface__
+        if cai["typestr"] not in _CAI:
+            raise ValueError(f"{who}: the dtype must be float32 or float16 through __cuda_array_interface__ (bfloat16: "
+                             f"__dlpack__), got {cai['typestr']}")
+        dl_code, bits = _CAI[cai["typestr"]]
+        strides = cai.get("strides")
+        if strides is not None:
+            if any(int(v) % (bits // 8) for v in strides):
+                raise ValueError(f"{who}: strides that are no multiple of the element size")
+            strides = tuple(int(v) // (bits // 8) for v in strides)
+        code, shape, strides = layout_of(cai["shape"], strides, dl_code, bits)
+        ptr, holder = int(cai["data"][0]), t
+        dev = getattr(t, "device", None)
+        if getattr(dev, "type", "cuda") != "cuda":
+            raise ValueError(f"{who}: the tensor must live on the GPU")
+        device = dev.index if dev is not None and dev.index is not None else shim.ptr_device(ptr)
+    else:
+        raise ValueError(f"{who}: a device tensor with __dlpack__ or __cuda_array_interface__")
+    if device != gpu_id:
+        raise ValueError(f"{who}: the tensor is on device {device}, the task on {gpu_id}")
+    return ptr, code, shape, strides, holder
+
+
+class MaskBatch:
+    """What PyInstanceMasker.Run works on: the frames, the head's two tensors, the selector's dets and the workspace,
+    checked and set up once (PyInstanceMasker.Prepare).  Keeps the surfaces and tensors alive."""
+
+    def __init__(self, gpu_id: int, stream: int, frames: Sequence[Surface], protos, coeffs, dets, max_det=100,
+                 net_size=(640, 640)):
+        frames = list(frames)
+        fmt = None
+        for i, d in enumerate(frames):
+            if d is None or d.IsEmpty:
+                raise ValueError(f"MaskBatch: surface {i} is empty")
+            if d.Format not in PySurfaceAnnotator._FORMATS:
+                raise ValueError(f"MaskBatch: surface {i} has format {d.Format!r}; supported: "
+                                 f"{', '.join(f.name for f in PySurfaceAnnotator._FORMATS)}")
+            if fmt is not None and d.Format != fmt:
+                raise ValueError(f"MaskBatch: surface {i} has format {d.Format!r}, surface 0 {fmt!r}: one format per batch")
+            fmt = d.Format
+            if fmt in (F.NV12, F.YUV420) and (d.Width | d.Height) & 1:
+                raise ValueError(f"MaskBatch: surface {i}: {fmt.name} is 4:2:0 and needs an even width and height, "
+                                 f"got {d.Width}x{d.Height}")
+            dev = getattr(d, "DeviceId", gpu_id)
+            if dev != gpu_id:
+                raise ValueError(f"MaskBatch: surface {i} is on device {dev}, the task on {gpu_id}")
+        pp, pcode, pshape, pstr, ph = _view("protos", protos_layout, protos, gpu_id)
+        cp, ccode, cshape, cstr, ch = _view("coeffs", coeffs_layout, coeffs, gpu_id)
+        n, m, hp, wp, k, D, net_w, net_h = mask_spec(len(frames), (pcode, pshape, pstr), (ccode, cshape, cstr), max_det,
+                                                     net_size)
+        if dets is None:
+            raise ValueError(f"dets: an int32 ({n * D}, 8) device tensor is required")
+        self.d_dets, dh = _device_i32("dets", dets, (n * D, 8), gpu_id)
+        if is_capturing(gpu_id, stream):
+            raise RuntimeError("MaskBatch: cannot be created while the stream is capturing -- Prepare() before the "
+                               "StreamCapture block and Keep() the batch with the capture")
+        self.gpu_id, self._stream = gpu_id, stream
+        self.n, self.m, self.hp, self.wp, self.k, self.D = n, m, hp, wp, k, D
+        self.net_w, self.net_h = net_w, net_h
+        self.format = fmt
+        self.sizes = [(d.Width, d.Height) for d in frames]
+        self.descs = [d.desc() for d in frames]
+        self.protos = (pp, pcode, pstr[0], pstr[1], pstr[2])
+        self.coeffs = (cp, ccode, *cstr)
+        self._keep = [frames, ph, ch, dh]
+        self._rects_keep = self._colours_keep = None
+        self._colours = None        # (host values, device pointer) of the last host colours
+        self.d_frames = self.d_ws = self.d_rects = self.d_colours = 0
+        self.ws_bytes = shim.mask_workspace_size(n, D, hp, wp)
+        self.d_frames = shim.descs_upload(gpu_id, self.descs, stream)
+        self.d_ws = shim.mem_alloc(gpu_id, self.ws_bytes)
+        self.d_rects = shim.mem_alloc(gpu_id, 32 * n)
+
+    def __len__(self):
+        return self.n
+
+    def __del__(self):
+        if getattr(self, "d_frames", 0):
+            try:    # a launch issued on the batch's stream may still be using the arrays
+                shim.stream_sync(self.gpu_id, self._stream)
+            except Exception:
+                pass
+        for name in ("d_frames", "d_ws", "d_rects", "d_colours"):
+            p = getattr(self, name, 0)
+            if p:
+                try:
+                    shim.mem_free(self.gpu_id, p)
+                except Exception:
+                    pass
+                setattr(self, name, 0)
+
+
+class PyInstanceMasker(_SurfaceTask):
+    """The instance masks of a segmentation network (YOLOv8-seg, YOLACT and their descendants) blended IN PLACE onto a
+    batch of NV12, YUV420, YUV444, RGB, BGR or RGB_PLANAR frames of any sizes, in two launches whatever the data, with
+    nothing allocated and no synchronisation, so the call can be captured and replayed after its tensors and frames were
+    rewritten in place (vali_mask_paint).
+
+    mb = Prepare(frames, protos, coeffs, dets, max_det=100, net_size=(640, 640)): `protos` (N, M, Hp, Wp) and `coeffs`
+    (N, K, M) are float32, float16 or bfloat16 GPU tensors (`__dlpack__`, or `__cuda_array_interface__` for float32 and
+    float16); protos has an x stride of 1 and any n, m, y strides >= 0 (a (1, M, Hp, Wp) tensor expanded over N), coeffs
+    any element strides >= 0 -- a YOLOv8-seg head (N, 4 + C + M, K) goes in as pred[:, 4 + C:].transpose(1, 2), without a
+    copy.  `dets` is PyDetectionSelector's (N * max_det, 8) int32 tensor, read on the device only: row i * max_det + r
+    belongs to frame i and its `k` picks the coefficients.  N 1..1024, M 1..64, Hp and Wp 1..1024, K 1..2^20, max_det
+    1..1024, N * max_det <= 65535, net_size (the network input's width and height) 1..65535.
+
+    Run(mb, rects, colours, alpha=128, cc_ctx=None): `rects` is the (N, 8) int32 record array the frames were placed with,
+    handled as PyDetectionSelector.Run handles it; `colours` packed colours (pack_colour) as a host sequence, uploaded
+    when it changes, or an int32 device tensor: a detection is painted in colours[class % len(colours)] at `alpha`
+    (None: the colour's own).  `cc_ctx` picks the RGB -> YUV matrix as PySurfaceAnnotator.RunBatch does.  The mask of a
+    detection exists inside its box only; masks are applied in row order.
+    """
+
+    def Prepare(self, frames: Sequence[Surface], protos, coeffs, dets, max_det=100, net_size=(640, 640)) -> MaskBatch:
+        return MaskBatch(self._gpu_id, self._stream, frames, protos, coeffs, dets, max_det, net_size)
+
+    def RunAsync(self, mb: MaskBatch, rects, colours, alpha=128, cc_ctx=None) -> Tuple[bool, TaskExecInfo]:
+        if not isinstance(mb, MaskBatch):
+            raise ValueError("Run: pass a MaskBatch (Prepare)")
+        host, a = paint_spec(colours, alpha)
+        params = None
+        if mb.format in (F.NV12, F.YUV420, F.YUV444):
+            mat = PySurfacePostprocessor.Matrix(cc_ctx)
+            if mat is None:
+                return _S_UNSUPP_CC.success, _S_UNSUPP_CC.info
+            params = _params(rgb2yuv=mat)
+        import array
+
+        if host is None:
+            shape = tuple(int(v) for v in (colours.__cuda_array_interface__["shape"]
+                                           if hasattr(colours, "__cuda_array_interface__") else colours.shape))
+            if len(shape) != 1 or shape[0] < 1:
+                raise ValueError(f"colours: need an int32 tensor of shape (n,), n >= 1, got {shape}")
+            dc, mb._colours_keep = _device_i32("colours", colours, shape, self._gpu_id)
+            nc = shape[0]
+        else:
+            if mb._colours is None or mb._colours[0] != host:
+                if is_capturing(self._gpu_id, self._stream):
+                    raise RuntimeError("PyInstanceMasker: host colours cannot be uploaded while the stream is capturing "
+                                       "-- Run once with them before the capture, or pass a device tensor")
+                buf = array.array("i", host)
+                shim.stream_sync(self._gpu_id, self._stream)      # a launch may still read the colours it replaces
+                if mb.d_colours:
+                    shim.mem_free(self._gpu_id, mb.d_colours)
+                    mb.d_colours = 0
+                mb.d_colours = shim.mem_alloc(self._gpu_id, 4 * len(host))
+                shim.memcpy2d_async(self._gpu_id, mb.d_colours, 4 * len(host), buf.buffer_info()[0], 4 * len(host),
+                                    4 * len(host), 1, 0, self._stream)
+                shim.stream_sync(self._gpu_id, self._stream)      # `buf` goes with this call
+                mb._colours = (host, mb.d_colours)
+            dc, nc = mb.d_colours, len(host)
+        if _is_device(rects):
+            d_rects, mb._rects_keep = _device_rects(rects, mb.n, self._gpu_id)
+        else:
+            rows = _host_rects(rects, mb.n)
+            buf = array.array("i", [v for r in rows for v in r])
+            nbytes = 32 * mb.n
+            shim.memcpy2d_async(self._gpu_id, mb.d_rects, nbytes, buf.buffer_info()[0], nbytes, nbytes, 1, 0, self._stream)
+            shim.stream_sync(self._gpu_id, self._stream)      # `buf` goes with this call
+            d_rects = mb.d_rects
+        d = _status(shim.mask_paint(mb.descs, mb.d_frames, int(mb.format), mb.protos, mb.coeffs, mb.m, mb.hp, mb.wp, mb.k,
+                                    mb.D, mb.net_w, mb.net_h, mb.d_dets, d_rects, dc, nc, a, params, mb.d_ws, mb.ws_bytes,
+                                    self._stream))
+        return d.success, d.info
+
+    def Run(self, mb: MaskBatch, rects, colours, alpha=128, cc_ctx=None) -> Tuple[bool, TaskExecInfo]:
+        r = self.RunAsync(mb, rects, colours, alpha, cc_ctx)
+        self._sync()
+        return r
