@@ -11,7 +11,7 @@ YUV = ("NV12", "YUV420", "YUV444")
 S420 = ("NV12", "YUV420")
 NONE, BOX, FILL, PIXELATE = 0, 1, 2, 3
 CELLS = (4, 8, 16, 32)
-TILE = 64          # the kernel's tile side (vali_amd/csrc/annotate.hip: kTile)
+TILE = 64          # the kernel's tile side (vali_amd/csrc/tile_paint.hpp: kTile)
 MAX_MARKS = 4096
 
 

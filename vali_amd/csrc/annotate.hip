@@ -25,39 +25,20 @@
 // barriers.  Every branch on the mark kind is workgroup-uniform; the mark records are read at a uniform index.
 //
 // Stamps (vali_annotate_batch_atlas, VALI_MARK_STAMP) blend the mark's colour with a per-pixel weight from a coverage
-// atlas: lane-local like FILL (stamp_piece), the lane reads the coverage bytes its pieces need straight from the atlas,
-// which is small, re-read by many tiles and therefore served by the L2.  k_annotate<FMT, true> holds that path; a call
-// without an atlas launches k_annotate<FMT, false>, which is the kernel as it was before stamps existed.
-#include "common.hpp"
-#include "dev_util.hpp"
+// atlas: lane-local like FILL (cover_piece over a StampCov), the lane reads the coverage bytes its pieces need straight
+// from the atlas, which is small, re-read by many tiles and therefore served by the L2.  k_annotate<FMT, true> holds that
+// path; a call without an atlas launches k_annotate<FMT, false>, which is the kernel as it was before stamps existed.
+//
+// The formats and the frame rules, the tile's pieces, the hit list and the coverage blend are tile_paint.hpp's, shared
+// with mask.hip; here are the marks, FILL / BOX, PIXELATE and the atlas reads.
+#include "tile_paint.hpp"
 
 namespace vali {
 namespace {
 
-constexpr int kTile = 64;                               // luma pixels a side
 constexpr int kMaxMarks = VALI_MAX_MARKS;
 constexpr size_t kBinBytes = 16 + (size_t)kMaxMarks * 2;  // per frame: the count, then uint16 row indices in row order
 constexpr int kCells = (kTile / 4) * (kTile / 4) * 3;   // cell sums of a tile: 16 x 16 cells of 4, three channels
-
-enum AnnFmt : int { A_NV12 = 0, A_YUV420 = 1, A_YUV444 = 2, A_RGB = 3, A_BGR = 4, A_RGBP = 5 };
-
-constexpr bool a_is420(int f) { return f == A_NV12 || f == A_YUV420; }
-constexpr bool a_isyuv(int f) { return f == A_NV12 || f == A_YUV420 || f == A_YUV444; }
-
-// A lane's share of the tile: piece (lane + first) of plane `plane`, whose bytes interleave `nc` channels starting with
-// colour channel c0 (0, 1, 2 = Y, U, V or the format's first, second, third stored colour) at 1 >> sh samples per pixel
-struct Slot {
-  int plane, nc, sh, c0, first;
-};
-constexpr int nslots(int f) { return f == A_NV12 ? 2 : 3; }
-constexpr Slot slot_of(int f, int s) {
-  return (f == A_RGB || f == A_BGR) ? Slot{0, 3, 0, 0, s * kBlock}
-         : f == A_NV12              ? (s == 0 ? Slot{0, 1, 0, 0, 0} : Slot{1, 2, 1, 1, 0})
-         : f == A_YUV420            ? Slot{s, 1, s ? 1 : 0, s, 0}
-                                    : Slot{s, 1, 0, s, 0};
-}
-// the subsampling of colour channel c
-constexpr int chan_shift(int f, int c) { return a_is420(f) && c > 0 ? 1 : 0; }
 
 // A sanitised row: what it paints, clipped to the frame (all values in 0 .. W resp. 0 .. H)
 struct Mark {
@@ -80,8 +61,6 @@ __device__ __forceinline__ void load_mark(const vali_mark* marks, int i, int (&r
   r[0] = (int)a.x, r[1] = (int)a.y, r[2] = (int)a.z, r[3] = (int)a.w;
   r[4] = (int)b.x, r[5] = (int)b.y, r[6] = (int)b.z, r[7] = (int)b.w;
 }
-
-__device__ __forceinline__ int clampi(long long v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : (int)v; }
 
 // false: the row is skipped (the rules of include/vali_hip.h; the frame index is the caller's to check).  AW x AH: the
 // atlas, 0 x 0 without one -- VALI_MARK_STAMP is then an unknown kind
@@ -144,28 +123,6 @@ __device__ __forceinline__ bool mark_meets_tile(const Mark& m, int tx0, int ty0,
   return !(tx0 >= m.ix0 && tx1 <= m.ix1 && ty0 >= m.iy0 && ty1 <= m.iy1);
 }
 
-// Ordered compaction over the workgroup: the flagged lanes' values go to out[base ...] in lane order; returns the new
-// end.  Every lane of the workgroup calls it.
-__device__ __forceinline__ int compact_put(bool flag, int value, uint16_t* out, int base, int* wtot) {
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const unsigned long long b = __ballot(flag);
-  const int before = __popcll(b & ((1ull << lane) - 1ull));
-  if (lane == 0)
-    wtot[wave] = __popcll(b);
-  __syncthreads();
-  int off = base, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kWavesPerBlock; ++w) {
-    const int c = wtot[w];
-    off += w < wave ? c : 0;
-    tot += c;
-  }
-  if (flag)
-    out[off + before] = (uint16_t)value;
-  __syncthreads();
-  return base + tot;
-}
-
 // ---- launch 1: the rows of each frame ---------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kBlock) k_annotate_bin(const vali_surface* __restrict__ d_frames,
                                                          const vali_mark* __restrict__ marks, int m, int is420,
@@ -203,41 +160,6 @@ struct StampAtlas {
   const uint8_t* p;
   int pitch, w, h;
 };
-
-// what a lane keeps of one of its pieces
-struct Piece {
-  uint8_t* p;  // where it lives
-  int n;       // bytes of it inside the image area: 0 (none: the lane has no such piece) .. 16
-  int y;       // its row, in samples of its plane
-  int bx;      // its first byte within the plane's row
-  int lbx;     // ... and within the tile's row
-};
-
-// t / 255 for 0 <= t < 65536
-__device__ __forceinline__ u32 div255(u32 t) { return (t * 0x8081u) >> 23; }
-
-__device__ __forceinline__ float dot_rgb(const float (&m)[4], float r, float g, float b) {
-  return __builtin_fmaf(m[2], b, __builtin_fmaf(m[1], g, __builtin_fmaf(m[0], r, m[3])));
-}
-
-// the colour of byte b of a piece is c[b % nc]: packed RGB pieces start at any of the three channels
-template <int FMT, int S>
-__device__ __forceinline__ void piece_colours(int lbx, const u32 (&col)[3], u32 (&c)[3]) {
-  constexpr Slot sl = slot_of(FMT, S);
-  constexpr int nc = sl.nc;
-  if constexpr (nc == 3) {
-    // (shifts of one packed word: a select chain over col[] becomes a table in scratch memory)
-    const u32 ch0 = (u32)lbx % 3u;
-    const unsigned long long pk = (unsigned long long)(col[0] | col[1] << 8 | col[2] << 16 | col[0] << 24) |
-                                  (unsigned long long)col[1] << 32;
-    c[0] = (u32)(pk >> (8u * ch0)) & 0xffu, c[1] = (u32)(pk >> (8u * ch0 + 8u)) & 0xffu;
-    c[2] = (u32)(pk >> (8u * ch0 + 16u)) & 0xffu;
-  } else if constexpr (nc == 2) {
-    c[0] = col[sl.c0], c[1] = col[sl.c0 + 1], c[2] = 0;
-  } else {
-    c[0] = col[sl.c0], c[1] = 0, c[2] = 0;
-  }
-}
 
 // FILL and BOX on one piece: lane-local
 template <int FMT, int S>
@@ -330,69 +252,16 @@ __device__ __forceinline__ void load_cov(const StampAtlas& t, const Stamp& mk, i
   }
 }
 
-template <int FMT, int S>
-__device__ __forceinline__ void stamp_piece(const StampAtlas& t, const Piece& pc, const Stamp& mk, const u32 (&col)[3],
-                                            u32 alpha, u32 (&w)[4]) {
-  constexpr Slot sl = slot_of(FMT, S);
-  constexpr int nc = sl.nc, sh = sl.sh;
-  // the luma pixels under the piece: `span` columns from X, 1 << sh rows from Y
-  constexpr int span = nc == 3 ? 6 : (16 / nc) << sh;
-  const int X = nc == 3 ? pc.bx / 3 : (pc.bx / nc) << sh, Y = pc.y << sh;
-  if (pc.n <= 0 || Y >= mk.ry1 || Y + (1 << sh) <= mk.ry0 || X >= mk.rx1 || X + span <= mk.rx0)
-    return;
-  u32 k[4] = {0u, 0u, 0u, 0u};  // the weight of every byte of the piece
-  if constexpr (nc == 3) {
-    // byte b belongs to pixel (ch0 + b) / 3 of the six, ch0 the channel the piece starts with: every weight three times
-    // (byte selects with constant selectors), then the 16 bytes from ch0 on -- nothing here but ch0 is the same for
-    // every mark, so nothing else is kept in registers across the marks
-    u32 cv[2];
-    load_cov<6>(t, mk, X, Y, cv);
-    if ((cv[0] | cv[1]) == 0u)
-      return;
-    const u32 ch0 = (u32)pc.bx - 3u * (u32)X;
-    const u32 e0 = __builtin_amdgcn_perm(0u, cv[0], 0x01000000u), e1 = __builtin_amdgcn_perm(0u, cv[0], 0x02020101u);
-    const u32 e2 = __builtin_amdgcn_perm(0u, cv[0], 0x03030302u), e3 = __builtin_amdgcn_perm(0u, cv[1], 0x01000000u);
-    const u32 e4 = __builtin_amdgcn_perm(0u, cv[1], 0x01010101u);
-    k[0] = __builtin_amdgcn_alignbyte(e1, e0, ch0), k[1] = __builtin_amdgcn_alignbyte(e2, e1, ch0);
-    k[2] = __builtin_amdgcn_alignbyte(e3, e2, ch0), k[3] = __builtin_amdgcn_alignbyte(e4, e3, ch0);
-  } else if constexpr (sh == 0) {
-    load_cov<16>(t, mk, X, Y, k);
-  } else {
-    // a 4:2:0 chroma sample: the rounded mean of the coverage of its four luma pixels, two 16-bit sums to a word
-#pragma unroll
-    for (int g = 0; g < span / 16; ++g) {
-      u32 r0[4], r1[4];
-      load_cov<16>(t, mk, X + 16 * g, Y, r0);
-      load_cov<16>(t, mk, X + 16 * g, Y + 1, r1);
-#pragma unroll
-      for (int d = 0; d < 4; ++d) {
-        const u32 sum = (r0[d] & 0xff00ffu) + ((r0[d] >> 8) & 0xff00ffu) + (r1[d] & 0xff00ffu) + ((r1[d] >> 8) & 0xff00ffu);
-        const u32 q = ((sum + 0x20002u) >> 2) & 0xff00ffu;
-        if constexpr (nc == 2)
-          k[d] = q | q << 8;  // U and V of a sample share its weight
-        else
-          k[2 * g + d / 2] |= ((q | q >> 8) & 0xffffu) << (16 * (d % 2));
-      }
-    }
+// a STAMP and the atlas as cover_piece's coverage source (tile_paint.hpp)
+struct StampCov {
+  const StampAtlas& t;
+  const Stamp& st;
+  int rx0, ry0, rx1, ry1;
+  template <int N>
+  __device__ __forceinline__ void get(int X, int py, u32 (&cv)[N == 16 ? 4 : 2]) const {
+    load_cov<N>(t, st, X, py, cv);
   }
-  if ((k[0] | k[1] | k[2] | k[3]) == 0u)
-    return;
-  u32 c[3];
-  piece_colours<FMT, S>(pc.lbx, col, c);
-  // per word, so that a word of weights is spent before the next is formed
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    u32 out = w[q];
-#pragma unroll
-    for (int b = 4 * q; b < 4 * q + 4; ++b) {
-      const u32 ae = div255(((k[q] >> (8 * (b % 4))) & 0xffu) * alpha + 127u);
-      const u32 v = (w[q] >> (8 * (b % 4))) & 0xffu;
-      const u32 nv = div255(v * (255u - ae) + c[b % nc] * ae + 127u);  // ae = 0: v
-      out = (out & ~(0xffu << (8 * (b % 4)))) | (nv << (8 * (b % 4)));
-    }
-    w[q] = out;
-  }
-}
+};
 
 // PIXELATE on one piece: ADD =the piece's samples go into the cell sums, !ADD = the cell means come back
 template <int FMT, int S, bool ADD>
@@ -434,42 +303,6 @@ __device__ __forceinline__ void pixelate_piece(const Piece& pc, const Mark& mk, 
         atomicAdd(sums + ((rowkey + run) * 3 + ch), acc);
   }
 }
-
-// a lane's piece S of the tile at (tx0, ty0): where it is, how much of it the image holds, and its bytes
-template <int FMT, int S>
-__device__ __forceinline__ void load_piece(const vali_surface* d, int tid, int tx0, int ty0, int W, int H, Piece& pc,
-                                           u32 (&cur)[4], u32 (&orig)[4]) {
-  constexpr Slot sl = slot_of(FMT, S);
-  constexpr int rows = kTile >> sl.sh, row_pieces = rows * sl.nc / 16;
-  const int k = tid + sl.first;
-  const int prow = k / row_pieces, pcol = k - prow * row_pieces;
-  pc.y = (ty0 >> sl.sh) + prow;
-  pc.lbx = pcol * 16;
-  pc.bx = (tx0 >> sl.sh) * sl.nc + pc.lbx;
-  const int row_bytes = (W >> sl.sh) * sl.nc;
-  pc.n = (k < row_pieces * rows && pc.y < (H >> sl.sh)) ? max(min(row_bytes - pc.bx, 16), 0) : 0;
-  pc.p = (uint8_t*)d->plane[sl.plane] + (size_t)pc.y * (size_t)d->pitch[sl.plane] + pc.bx;
-  uint4 v = make_uint4(0u, 0u, 0u, 0u);
-  if (pc.n > 0)
-    v = load16_n(pc.p, pc.n);
-  cur[0] = orig[0] = v.x, cur[1] = orig[1] = v.y, cur[2] = orig[2] = v.z, cur[3] = orig[3] = v.w;
-}
-
-__device__ __forceinline__ void store_piece(const Piece& pc, const u32 (&cur)[4], const u32 (&orig)[4]) {
-  const bool changed = ((cur[0] ^ orig[0]) | (cur[1] ^ orig[1]) | (cur[2] ^ orig[2]) | (cur[3] ^ orig[3])) != 0u;
-  if (pc.n > 0 && changed)
-    store16_n(pc.p, make_uint4(cur[0], cur[1], cur[2], cur[3]), pc.n);
-}
-
-// once per slot of the format: a slot's layout is a template argument, so the slots are spelled out, not looped over
-#define VALI_SLOTS(CALL)   \
-  {                        \
-    CALL(0)                \
-    CALL(1)                \
-    if constexpr (NS > 2) { \
-      CALL(2)              \
-    }                      \
-  }
 
 // STAMPS: the call has an atlas.  Without one the kernel holds no stamp path and VALI_MARK_STAMP is an unknown kind.
 // The waves per SIMD asked of the register allocator: YUV420 with stamps lands one register above the fourth wave (129)
@@ -566,6 +399,8 @@ k_annotate(const AnnArgs a, const StampAtlas t) {
       __syncthreads();  // the next pixelate mark clears the sums
     } else {
       const u32 alpha = mk.colour >> 24;
+      // (spelled out here and in mask.hip, not a function of tile_paint.hpp: as one, the twelve scalars of a.m are loaded
+      // before the hit loop and held through it, 8 to 15 more scalar registers in k_mask_paint's YUV forms)
       const u32 cr = (mk.colour >> 16) & 0xffu, cg = (mk.colour >> 8) & 0xffu, cb = mk.colour & 0xffu;
       u32 col[3];
       if constexpr (a_isyuv(FMT)) {
@@ -580,9 +415,10 @@ k_annotate(const AnnArgs a, const StampAtlas t) {
       }
       if (STAMPS && mk.kind == VALI_MARK_STAMP) {
         if constexpr (STAMPS) {
-          Stamp st;
-          resolve_stamp(r, W, H, AW, AH, st);
-#define VALI_SLOT(S) stamp_piece<FMT, S>(t, pc[S], st, col, alpha, cur[S]);
+          Stamp sp;
+          resolve_stamp(r, W, H, AW, AH, sp);
+          const StampCov st = {t, sp, sp.rx0, sp.ry0, sp.rx1, sp.ry1};
+#define VALI_SLOT(S) cover_piece<FMT, S>(st, pc[S], col, alpha, cur[S]);
           VALI_SLOTS(VALI_SLOT)
 #undef VALI_SLOT
         }
@@ -601,55 +437,12 @@ k_annotate(const AnnArgs a, const StampAtlas t) {
 }
 #undef VALI_SLOTS
 
-int ann_format(int format) {
-  switch (format) {
-  case VALI_FMT_NV12: return A_NV12;
-  case VALI_FMT_YUV420: return A_YUV420;
-  case VALI_FMT_YUV444: return A_YUV444;
-  case VALI_FMT_RGB: return A_RGB;
-  case VALI_FMT_BGR: return A_BGR;
-  case VALI_FMT_RGB_PLANAR: return A_RGBP;
-  default: return -1;
-  }
-}
-
 template <int FMT>
 void launch_tiles(const dim3& grid, hipStream_t s, const AnnArgs& a, const StampAtlas& t) {
   if (t.p)
     hipLaunchKernelGGL((k_annotate<FMT, true>), grid, dim3(kBlock), 0, s, a, t);
   else
     hipLaunchKernelGGL((k_annotate<FMT, false>), grid, dim3(kBlock), 0, s, a, t);
-}
-
-// the rules for the frames of a batch; *max_tiles: the tiles of the largest one
-int check_frames(const char* who, int n, const vali_surface* frames, int format, int* max_tiles) {
-  const int fmt = ann_format(format);
-  if (fmt < 0)
-    return fail(VALI_ERR_UNSUPPORTED, "%s: format %d (NV12, YUV420, YUV444, RGB, BGR, RGB_PLANAR)", who, format);
-  const int planes = (fmt == A_RGB || fmt == A_BGR) ? 1 : fmt == A_NV12 ? 2 : 3;
-  int tiles = 0;
-  for (int i = 0; i < n; ++i) {
-    const vali_surface& s = frames[i];
-    if (s.format != format)
-      return fail(VALI_ERR_INVALID_ARG, "%s: frame %d has format %d, the batch %d: one format per batch", who, i,
-                  s.format, format);
-    if (s.width < 1 || s.height < 1 || s.width > 65535 || s.height > 65535)
-      return fail(VALI_ERR_INVALID_ARG, "%s: frame %d: size %dx%d outside 1..65535", who, i, s.width, s.height);
-    if (!subsampled_sizes_ok(format, s.width, s.height))
-      return fail(VALI_ERR_INVALID_ARG, "%s: frame %d: 4:2:0 formats need an even width and height, got %dx%d", who, i,
-                  s.width, s.height);
-    for (int p = 0; p < planes; ++p) {
-      const Slot sl = slot_of(fmt, (fmt == A_RGB || fmt == A_BGR) ? 0 : p);
-      if (!s.plane[p])
-        return fail(VALI_ERR_INVALID_ARG, "%s: frame %d: plane %d is null", who, i, p);
-      if (s.pitch[p] < (s.width >> sl.sh) * sl.nc)
-        return fail(VALI_ERR_INVALID_ARG, "%s: frame %d: pitch %d of plane %d is shorter than a row", who, i, s.pitch[p], p);
-    }
-    const int t = ((s.width + kTile - 1) / kTile) * ((s.height + kTile - 1) / kTile);
-    tiles = t > tiles ? t : tiles;
-  }
-  *max_tiles = tiles;
-  return VALI_OK;
 }
 
 } // namespace
@@ -691,7 +484,7 @@ int vali_annotate_batch_atlas(const vali_surface* frames, const vali_surface* d_
   const int rc = check_frames(__func__, n, frames, format, &tiles);
   if (rc != VALI_OK)
     return rc;
-  const int fmt = ann_format(format);
+  const int fmt = tile_format(format);
   VALI_REQUIRE(params || !a_isyuv(fmt), "a YUV format needs params (rgb2yuv)");
   VALI_REQUIRE(workspace || n == 0, "null workspace");
   VALI_REQUIRE(((uintptr_t)workspace & 15u) == 0, "the workspace is not 16-byte aligned");

@@ -53,13 +53,6 @@ struct DetOut {
   int crop[4];
 };
 
-__device__ __forceinline__ float ld_elem(const void* p, int dt, long long i) {
-  if (dt == VALI_DTYPE_F32)
-    return ((const float*)p)[i];
-  const u32 b = ((const u16*)p)[i];
-  return dt == VALI_DTYPE_F16 ? TensorElem<VALI_DTYPE_F16>::f(b) : TensorElem<VALI_DTYPE_BF16>::f(b);
-}
-
 __device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 struct FrameRec {
@@ -78,10 +71,10 @@ __device__ __forceinline__ FrameRec frame_rec(const vali_roi& r) {
 // step 3 of the definition: the box of candidate k in network coordinates, clipped to the placement
 __device__ __forceinline__ bool det_box(const DetArgs& a, int f, int k, const FrameRec& fr, float4& o) {
   const long long base = (long long)f * a.boxes.sn + (long long)k * a.boxes.sk;
-  const float b0 = ld_elem(a.boxes.p, a.boxes.dtype, base);
-  const float b1 = ld_elem(a.boxes.p, a.boxes.dtype, base + a.boxes.sc);
-  const float b2 = ld_elem(a.boxes.p, a.boxes.dtype, base + 2 * a.boxes.sc);
-  const float b3 = ld_elem(a.boxes.p, a.boxes.dtype, base + 3 * a.boxes.sc);
+  const float b0 = tensor_elem_f(a.boxes.p, a.boxes.dtype, base);
+  const float b1 = tensor_elem_f(a.boxes.p, a.boxes.dtype, base + a.boxes.sc);
+  const float b2 = tensor_elem_f(a.boxes.p, a.boxes.dtype, base + 2 * a.boxes.sc);
+  const float b3 = tensor_elem_f(a.boxes.p, a.boxes.dtype, base + 3 * a.boxes.sc);
   float x1 = b0, y1 = b1, x2 = b2, y2 = b3;
   if (a.cxcywh) {
     const float hw = __fmul_rn(b2, 0.5f), hh = __fmul_rn(b3, 0.5f);

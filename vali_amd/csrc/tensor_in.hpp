@@ -44,6 +44,15 @@ struct TensorElem<VALI_DTYPE_U8> {
   static __device__ __forceinline__ float f(u32 b) { return (float)b; }
 };
 
+// element i of a float32, float16 or bfloat16 tensor whose dtype is known at run time only (the heads that
+// vali_detect_select and vali_mask_paint read)
+__device__ __forceinline__ float tensor_elem_f(const void* p, int dt, long long i) {
+  if (dt == VALI_DTYPE_F32)
+    return ((const float*)p)[i];
+  const u32 b = ((const uint16_t*)p)[i];
+  return dt == VALI_DTYPE_F16 ? TensorElem<VALI_DTYPE_F16>::f(b) : TensorElem<VALI_DTYPE_BF16>::f(b);
+}
+
 // element i of a run of elements held in dwords
 template <int ES>
 __device__ __forceinline__ u32 elem_bits(const u32* w, int i) {

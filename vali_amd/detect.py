@@ -13,7 +13,7 @@ from typing import Optional, Tuple
 from ._native import shim
 from .enums import DLDeviceType, TaskExecInfo
 from .runtime import is_capturing
-from .tasks import MAX_MARKS, _SurfaceTask, _device_rects, _status, pack_colour
+from .tasks import MAX_MARKS, _SurfaceTask, _device_rects, _release, _status, pack_colour
 
 MAX_FRAMES, MAX_HEAD, MAX_CLASSES, MAX_CANDIDATES = 1024, 1 << 20, 4096, 1024
 
@@ -341,19 +341,7 @@ class SelectBatch:
         return self.n
 
     def __del__(self):
-        if getattr(self, "d_ws", 0):
-            try:    # a launch issued on the batch's stream may still be using the workspace
-                shim.stream_sync(self.gpu_id, self._stream)
-            except Exception:
-                pass
-        for name in ("d_ws", "d_rects"):
-            p = getattr(self, name, 0)
-            if p:
-                try:
-                    shim.mem_free(self.gpu_id, p)
-                except Exception:
-                    pass
-                setattr(self, name, 0)
+        _release(self, ("d_ws", "d_rects"))
 
 
 class PyDetectionSelector(_SurfaceTask):

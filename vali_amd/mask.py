@@ -16,8 +16,8 @@ from .detect import _DTYPES, _CAI, _device_i32, _host_rects, _is_device
 from .enums import DLDeviceType, PixelFormat as F, TaskExecInfo
 from .runtime import is_capturing
 from .surface import Surface
-from .tasks import (PySurfaceAnnotator, PySurfacePostprocessor, _S_UNSUPP_CC, _SurfaceTask, _device_rects, _params,
-                    _status)
+from .tasks import (PySurfaceAnnotator, PySurfacePostprocessor, _S_UNSUPP_CC, _SurfaceTask, _device_rects,
+                    _frames_of_one_format, _params, _release, _status)
 
 MAX_FRAMES, MAX_PROTOS, MAX_SIDE, MAX_HEAD, MAX_DET, MAX_NET = 1024, 64, 1024, 1 << 20, 1024, 65535
 
@@ -157,22 +157,7 @@ class MaskBatch:
     def __init__(self, gpu_id: int, stream: int, frames: Sequence[Surface], protos, coeffs, dets, max_det=100,
                  net_size=(640, 640)):
         frames = list(frames)
-        fmt = None
-        for i, d in enumerate(frames):
-            if d is None or d.IsEmpty:
-                raise ValueError(f"MaskBatch: surface {i} is empty")
-            if d.Format not in PySurfaceAnnotator._FORMATS:
-                raise ValueError(f"MaskBatch: surface {i} has format {d.Format!r}; supported: "
-                                 f"{', '.join(f.name for f in PySurfaceAnnotator._FORMATS)}")
-            if fmt is not None and d.Format != fmt:
-                raise ValueError(f"MaskBatch: surface {i} has format {d.Format!r}, surface 0 {fmt!r}: one format per batch")
-            fmt = d.Format
-            if fmt in (F.NV12, F.YUV420) and (d.Width | d.Height) & 1:
-                raise ValueError(f"MaskBatch: surface {i}: {fmt.name} is 4:2:0 and needs an even width and height, "
-                                 f"got {d.Width}x{d.Height}")
-            dev = getattr(d, "DeviceId", gpu_id)
-            if dev != gpu_id:
-                raise ValueError(f"MaskBatch: surface {i} is on device {dev}, the task on {gpu_id}")
+        fmt = _frames_of_one_format("MaskBatch", frames, PySurfaceAnnotator._FORMATS, gpu_id)
         pp, pcode, pshape, pstr, ph = _view("protos", protos_layout, protos, gpu_id)
         cp, ccode, cshape, cstr, ch = _view("coeffs", coeffs_layout, coeffs, gpu_id)
         n, m, hp, wp, k, D, net_w, net_h = mask_spec(len(frames), (pcode, pshape, pstr), (ccode, cshape, cstr), max_det,
@@ -204,19 +189,7 @@ class MaskBatch:
         return self.n
 
     def __del__(self):
-        if getattr(self, "d_frames", 0):
-            try:    # a launch issued on the batch's stream may still be using the arrays
-                shim.stream_sync(self.gpu_id, self._stream)
-            except Exception:
-                pass
-        for name in ("d_frames", "d_ws", "d_rects", "d_colours"):
-            p = getattr(self, name, 0)
-            if p:
-                try:
-                    shim.mem_free(self.gpu_id, p)
-                except Exception:
-                    pass
-                setattr(self, name, 0)
+        _release(self, ("d_frames", "d_ws", "d_rects", "d_colours"))
 
 
 class PyInstanceMasker(_SurfaceTask):

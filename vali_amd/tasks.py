@@ -429,6 +429,48 @@ class PySurfaceConverter(_SurfaceTask):
         return r
 
 
+def _release(batch, names):
+    """The teardown of a prepared batch (its __del__): free the device arrays it names, after the batch's stream."""
+    if any(getattr(batch, name, 0) for name in names):
+        try:    # a launch issued on the batch's stream may still be using the arrays
+            shim.stream_sync(batch.gpu_id, batch._stream)
+        except Exception:
+            pass
+    for name in names:
+        p = getattr(batch, name, 0)
+        if p:
+            try:
+                shim.mem_free(batch.gpu_id, p)
+            except Exception:
+                pass
+            setattr(batch, name, 0)
+
+
+def _frames_of_one_format(who, frames, formats, gpu_id, also=None):
+    """The rules for the surfaces a batch writes to: none empty, one of `formats` and the same for all, 4:2:0 ones of even
+    size, all on `gpu_id`.  `also(i, surface)`: the caller's own check, made once the surface's format is known.
+    Returns the format (None for no surfaces)."""
+    fmt = None
+    for i, d in enumerate(frames):
+        if d is None or d.IsEmpty:
+            raise ValueError(f"{who}: surface {i} is empty")
+        if d.Format not in formats:
+            raise ValueError(f"{who}: surface {i} has format {d.Format!r}; supported: "
+                             f"{', '.join(f.name for f in formats)}")
+        if fmt is not None and d.Format != fmt:
+            raise ValueError(f"{who}: surface {i} has format {d.Format!r}, surface 0 {fmt!r}: one format per batch")
+        fmt = d.Format
+        if also is not None:
+            also(i, d)
+        if fmt in (F.NV12, F.YUV420) and (d.Width | d.Height) & 1:
+            raise ValueError(f"{who}: surface {i}: {fmt.name} is 4:2:0 and needs an even width and height, "
+                             f"got {d.Width}x{d.Height}")
+        dev = getattr(d, "DeviceId", gpu_id)
+        if dev != gpu_id:
+            raise ValueError(f"{who}: surface {i} is on device {dev}, the task on {gpu_id}")
+    return fmt
+
+
 class SurfaceBatch:
     """Device-resident descriptor arrays for n (src, dst) surface pairs of one geometry."""
 
@@ -461,19 +503,7 @@ class SurfaceBatch:
         return self.n
 
     def __del__(self):
-        if getattr(self, "d_src", 0) or getattr(self, "d_dst", 0):
-            try:    # a launch issued on the batch's stream may still be reading the arrays
-                shim.stream_sync(self.gpu_id, self._stream)
-            except Exception:
-                pass
-        for name in ("d_src", "d_dst"):
-            p = getattr(self, name, 0)
-            if p:
-                try:
-                    shim.mem_free(self.gpu_id, p)
-                except Exception:
-                    pass
-                setattr(self, name, 0)
+        _release(self, ("d_src", "d_dst"))
 
 
 # ---- PySurfaceUD -------------------------------------------------------------------------
@@ -979,19 +1009,7 @@ class RoiBatch:
         return self.n
 
     def __del__(self):
-        if getattr(self, "d_src", 0) or getattr(self, "d_dst", 0) or getattr(self, "d_roi", 0):
-            try:    # a launch issued on the batch's stream may still be reading the arrays
-                shim.stream_sync(self.gpu_id, self._stream)
-            except Exception:
-                pass
-        for name in ("d_src", "d_dst", "d_roi"):
-            p = getattr(self, name, 0)
-            if p:
-                try:
-                    shim.mem_free(self.gpu_id, p)
-                except Exception:
-                    pass
-                setattr(self, name, 0)
+        _release(self, ("d_src", "d_dst", "d_roi"))
 
 
 # DLPack dtype (code, bits) -> (name, enum vali_dtype): kDLFloat = 2, kDLBfloat = 4
@@ -1152,19 +1170,7 @@ class TensorBatch:
         return self.n
 
     def __del__(self):
-        if getattr(self, "d_src", 0) or getattr(self, "d_roi", 0):
-            try:    # a launch issued on the batch's stream may still be reading the arrays
-                shim.stream_sync(self.gpu_id, self._stream)
-            except Exception:
-                pass
-        for name in ("d_src", "d_roi"):
-            p = getattr(self, name, 0)
-            if p:
-                try:
-                    shim.mem_free(self.gpu_id, p)
-                except Exception:
-                    pass
-                setattr(self, name, 0)
+        _release(self, ("d_src", "d_roi"))
 
 
 # ---- PySurfaceRotator --------------------------------------------------------------------
@@ -1200,25 +1206,13 @@ class FrameBatch:
         dsts = list(dsts)
         if len(dsts) != n:
             raise ValueError(f"FrameBatch: {len(dsts)} surfaces for a tensor of {n} items")
-        fmt = None
-        for i, d in enumerate(dsts):
-            if d is None or d.IsEmpty:
-                raise ValueError(f"FrameBatch: surface {i} is empty")
-            if d.Format not in PySurfacePostprocessor._DST:
-                raise ValueError(f"FrameBatch: surface {i} has format {d.Format!r}; supported: "
-                                 f"{', '.join(f.name for f in PySurfacePostprocessor._DST)}")
-            if fmt is not None and d.Format != fmt:
-                raise ValueError(f"FrameBatch: surface {i} has format {d.Format!r}, surface 0 {fmt!r}: one format per batch")
-            fmt = d.Format
+
+        def same_size(i, d):
             if (d.Width, d.Height) != (w, h):
                 raise ValueError(f"FrameBatch: surface {i} is {d.Width}x{d.Height}, the tensor's items are {w}x{h}: "
                                  "the sizes must be equal (no resizing on the way out)")
-            if fmt in (F.NV12, F.YUV420) and (w | h) & 1:
-                raise ValueError(f"FrameBatch: surface {i}: {fmt.name} is 4:2:0 and needs an even width and height, "
-                                 f"got {w}x{h}")
-            dev = getattr(d, "DeviceId", gpu_id)
-            if dev != gpu_id:
-                raise ValueError(f"FrameBatch: surface {i} is on device {dev}, the task on {gpu_id}")
+
+        fmt = _frames_of_one_format("FrameBatch", dsts, PySurfacePostprocessor._DST, gpu_id, same_size)
         if is_capturing(gpu_id, stream):
             raise RuntimeError("FrameBatch: cannot be created while the stream is capturing -- PrepareTensorBatch() "
                                "before the StreamCapture block and Keep() the batch with the capture")
@@ -1235,17 +1229,7 @@ class FrameBatch:
         return self.n
 
     def __del__(self):
-        p = getattr(self, "d_dst", 0)
-        if p:
-            try:    # a launch issued on the batch's stream may still be reading the array
-                shim.stream_sync(self.gpu_id, self._stream)
-            except Exception:
-                pass
-            try:
-                shim.mem_free(self.gpu_id, p)
-            except Exception:
-                pass
-            self.d_dst = 0
+        _release(self, ("d_dst",))
 
 
 class PySurfacePostprocessor(_SurfaceTask):
@@ -1439,22 +1423,7 @@ class AnnotateBatch:
 
     def __init__(self, gpu_id: int, stream: int, frames: Sequence[Surface]):
         frames = list(frames)
-        fmt = None
-        for i, d in enumerate(frames):
-            if d is None or d.IsEmpty:
-                raise ValueError(f"AnnotateBatch: surface {i} is empty")
-            if d.Format not in PySurfaceAnnotator._FORMATS:
-                raise ValueError(f"AnnotateBatch: surface {i} has format {d.Format!r}; supported: "
-                                 f"{', '.join(f.name for f in PySurfaceAnnotator._FORMATS)}")
-            if fmt is not None and d.Format != fmt:
-                raise ValueError(f"AnnotateBatch: surface {i} has format {d.Format!r}, surface 0 {fmt!r}: one format per batch")
-            fmt = d.Format
-            if fmt in (F.NV12, F.YUV420) and (d.Width | d.Height) & 1:
-                raise ValueError(f"AnnotateBatch: surface {i}: {fmt.name} is 4:2:0 and needs an even width and height, "
-                                 f"got {d.Width}x{d.Height}")
-            dev = getattr(d, "DeviceId", gpu_id)
-            if dev != gpu_id:
-                raise ValueError(f"AnnotateBatch: surface {i} is on device {dev}, the task on {gpu_id}")
+        fmt = _frames_of_one_format("AnnotateBatch", frames, PySurfaceAnnotator._FORMATS, gpu_id)
         if frames and is_capturing(gpu_id, stream):
             raise RuntimeError("AnnotateBatch: cannot be created while the stream is capturing -- PrepareBatch() "
                                "before the StreamCapture block and Keep() the batch with the capture")
@@ -1478,19 +1447,7 @@ class AnnotateBatch:
         return self.n
 
     def __del__(self):
-        if getattr(self, "d_frames", 0):
-            try:    # a launch issued on the batch's stream may still be reading the arrays
-                shim.stream_sync(self.gpu_id, self._stream)
-            except Exception:
-                pass
-        for name in ("d_frames", "d_ws", "d_marks"):
-            p = getattr(self, name, 0)
-            if p:
-                try:
-                    shim.mem_free(self.gpu_id, p)
-                except Exception:
-                    pass
-                setattr(self, name, 0)
+        _release(self, ("d_frames", "d_ws", "d_marks"))
 
 
 class PySurfaceAnnotator(_SurfaceTask):
