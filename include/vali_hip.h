@@ -740,6 +740,77 @@ VALI_API int vali_mask_paint(const vali_surface* frames, const vali_surface* d_f
                              const int32_t* d_colours, int n_colours, int alpha, const vali_cvt_params* params,
                              void* d_ws, size_t ws_bytes, vali_stream_t stream);
 
+/* ---- pose skeletons: a keypoint head's points in frame pixels, drawn as limbs and joints ---------------
+ *
+ * kpts (n, k, p, kdim), float32, float16 or bfloat16 with any four element strides >= 0 (a transposed, unflattened head
+ * slice, a broadcast): (kx, ky, conf) per keypoint in the coordinates of the network's input with kdim = 3, (kx, ky) and
+ * conf = 1.0 with kdim = 2.  d_dets are the (n * D) rows of vali_detect_select (frame, x, y, w, h, class, score bits, k;
+ * D = max_det), d_rects[i] the record frame i was placed with, d_limbs n_limbs pairs (a, b) of keypoint indices in device
+ * memory.  The keypoints of the rows are written to `points` and drawn IN PLACE onto n frames of one format (the six of
+ * vali_annotate_batch, under its rules for frames) in TWO launches whatever the data; nothing is allocated and nothing
+ * synchronises, so the call can be captured and replayed after kpts, d_dets, d_rects and the frames were rewritten in
+ * place.  The reference has no such task.  Float arithmetic is IEEE float32, one rounding per operation, never a fused
+ * multiply-add; (float) of an integer rounds to nearest.  Frame i is W x H with record src_x, src_y, src_w, src_h, dst_x,
+ * dst_y, dst_w, dst_h; row i * D + r:
+ *   1. skipped  exactly as a row of vali_mask_paint (its step 1), for every int32 value: its frame field is not i, w < 1
+ *               or h < 1, k is outside 0..K-1, src_w, src_h, dst_w or dst_h is below 1, or the box [x, x + w) x
+ *               [y, y + h) does not meet the frame.  The p points of a skipped row are all zero.
+ *   2. mapping  keypoint j of a drawn row: (kx, ky, conf) = (float)kpts[i][k][j][0..2];
+ *               fx = (kx - (float)dst_x) * ((float)src_w / (float)dst_w) + (float)src_x, fy likewise with dst_y, src_h /
+ *               dst_h, src_y (vali_detect_select's step 6); X = floor(fx), Y = floor(fy).
+ *   3. visible  when conf > kpt_thr (a NaN never is), kx and ky are finite, -65536 <= fx < 131072 and -65536 <= fy <
+ *               131072 (tested on the floats, before the conversion).  A visible keypoint is inside the frame when
+ *               0 <= X < W and 0 <= Y < H.  points[(i * D + r) * p + j] = X, Y, the bits of conf as float32, flag: flag 0
+ *               invisible (X = Y = 0), 1 visible, 3 visible and inside the frame.
+ *   4. coverage 255 or 0 per luma pixel, decided at the pixel's integer coordinates P in exact integers.  A joint of
+ *               diameter d at C covers P when 4 |P - C|^2 <= d^2.  A limb of thickness t from A to B, with e = B - A,
+ *               q = P - A, L2 = e . e, s = q . e: if L2 == 0 or s <= 0, when 4 |q|^2 <= t^2; else if s >= L2, when
+ *               4 |P - B|^2 <= t^2; else when 4 c^2 <= t^2 L2 with c = q.x e.y - q.y e.x.  A capsule and a disc: no
+ *               float, no square root, no anti-aliasing.  A limb is drawn when both its keypoints are visible, a joint
+ *               when its keypoint is; a pair with an index outside 0..p-1 draws nothing.
+ *   5. order    rows ascending; within a row the limbs in table order, then the joints by ascending keypoint.
+ *   6. blend    VALI_MARK_STAMP's with that coverage: k = cov for full-resolution channels, (the four luma coverages + 2)
+ *               >> 2 for a 4:2:0 chroma sample (shapes are NOT snapped to even coordinates), a_eff = (k * a + 127) / 255,
+ *               v = (v * (255 - a_eff) + c * a_eff + 127) / 255, c as for VALI_MARK_FILL (params->rgb2yuv for YUV
+ *               formats) of the colour d_limb_colours[l mod n_limb_colours] of limb l, d_joint_colours[j mod
+ *               n_joint_colours] of joint j; a its alpha or, with alpha in 0..255, alpha (alpha = -1 keeps the colour's).
+ *               The result is bit for bit that of vali_annotate_batch_atlas for STAMP rows, in that order, over an atlas
+ *               holding each shape's coverage as 255 / 0.  Nothing outside a plane's image area is written; frames and
+ *               tiles no shape meets are neither read nor written, and only 16-byte pieces a shape changed are stored.
+ * Limits: n 1..1024, k 1..2^20, p 1..64, n_limbs 0..128, D 1..1024 with n * D <= 65535, thickness and diameter 1..64.
+ * d_points: NULL, or n * D * p rows of 4 int32 in device memory, 16-byte aligned, every row rewritten by every call; with
+ * NULL the rows go to the workspace.  d_ws: vali_pose_workspace_size(n, max_det, p) = n * max_det * (1 + p) * 16 bytes
+ * of device memory, 16-byte aligned (0 for sizes outside the limits): a box per row, then the points.  Its contents need
+ * not survive between calls.
+ * VALI_ERR_INVALID_ARG, before any device is touched: null frames, d_frames, in, d_dets, d_rects, style or d_ws, null
+ * params for a YUV format; a null kpts, d_limbs (with n_limbs > 0) or colour pointer, a dtype outside the three, a kpts
+ * pointer not aligned to its element, a stride outside 0..2^40, kdim other than 2 or 3; a limit above broken; a colour
+ * count below 1; a NaN kpt_thr; alpha outside -1..255; d_dets, d_rects, d_limbs or the colours not 4-byte aligned;
+ * d_points or a workspace not 16-byte aligned, a workspace that is too small; a frame that breaks vali_annotate_batch's
+ * rules.  VALI_ERR_UNSUPPORTED for a format outside the six.
+ */
+typedef struct vali_pose_in {
+  const void* kpts;                      /* element (0, 0, 0, 0) */
+  int32_t dtype;                         /* VALI_DTYPE_F32, _F16 or _BF16 */
+  int32_t kdim;                          /* 3: (kx, ky, conf); 2: (kx, ky), conf = 1.0 */
+  int64_t stride_n, stride_k, stride_p, stride_c; /* in elements, >= 0 */
+  int32_t k, p, max_det, n_limbs;
+  const int32_t* d_limbs;                /* device, n_limbs pairs (a, b) */
+} vali_pose_in;                          /* 72 bytes */
+typedef struct vali_pose_style {
+  const int32_t* d_limb_colours;         /* device, n_limb_colours packed colours */
+  const int32_t* d_joint_colours;        /* device, n_joint_colours packed colours */
+  int32_t n_limb_colours, n_joint_colours;
+  float kpt_thr;
+  int32_t thickness, diameter, alpha;
+} vali_pose_style;                       /* 40 bytes */
+
+VALI_API size_t vali_pose_workspace_size(int n, int max_det, int p);
+VALI_API int vali_pose_paint(const vali_surface* frames, const vali_surface* d_frames, int n, int format,
+                             const vali_pose_in* in, const int32_t* d_dets, const vali_roi* d_rects,
+                             const vali_pose_style* style, int32_t* d_points, const vali_cvt_params* params,
+                             void* d_ws, size_t ws_bytes, vali_stream_t stream);
+
 /*
  * Rectangles of surfaces of ANY sizes as files, in one fixed set of launches.  Item i is rectangle rois[i] of the
  * surface d_src[i] (the same surface may stand behind any number of items); its file is byte for byte the file of

@@ -24,6 +24,7 @@ if not _BUILDING:
                         letterbox_rect, pack_colour, pack_uv, render_labels)
     from .detect import DetectionStyle, PyDetectionSelector, SelectBatch
     from .mask import MaskBatch, PyInstanceMasker
+    from .pose import COCO_SKELETON, PoseBatch, PyPoseDrawer
     from .pipeline import BatchedFramePipeline, broadcast_coefficients, shard_frames
     from .transfer import PyFrameUploader, PySurfaceDownloader
     from . import tuning

@@ -18,11 +18,11 @@
 //                   registers, applies all hits in order -- the logits come through the L2 -- and stores a piece only if a
 //                   mask changed it.  The blend is STAMP's (cover_piece) with the coverage made on the fly.
 // The formats and the frame rules, the tile's pieces, the hit list and the coverage blend are tile_paint.hpp's, shared
-// with annotate.hip; here are the rows, the sampler and the coverage of a hit.
+// with annotate.hip, the rows det_rows.hpp's, shared with pose.hip; here are the sampler and the coverage of a hit.
 #include <math.h>
 
+#include "det_rows.hpp"
 #include "tensor_in.hpp"
-#include "tile_paint.hpp"
 
 #pragma clang fp contract(off)
 
@@ -47,37 +47,6 @@ struct MaskArgs {
   int n_colours, alpha;
   float m[3][4];  // rgb2yuv rows (YUV formats)
 };
-
-__device__ __forceinline__ void load_row(const int32_t* dets, int i, int (&r)[8]) {
-  const uint4 a = load16_u((const uint8_t*)(dets + (size_t)i * 8)), b = load16_u((const uint8_t*)(dets + (size_t)i * 8) + 16);
-  r[0] = (int)a.x, r[1] = (int)a.y, r[2] = (int)a.z, r[3] = (int)a.w;
-  r[4] = (int)b.x, r[5] = (int)b.y, r[6] = (int)b.z, r[7] = (int)b.w;
-}
-
-// step 1 of the definition; the box clipped to the W x H frame
-struct Row {
-  int x0, y0, x1, y1;
-  int cls, k;
-};
-__device__ __forceinline__ bool resolve_row(const int (&r)[8], int f, int W, int H, int K, const vali_roi& rc, Row& o) {
-  if (r[0] != f || r[3] < 1 || r[4] < 1 || r[7] < 0 || r[7] >= K)
-    return false;
-  if (rc.src_w < 1 || rc.src_h < 1 || rc.dst_w < 1 || rc.dst_h < 1)
-    return false;
-  // 64 bits: x + w overflows int32
-  const long long x0 = r[1], y0 = r[2], x1 = x0 + r[3], y1 = y0 + r[4];
-  if (x0 >= W || y0 >= H || x1 <= 0 || y1 <= 0)
-    return false;
-  o.x0 = clampi(x0, 0, W), o.y0 = clampi(y0, 0, H), o.x1 = clampi(x1, 0, W), o.y1 = clampi(y1, 0, H);
-  o.cls = r[5], o.k = r[7];
-  return true;
-}
-// the same box for a row that is known to pass
-__device__ __forceinline__ void clip_box(const int (&r)[8], int W, int H, Row& o) {
-  const long long x0 = r[1], y0 = r[2], x1 = x0 + r[3], y1 = y0 + r[4];
-  o.x0 = clampi(x0, 0, W), o.y0 = clampi(y0, 0, H), o.x1 = clampi(x1, 0, W), o.y1 = clampi(y1, 0, H);
-  o.cls = r[5], o.k = r[7];
-}
 
 // step 3 of the definition along one axis
 struct Axis {

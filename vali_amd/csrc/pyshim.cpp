@@ -778,6 +778,39 @@ PYBIND11_MODULE(_vali_shim, m) {
                                  ws_bytes, P(stream));
         });
 
+  // pose skeletons: kpts = (ptr, dtype, stride_n, stride_k, stride_p, stride_c); descs = the host copy of the descriptors
+  // in d_frames; d_points may be 0 (the rows go to the workspace); everything else as in the header
+  m.def("pose_workspace_size", [](int n, int max_det, int p) { return vali_pose_workspace_size(n, max_det, p); });
+  m.def("pose_paint",
+        [](const std::vector<SurfaceDesc>& descs, uintptr_t d_frames, int format, const std::array<int64_t, 6>& kpts,
+           int kdim, int k, int pp, int max_det, uintptr_t d_limbs, int n_limbs, uintptr_t d_dets, uintptr_t d_rects,
+           uintptr_t d_limb_colours, int n_limb_colours, uintptr_t d_joint_colours, int n_joint_colours, float kpt_thr,
+           int thickness, int diameter, int alpha, uintptr_t d_points, const CvtParams* p, uintptr_t workspace,
+           size_t ws_bytes, uintptr_t stream) {
+          std::vector<vali_surface> host(descs.size());
+          for (size_t i = 0; i < descs.size(); ++i)
+            host[i] = descs[i].s;
+          vali_pose_in in;
+          std::memset(&in, 0, sizeof(in));
+          in.kpts = P((uintptr_t)kpts[0]);
+          in.dtype = (int32_t)kpts[1];
+          in.kdim = kdim;
+          in.stride_n = kpts[2]; in.stride_k = kpts[3]; in.stride_p = kpts[4]; in.stride_c = kpts[5];
+          in.k = k; in.p = pp; in.max_det = max_det; in.n_limbs = n_limbs;
+          in.d_limbs = (const int32_t*)P(d_limbs);
+          vali_pose_style st;
+          std::memset(&st, 0, sizeof(st));
+          st.d_limb_colours = (const int32_t*)P(d_limb_colours);
+          st.d_joint_colours = (const int32_t*)P(d_joint_colours);
+          st.n_limb_colours = n_limb_colours; st.n_joint_colours = n_joint_colours;
+          st.kpt_thr = kpt_thr;
+          st.thickness = thickness; st.diameter = diameter; st.alpha = alpha;
+          py::gil_scoped_release nogil;
+          return vali_pose_paint(host.empty() ? nullptr : host.data(), (const vali_surface*)P(d_frames), (int)host.size(),
+                                 format, &in, (const int32_t*)P(d_dets), (const vali_roi*)P(d_rects), &st,
+                                 (int32_t*)P(d_points), p ? &p->p : nullptr, P(workspace), ws_bytes, P(stream));
+        });
+
   // ---- JPEG decoder: host-side parser and sizes, then the batched decoder --------------------------------------
   py::class_<JpegInfo>(m, "JpegInfo")
       .def_property_readonly("width", [](const JpegInfo& j) { return j.f.width; })

@@ -1,0 +1,239 @@
+"""PyPoseDrawer: a pose head's keypoints -> points in frame pixels and skeletons drawn onto frames, on the GPU
+(vali_pose_paint).
+
+The keypoints of the selector's detections are gathered by each detection's k, mapped back through the letterbox, written
+to a tensor of points and drawn in place as limbs (capsules) and joints (discs), in row order, in two launches whatever
+the data: no keypoint is ever on the host.  The definition, sample for sample, is in include/vali_hip.h;
+tests/pose_model.py restates it in numpy.
+"""
+from __future__ import annotations
+
+import array
+import math
+import operator
+from typing import Sequence, Tuple
+
+from ._native import shim
+from .detect import _device_i32, _host_rects, _is_device
+from .enums import PixelFormat as F, TaskExecInfo
+from .mask import _layout, _view
+from .runtime import is_capturing
+from .surface import Surface
+from .tasks import (PySurfaceAnnotator, PySurfacePostprocessor, _S_UNSUPP_CC, _SurfaceTask, _device_rects,
+                    _frames_of_one_format, _params, _release, _status)
+
+MAX_FRAMES, MAX_HEAD, MAX_POINTS, MAX_LIMBS, MAX_DET, MAX_WIDTH = 1024, 1 << 20, 64, 128, 1024, 64
+
+# the 19 limbs of the 17 COCO keypoints, 0-based
+COCO_SKELETON = ((15, 13), (13, 11), (16, 14), (14, 12), (11, 12), (5, 11), (6, 12), (5, 6), (5, 7), (6, 8), (7, 9),
+                 (8, 10), (1, 2), (0, 1), (0, 2), (1, 3), (2, 4), (3, 5), (4, 6))
+
+
+def kpts_layout(shape, strides, code, bits):
+    """The rules for `kpts`, without a device: (N, K, P, 3) or (N, K, P, 2) with any element strides >= 0.  Returns
+    (dtype code, shape, strides); ValueError, naming what is wrong, otherwise."""
+    code, shape, strides = _layout("kpts", ("N", "K", "P", "3 or 2"), shape, strides, code, bits)
+    n, k, p, c = shape
+    if not 1 <= n <= MAX_FRAMES:
+        raise ValueError(f"kpts: N = {n} is outside 1..{MAX_FRAMES}")
+    if not 1 <= k <= MAX_HEAD:
+        raise ValueError(f"kpts: K = {k} is outside 1..2^20")
+    if not 1 <= p <= MAX_POINTS:
+        raise ValueError(f"kpts: P = {p} is outside 1..{MAX_POINTS}")
+    if c not in (2, 3):
+        raise ValueError(f"kpts: the last dimension must be 3 (x, y, confidence) or 2 (x, y), got {shape}")
+    return code, shape, strides
+
+
+def pose_spec(n_frames, kpts_view, max_det=100, limbs=COCO_SKELETON):
+    """What Prepare checks once the tensor is seen, without a device: the view is (dtype code, shape, strides) as
+    kpts_layout returns it.  Returns (n, k, p, kdim, D, limbs as a flat list)."""
+    _, (n, k, p, kdim), _ = kpts_view
+    if n_frames != n:
+        raise ValueError(f"frames: {n_frames} surfaces for a tensor of N = {n}")
+    D = operator.index(max_det)
+    if not 1 <= D <= MAX_DET:
+        raise ValueError(f"max_det = {D} is outside 1..{MAX_DET}")
+    if n * D > 65535:
+        raise ValueError(f"N * max_det = {n * D} exceeds 65535")
+    try:
+        pairs = [tuple(operator.index(v) for v in pair) for pair in limbs]
+    except TypeError:
+        raise ValueError("limbs: a sequence of (a, b) pairs of keypoint indices") from None
+    if any(len(pair) != 2 for pair in pairs):
+        raise ValueError("limbs: a sequence of (a, b) pairs of keypoint indices")
+    if len(pairs) > MAX_LIMBS:
+        raise ValueError(f"limbs: {len(pairs)} pairs; at most {MAX_LIMBS}")
+    for l, (a, b) in enumerate(pairs):
+        if not (0 <= a < p and 0 <= b < p):
+            raise ValueError(f"limbs: pair {l} = ({a}, {b}) is outside 0..{p - 1} (P = {p})")
+    return n, k, p, kdim, D, [v for pair in pairs for v in pair]
+
+
+def draw_spec(limb_colours, joint_colours, kpt_thr, thickness, diameter, alpha):
+    """What Run checks of its host arguments: (host limb colours or None for a device tensor, host joint colours or None,
+    kpt_thr, thickness, diameter, alpha as the C ABI takes it)"""
+    thr = float(kpt_thr)
+    if math.isnan(thr):
+        raise ValueError("kpt_thr must not be a NaN")
+    t, d = operator.index(thickness), operator.index(diameter)
+    if not 1 <= t <= MAX_WIDTH:
+        raise ValueError(f"thickness = {t} is outside 1..{MAX_WIDTH}")
+    if not 1 <= d <= MAX_WIDTH:
+        raise ValueError(f"diameter = {d} is outside 1..{MAX_WIDTH}")
+    a = -1
+    if alpha is not None:
+        a = operator.index(alpha)
+        if not 0 <= a <= 255:
+            raise ValueError(f"alpha = {a} is outside 0..255 (None keeps the colours' own)")
+    hosts = []
+    for name, colours in (("limb_colours", limb_colours), ("joint_colours", joint_colours)):
+        host = None
+        if not _is_device(colours):
+            try:
+                host = [operator.index(v) for v in colours]
+            except TypeError:
+                raise ValueError(f"{name}: an int32 device tensor or a sequence of packed colours (pack_colour)") from None
+            if not host:
+                raise ValueError(f"{name}: at least one colour")
+            if any(not -(1 << 31) <= v < (1 << 31) for v in host):
+                raise ValueError(f"{name}: every colour must fit an int32 (pack_colour)")
+        hosts.append(host)
+    return hosts[0], hosts[1], thr, t, d, a
+
+
+class PoseBatch:
+    """What PyPoseDrawer.Run works on: the frames, the head's keypoints, the selector's dets, the limb table, the points
+    and the workspace, checked and set up once (PyPoseDrawer.Prepare).  Keeps the surfaces and tensors alive."""
+
+    def __init__(self, gpu_id: int, stream: int, frames: Sequence[Surface], kpts, dets, max_det=100, limbs=COCO_SKELETON,
+                 points=None):
+        frames = list(frames)
+        fmt = _frames_of_one_format("PoseBatch", frames, PySurfaceAnnotator._FORMATS, gpu_id)
+        kp, kcode, kshape, kstr, kh = _view("kpts", kpts_layout, kpts, gpu_id)
+        n, k, p, kdim, D, flat = pose_spec(len(frames), (kcode, kshape, kstr), max_det, limbs)
+        if dets is None:
+            raise ValueError(f"dets: an int32 ({n * D}, 8) device tensor is required")
+        self.d_dets, dh = _device_i32("dets", dets, (n * D, 8), gpu_id)
+        self.d_points, ph = 0, None
+        if points is not None:
+            self.d_points, ph = _device_i32("points", points, (n * D, p, 4), gpu_id)
+            if self.d_points % 16:
+                raise ValueError("points: the tensor must be 16-byte aligned")
+        if is_capturing(gpu_id, stream):
+            raise RuntimeError("PoseBatch: cannot be created while the stream is capturing -- Prepare() before the "
+                               "StreamCapture block and Keep() the batch with the capture")
+        self.gpu_id, self._stream = gpu_id, stream
+        self.n, self.k, self.p, self.kdim, self.D, self.L = n, k, p, kdim, D, len(flat) // 2
+        self.format = fmt
+        self.sizes = [(d.Width, d.Height) for d in frames]
+        self.descs = [d.desc() for d in frames]
+        self.kpts = (kp, kcode, *kstr)
+        self._keep = [frames, kh, dh, ph]
+        self._rects_keep = None
+        self._colours_keep = [None, None]
+        self._colours = [None, None]          # the last host limb / joint colours
+        self.d_frames = self.d_ws = self.d_rects = self.d_limbs = self.d_limb_colours = self.d_joint_colours = 0
+        self.ws_bytes = shim.pose_workspace_size(n, D, p)
+        self.d_frames = shim.descs_upload(gpu_id, self.descs, stream)
+        self.d_ws = shim.mem_alloc(gpu_id, self.ws_bytes)
+        self.d_rects = shim.mem_alloc(gpu_id, 32 * n)
+        if flat:
+            buf = array.array("i", flat)
+            self.d_limbs = shim.mem_alloc(gpu_id, 4 * len(flat))
+            shim.memcpy2d_async(gpu_id, self.d_limbs, 4 * len(flat), buf.buffer_info()[0], 4 * len(flat), 4 * len(flat), 1,
+                                0, stream)
+            shim.stream_sync(gpu_id, stream)      # `buf` goes with this call
+
+    def __len__(self):
+        return self.n
+
+    def __del__(self):
+        _release(self, ("d_frames", "d_ws", "d_rects", "d_limbs", "d_limb_colours", "d_joint_colours"))
+
+
+class PyPoseDrawer(_SurfaceTask):
+    """The keypoints of a pose network (YOLOv8-pose and its relatives) for the selector's detections: mapped to frame
+    pixels, written to `points` and drawn IN PLACE as skeletons onto a batch of NV12, YUV420, YUV444, RGB, BGR or
+    RGB_PLANAR frames of any sizes, in two launches whatever the data, with nothing allocated and no synchronisation, so
+    the call can be captured and replayed after its tensors and frames were rewritten in place (vali_pose_paint).
+
+    pb = Prepare(frames, kpts, dets, max_det=100, limbs=COCO_SKELETON, points=None): `kpts` (N, K, P, 3) -- x, y,
+    confidence in the network input's coordinates -- or (N, K, P, 2) -- every confidence 1.0 -- is a float32, float16 or
+    bfloat16 GPU tensor (`__dlpack__`, or `__cuda_array_interface__` for float32 and float16) with any element strides
+    >= 0: a YOLOv8-pose head (N, 4 + 1 + 3 P, K) goes in as pred[:, 5:].transpose(1, 2).unflatten(2, (P, 3)), without a
+    copy.  `dets` is PyDetectionSelector's (N * max_det, 8) int32 tensor, read on the device only: row i * max_det + r
+    belongs to frame i and its `k` picks the keypoints.  `limbs` is a host sequence of (a, b) keypoint pairs, uploaded
+    once.  `points`, optional, is a contiguous (N * max_det, P, 4) int32 GPU tensor that every call rewrites in full:
+    X, Y, the confidence's float32 bits, flag (0 invisible, 1 visible, 3 visible and inside the frame); rows of skipped
+    detections are zero.  N 1..1024, K 1..2^20, P 1..64, at most 128 limbs, max_det 1..1024, N * max_det <= 65535.
+
+    Run(pb, rects, limb_colours, joint_colours, kpt_thr=0.5, thickness=3, diameter=7, alpha=None, cc_ctx=None): `rects`
+    is the (N, 8) int32 record array the frames were placed with, handled as PyDetectionSelector.Run handles it; limb l
+    is drawn in limb_colours[l % len], joint p in joint_colours[p % len], packed colours (pack_colour) as host sequences,
+    uploaded when they change, or int32 device tensors, at `alpha` (None: the colour's own).  A keypoint is visible when
+    its confidence is above `kpt_thr`; a limb needs both of its keypoints.  `thickness` and `diameter` are 1..64 pixels.
+    `cc_ctx` picks the RGB -> YUV matrix as PySurfaceAnnotator.RunBatch does.
+    """
+
+    def Prepare(self, frames: Sequence[Surface], kpts, dets, max_det=100, limbs=COCO_SKELETON, points=None) -> PoseBatch:
+        return PoseBatch(self._gpu_id, self._stream, frames, kpts, dets, max_det, limbs, points)
+
+    def _device_colours(self, pb, which, name, colours, host):
+        """(device pointer, count) of limb (which = 0) or joint (1) colours"""
+        attr = ("d_limb_colours", "d_joint_colours")[which]
+        if host is None:
+            shape = tuple(int(v) for v in (colours.__cuda_array_interface__["shape"]
+                                           if hasattr(colours, "__cuda_array_interface__") else colours.shape))
+            if len(shape) != 1 or shape[0] < 1:
+                raise ValueError(f"{name}: need an int32 tensor of shape (n,), n >= 1, got {shape}")
+            dc, pb._colours_keep[which] = _device_i32(name, colours, shape, self._gpu_id)
+            return dc, shape[0]
+        if pb._colours[which] != host:
+            if is_capturing(self._gpu_id, self._stream):
+                raise RuntimeError(f"PyPoseDrawer: host {name} cannot be uploaded while the stream is capturing -- Run "
+                                   "once with them before the capture, or pass a device tensor")
+            buf = array.array("i", host)
+            shim.stream_sync(self._gpu_id, self._stream)      # a launch may still read the colours it replaces
+            if getattr(pb, attr):
+                shim.mem_free(self._gpu_id, getattr(pb, attr))
+                setattr(pb, attr, 0)
+            setattr(pb, attr, shim.mem_alloc(self._gpu_id, 4 * len(host)))
+            shim.memcpy2d_async(self._gpu_id, getattr(pb, attr), 4 * len(host), buf.buffer_info()[0], 4 * len(host),
+                                4 * len(host), 1, 0, self._stream)
+            shim.stream_sync(self._gpu_id, self._stream)      # `buf` goes with this call
+            pb._colours[which] = host
+        return getattr(pb, attr), len(host)
+
+    def RunAsync(self, pb: PoseBatch, rects, limb_colours, joint_colours, kpt_thr=0.5, thickness=3, diameter=7,
+                 alpha=None, cc_ctx=None) -> Tuple[bool, TaskExecInfo]:
+        if not isinstance(pb, PoseBatch):
+            raise ValueError("Run: pass a PoseBatch (Prepare)")
+        lhost, jhost, thr, t, dia, a = draw_spec(limb_colours, joint_colours, kpt_thr, thickness, diameter, alpha)
+        params = None
+        if pb.format in (F.NV12, F.YUV420, F.YUV444):
+            mat = PySurfacePostprocessor.Matrix(cc_ctx)
+            if mat is None:
+                return _S_UNSUPP_CC.success, _S_UNSUPP_CC.info
+            params = _params(rgb2yuv=mat)
+        dlc, nlc = self._device_colours(pb, 0, "limb_colours", limb_colours, lhost)
+        djc, njc = self._device_colours(pb, 1, "joint_colours", joint_colours, jhost)
+        if _is_device(rects):
+            d_rects, pb._rects_keep = _device_rects(rects, pb.n, self._gpu_id)
+        else:
+            rows = _host_rects(rects, pb.n)
+            buf = array.array("i", [v for r in rows for v in r])
+            nbytes = 32 * pb.n
+            shim.memcpy2d_async(self._gpu_id, pb.d_rects, nbytes, buf.buffer_info()[0], nbytes, nbytes, 1, 0, self._stream)
+            shim.stream_sync(self._gpu_id, self._stream)      # `buf` goes with this call
+            d_rects = pb.d_rects
+        d = _status(shim.pose_paint(pb.descs, pb.d_frames, int(pb.format), pb.kpts, pb.kdim, pb.k, pb.p, pb.D, pb.d_limbs,
+                                    pb.L, pb.d_dets, d_rects, dlc, nlc, djc, njc, thr, t, dia, a, pb.d_points, params,
+                                    pb.d_ws, pb.ws_bytes, self._stream))
+        return d.success, d.info
+
+    def Run(self, pb: PoseBatch, rects, limb_colours, joint_colours, kpt_thr=0.5, thickness=3, diameter=7, alpha=None,
+            cc_ctx=None) -> Tuple[bool, TaskExecInfo]:
+        r = self.RunAsync(pb, rects, limb_colours, joint_colours, kpt_thr, thickness, diameter, alpha, cc_ctx)
+        self._sync()
+        return r
