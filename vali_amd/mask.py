@@ -12,43 +12,21 @@ import operator
 from typing import Sequence, Tuple
 
 from ._native import shim
-from .detect import _DTYPES, _CAI, _device_i32, _host_rects, _is_device
-from .enums import DLDeviceType, PixelFormat as F, TaskExecInfo
+from ._runargs import alpha_arg, host_colours, run_colours, run_rects
+from .enums import TaskExecInfo
 from .runtime import is_capturing
 from .surface import Surface
-from .tasks import (PySurfaceAnnotator, PySurfacePostprocessor, _S_UNSUPP_CC, _SurfaceTask, _device_rects,
-                    _frames_of_one_format, _params, _release, _status)
+from .tasks import (PySurfaceAnnotator, _UNSUPP_CC_PAIR, _SurfaceTask, _frames_of_one_format, _release, _rgb2yuv_params,
+                    _status)
+from .tensors import HEAD_CAI, device_float, device_i32, strided_layout
 
 MAX_FRAMES, MAX_PROTOS, MAX_SIDE, MAX_HEAD, MAX_DET, MAX_NET = 1024, 64, 1024, 1 << 20, 1024, 65535
-
-
-def _layout(who, dims, shape, strides, code, bits):
-    """a float32, float16 or bfloat16 view of len(dims) dimensions with element strides >= 0: (dtype code, shape, strides)"""
-    dtype = _DTYPES.get((int(code), int(bits)))
-    if dtype is None:
-        raise ValueError(f"{who}: the dtype must be float32, float16 or bfloat16 (DLPack code {code}, {bits} bits)")
-    shape = tuple(int(v) for v in shape)
-    if len(shape) != len(dims):
-        raise ValueError(f"{who}: need a {len(dims)}-D tensor ({', '.join(dims)}), got {len(shape)}-D {shape}")
-    if strides is None:
-        strides, step = [], 1
-        for size in reversed(shape):
-            strides.insert(0, step)
-            step *= size
-    strides = tuple(int(v) for v in strides)
-    if len(strides) != len(shape):
-        raise ValueError(f"{who}: {len(strides)} strides for a {len(shape)}-D tensor")
-    if any(v < 0 for v in strides):
-        raise ValueError(f"{who}: negative strides {strides} (a flipped view) are not supported")
-    if any(v > 1 << 40 for v in strides):
-        raise ValueError(f"{who}: strides {strides} beyond 2^40 elements")
-    return dtype[1], shape, strides
 
 
 def protos_layout(shape, strides, code, bits):
     """The rules for `protos`, without a device: (N, M, Hp, Wp) with an x stride of 1.  Returns (dtype code, shape,
     strides); ValueError, naming what is wrong, otherwise."""
-    code, shape, strides = _layout("protos", ("N", "M", "Hp", "Wp"), shape, strides, code, bits)
+    code, shape, strides = strided_layout("protos", ("N", "M", "Hp", "Wp"), shape, strides, code, bits)
     n, m, hp, wp = shape
     if not 1 <= n <= MAX_FRAMES:
         raise ValueError(f"protos: N = {n} is outside 1..{MAX_FRAMES}")
@@ -63,7 +41,7 @@ def protos_layout(shape, strides, code, bits):
 
 def coeffs_layout(shape, strides, code, bits):
     """The rules for `coeffs`, without a device: (N, K, M) with any element strides >= 0"""
-    code, shape, strides = _layout("coeffs", ("N", "K", "M"), shape, strides, code, bits)
+    code, shape, strides = strided_layout("coeffs", ("N", "K", "M"), shape, strides, code, bits)
     n, k, m = shape
     if not 1 <= n <= MAX_FRAMES:
         raise ValueError(f"coeffs: N = {n} is outside 1..{MAX_FRAMES}")
@@ -98,56 +76,8 @@ def mask_spec(n_frames, protos_view, coeffs_view, max_det=100, net_size=(640, 64
 
 def paint_spec(colours, alpha):
     """What Run checks of its host arguments: (host colours or None for a device tensor, alpha as the C ABI takes it)"""
-    a = -1
-    if alpha is not None:
-        a = operator.index(alpha)
-        if not 0 <= a <= 255:
-            raise ValueError(f"alpha = {a} is outside 0..255 (None keeps the colours' own)")
-    if _is_device(colours):
-        return None, a
-    try:
-        host = [operator.index(v) for v in colours]
-    except TypeError:
-        raise ValueError("colours: an int32 device tensor or a sequence of packed colours (pack_colour)") from None
-    if not host:
-        raise ValueError("colours: at least one colour")
-    if any(not -(1 << 31) <= v < (1 << 31) for v in host):
-        raise ValueError("colours: every colour must fit an int32 (pack_colour)")
-    return host, a
-
-
-def _view(who, layout_of, t, gpu_id):
-    """(ptr, dtype code, shape, strides, holder) of a device tensor on `gpu_id`"""
-    if hasattr(t, "__dlpack__"):
-        info, holder = shim.dlpack_import(t.__dlpack__())
-        if info["lanes"] != 1:
-            raise ValueError(f"{who}: vector dtypes are not supported")
-        code, shape, strides = layout_of(info["shape"], info["strides"], info["code"], info["bits"])
-        if info["device_type"] not in (int(DLDeviceType.kDLROCM), int(DLDeviceType.kDLCUDA)):
-            raise ValueError(f"{who}: the tensor must live on the GPU")
-        ptr, device = int(info["ptr"]), int(info["device_id"])
-    elif hasattr(t, "__cuda_array_interface__"):
-        cai = t.__cuda_array_interface__
-        if cai["typestr"] not in _CAI:
-            raise ValueError(f"{who}: the dtype must be float32 or float16 through __cuda_array_interface__ (bfloat16: "
-                             f"__dlpack__), got {cai['typestr']}")
-        dl_code, bits = _CAI[cai["typestr"]]
-        strides = cai.get("strides")
-        if strides is not None:
-            if any(int(v) % (bits // 8) for v in strides):
-                raise ValueError(f"{who}: strides that are no multiple of the element size")
-            strides = tuple(int(v) // (bits // 8) for v in strides)
-        code, shape, strides = layout_of(cai["shape"], strides, dl_code, bits)
-        ptr, holder = int(cai["data"][0]), t
-        dev = getattr(t, "device", None)
-        if getattr(dev, "type", "cuda") != "cuda":
-            raise ValueError(f"{who}: the tensor must live on the GPU")
-        device = dev.index if dev is not None and dev.index is not None else shim.ptr_device(ptr)
-    else:
-        raise ValueError(f"{who}: a device tensor with __dlpack__ or __cuda_array_interface__")
-    if device != gpu_id:
-        raise ValueError(f"{who}: the tensor is on device {device}, the task on {gpu_id}")
-    return ptr, code, shape, strides, holder
+    a = alpha_arg(alpha)
+    return host_colours("colours", colours), a
 
 
 class MaskBatch:
@@ -158,13 +88,13 @@ class MaskBatch:
                  net_size=(640, 640)):
         frames = list(frames)
         fmt = _frames_of_one_format("MaskBatch", frames, PySurfaceAnnotator._FORMATS, gpu_id)
-        pp, pcode, pshape, pstr, ph = _view("protos", protos_layout, protos, gpu_id)
-        cp, ccode, cshape, cstr, ch = _view("coeffs", coeffs_layout, coeffs, gpu_id)
+        pseen, (pcode, pshape, pstr) = device_float("protos", protos, protos_layout, gpu_id, *HEAD_CAI)
+        cseen, (ccode, cshape, cstr) = device_float("coeffs", coeffs, coeffs_layout, gpu_id, *HEAD_CAI)
         n, m, hp, wp, k, D, net_w, net_h = mask_spec(len(frames), (pcode, pshape, pstr), (ccode, cshape, cstr), max_det,
                                                      net_size)
         if dets is None:
             raise ValueError(f"dets: an int32 ({n * D}, 8) device tensor is required")
-        self.d_dets, dh = _device_i32("dets", dets, (n * D, 8), gpu_id)
+        self.d_dets, _, dh = device_i32("dets", dets, (n * D, 8), gpu_id)
         if is_capturing(gpu_id, stream):
             raise RuntimeError("MaskBatch: cannot be created while the stream is capturing -- Prepare() before the "
                                "StreamCapture block and Keep() the batch with the capture")
@@ -174,11 +104,11 @@ class MaskBatch:
         self.format = fmt
         self.sizes = [(d.Width, d.Height) for d in frames]
         self.descs = [d.desc() for d in frames]
-        self.protos = (pp, pcode, pstr[0], pstr[1], pstr[2])
-        self.coeffs = (cp, ccode, *cstr)
-        self._keep = [frames, ph, ch, dh]
-        self._rects_keep = self._colours_keep = None
-        self._colours = None        # (host values, device pointer) of the last host colours
+        self.protos = (pseen.ptr, pcode, pstr[0], pstr[1], pstr[2])
+        self.coeffs = (cseen.ptr, ccode, *cstr)
+        self._keep = [frames, pseen.holder, cseen.holder, dh]
+        self._rects_keep = None
+        self._colours_keep, self._colours = {}, {}        # run_colours: the device tensor, the last host colours
         self.d_frames = self.d_ws = self.d_rects = self.d_colours = 0
         self.ws_bytes = shim.mask_workspace_size(n, D, hp, wp)
         self.d_frames = shim.descs_upload(gpu_id, self.descs, stream)
@@ -220,46 +150,11 @@ class PyInstanceMasker(_SurfaceTask):
         if not isinstance(mb, MaskBatch):
             raise ValueError("Run: pass a MaskBatch (Prepare)")
         host, a = paint_spec(colours, alpha)
-        params = None
-        if mb.format in (F.NV12, F.YUV420, F.YUV444):
-            mat = PySurfacePostprocessor.Matrix(cc_ctx)
-            if mat is None:
-                return _S_UNSUPP_CC.success, _S_UNSUPP_CC.info
-            params = _params(rgb2yuv=mat)
-        import array
-
-        if host is None:
-            shape = tuple(int(v) for v in (colours.__cuda_array_interface__["shape"]
-                                           if hasattr(colours, "__cuda_array_interface__") else colours.shape))
-            if len(shape) != 1 or shape[0] < 1:
-                raise ValueError(f"colours: need an int32 tensor of shape (n,), n >= 1, got {shape}")
-            dc, mb._colours_keep = _device_i32("colours", colours, shape, self._gpu_id)
-            nc = shape[0]
-        else:
-            if mb._colours is None or mb._colours[0] != host:
-                if is_capturing(self._gpu_id, self._stream):
-                    raise RuntimeError("PyInstanceMasker: host colours cannot be uploaded while the stream is capturing "
-                                       "-- Run once with them before the capture, or pass a device tensor")
-                buf = array.array("i", host)
-                shim.stream_sync(self._gpu_id, self._stream)      # a launch may still read the colours it replaces
-                if mb.d_colours:
-                    shim.mem_free(self._gpu_id, mb.d_colours)
-                    mb.d_colours = 0
-                mb.d_colours = shim.mem_alloc(self._gpu_id, 4 * len(host))
-                shim.memcpy2d_async(self._gpu_id, mb.d_colours, 4 * len(host), buf.buffer_info()[0], 4 * len(host),
-                                    4 * len(host), 1, 0, self._stream)
-                shim.stream_sync(self._gpu_id, self._stream)      # `buf` goes with this call
-                mb._colours = (host, mb.d_colours)
-            dc, nc = mb.d_colours, len(host)
-        if _is_device(rects):
-            d_rects, mb._rects_keep = _device_rects(rects, mb.n, self._gpu_id)
-        else:
-            rows = _host_rects(rects, mb.n)
-            buf = array.array("i", [v for r in rows for v in r])
-            nbytes = 32 * mb.n
-            shim.memcpy2d_async(self._gpu_id, mb.d_rects, nbytes, buf.buffer_info()[0], nbytes, nbytes, 1, 0, self._stream)
-            shim.stream_sync(self._gpu_id, self._stream)      # `buf` goes with this call
-            d_rects = mb.d_rects
+        supported, params = _rgb2yuv_params(mb.format, cc_ctx)
+        if not supported:
+            return _UNSUPP_CC_PAIR
+        dc, nc = run_colours("PyInstanceMasker", mb, "colours", colours, host, self._gpu_id, self._stream)
+        d_rects = run_rects(mb, rects, self._gpu_id, self._stream)
         d = _status(shim.mask_paint(mb.descs, mb.d_frames, int(mb.format), mb.protos, mb.coeffs, mb.m, mb.hp, mb.wp, mb.k,
                                     mb.D, mb.net_w, mb.net_h, mb.d_dets, d_rects, dc, nc, a, params, mb.d_ws, mb.ws_bytes,
                                     self._stream))

@@ -8,19 +8,18 @@ tests/pose_model.py restates it in numpy.
 """
 from __future__ import annotations
 
-import array
 import math
 import operator
 from typing import Sequence, Tuple
 
 from ._native import shim
-from .detect import _device_i32, _host_rects, _is_device
-from .enums import PixelFormat as F, TaskExecInfo
-from .mask import _layout, _view
+from ._runargs import alpha_arg, host_colours, run_colours, run_rects
+from .enums import TaskExecInfo
 from .runtime import is_capturing
 from .surface import Surface
-from .tasks import (PySurfaceAnnotator, PySurfacePostprocessor, _S_UNSUPP_CC, _SurfaceTask, _device_rects,
-                    _frames_of_one_format, _params, _release, _status)
+from .tasks import (PySurfaceAnnotator, _UNSUPP_CC_PAIR, _SurfaceTask, _frames_of_one_format, _release, _rgb2yuv_params,
+                    _status)
+from .tensors import HEAD_CAI, device_float, device_i32, strided_layout, upload_i32
 
 MAX_FRAMES, MAX_HEAD, MAX_POINTS, MAX_LIMBS, MAX_DET, MAX_WIDTH = 1024, 1 << 20, 64, 128, 1024, 64
 
@@ -32,7 +31,7 @@ COCO_SKELETON = ((15, 13), (13, 11), (16, 14), (14, 12), (11, 12), (5, 11), (6, 
 def kpts_layout(shape, strides, code, bits):
     """The rules for `kpts`, without a device: (N, K, P, 3) or (N, K, P, 2) with any element strides >= 0.  Returns
     (dtype code, shape, strides); ValueError, naming what is wrong, otherwise."""
-    code, shape, strides = _layout("kpts", ("N", "K", "P", "3 or 2"), shape, strides, code, bits)
+    code, shape, strides = strided_layout("kpts", ("N", "K", "P", "3 or 2"), shape, strides, code, bits)
     n, k, p, c = shape
     if not 1 <= n <= MAX_FRAMES:
         raise ValueError(f"kpts: N = {n} is outside 1..{MAX_FRAMES}")
@@ -81,25 +80,8 @@ def draw_spec(limb_colours, joint_colours, kpt_thr, thickness, diameter, alpha):
         raise ValueError(f"thickness = {t} is outside 1..{MAX_WIDTH}")
     if not 1 <= d <= MAX_WIDTH:
         raise ValueError(f"diameter = {d} is outside 1..{MAX_WIDTH}")
-    a = -1
-    if alpha is not None:
-        a = operator.index(alpha)
-        if not 0 <= a <= 255:
-            raise ValueError(f"alpha = {a} is outside 0..255 (None keeps the colours' own)")
-    hosts = []
-    for name, colours in (("limb_colours", limb_colours), ("joint_colours", joint_colours)):
-        host = None
-        if not _is_device(colours):
-            try:
-                host = [operator.index(v) for v in colours]
-            except TypeError:
-                raise ValueError(f"{name}: an int32 device tensor or a sequence of packed colours (pack_colour)") from None
-            if not host:
-                raise ValueError(f"{name}: at least one colour")
-            if any(not -(1 << 31) <= v < (1 << 31) for v in host):
-                raise ValueError(f"{name}: every colour must fit an int32 (pack_colour)")
-        hosts.append(host)
-    return hosts[0], hosts[1], thr, t, d, a
+    a = alpha_arg(alpha)
+    return host_colours("limb_colours", limb_colours), host_colours("joint_colours", joint_colours), thr, t, d, a
 
 
 class PoseBatch:
@@ -110,14 +92,14 @@ class PoseBatch:
                  points=None):
         frames = list(frames)
         fmt = _frames_of_one_format("PoseBatch", frames, PySurfaceAnnotator._FORMATS, gpu_id)
-        kp, kcode, kshape, kstr, kh = _view("kpts", kpts_layout, kpts, gpu_id)
+        kseen, (kcode, kshape, kstr) = device_float("kpts", kpts, kpts_layout, gpu_id, *HEAD_CAI)
         n, k, p, kdim, D, flat = pose_spec(len(frames), (kcode, kshape, kstr), max_det, limbs)
         if dets is None:
             raise ValueError(f"dets: an int32 ({n * D}, 8) device tensor is required")
-        self.d_dets, dh = _device_i32("dets", dets, (n * D, 8), gpu_id)
+        self.d_dets, _, dh = device_i32("dets", dets, (n * D, 8), gpu_id)
         self.d_points, ph = 0, None
         if points is not None:
-            self.d_points, ph = _device_i32("points", points, (n * D, p, 4), gpu_id)
+            self.d_points, _, ph = device_i32("points", points, (n * D, p, 4), gpu_id)
             if self.d_points % 16:
                 raise ValueError("points: the tensor must be 16-byte aligned")
         if is_capturing(gpu_id, stream):
@@ -128,22 +110,17 @@ class PoseBatch:
         self.format = fmt
         self.sizes = [(d.Width, d.Height) for d in frames]
         self.descs = [d.desc() for d in frames]
-        self.kpts = (kp, kcode, *kstr)
-        self._keep = [frames, kh, dh, ph]
+        self.kpts = (kseen.ptr, kcode, *kstr)
+        self._keep = [frames, kseen.holder, dh, ph]
         self._rects_keep = None
-        self._colours_keep = [None, None]
-        self._colours = [None, None]          # the last host limb / joint colours
+        self._colours_keep, self._colours = {}, {}        # run_colours: the device tensors, the last host colours
         self.d_frames = self.d_ws = self.d_rects = self.d_limbs = self.d_limb_colours = self.d_joint_colours = 0
         self.ws_bytes = shim.pose_workspace_size(n, D, p)
         self.d_frames = shim.descs_upload(gpu_id, self.descs, stream)
         self.d_ws = shim.mem_alloc(gpu_id, self.ws_bytes)
         self.d_rects = shim.mem_alloc(gpu_id, 32 * n)
         if flat:
-            buf = array.array("i", flat)
-            self.d_limbs = shim.mem_alloc(gpu_id, 4 * len(flat))
-            shim.memcpy2d_async(gpu_id, self.d_limbs, 4 * len(flat), buf.buffer_info()[0], 4 * len(flat), 4 * len(flat), 1,
-                                0, stream)
-            shim.stream_sync(gpu_id, stream)      # `buf` goes with this call
+            self.d_limbs = upload_i32(gpu_id, stream, flat)
 
     def __len__(self):
         return self.n
@@ -179,54 +156,17 @@ class PyPoseDrawer(_SurfaceTask):
     def Prepare(self, frames: Sequence[Surface], kpts, dets, max_det=100, limbs=COCO_SKELETON, points=None) -> PoseBatch:
         return PoseBatch(self._gpu_id, self._stream, frames, kpts, dets, max_det, limbs, points)
 
-    def _device_colours(self, pb, which, name, colours, host):
-        """(device pointer, count) of limb (which = 0) or joint (1) colours"""
-        attr = ("d_limb_colours", "d_joint_colours")[which]
-        if host is None:
-            shape = tuple(int(v) for v in (colours.__cuda_array_interface__["shape"]
-                                           if hasattr(colours, "__cuda_array_interface__") else colours.shape))
-            if len(shape) != 1 or shape[0] < 1:
-                raise ValueError(f"{name}: need an int32 tensor of shape (n,), n >= 1, got {shape}")
-            dc, pb._colours_keep[which] = _device_i32(name, colours, shape, self._gpu_id)
-            return dc, shape[0]
-        if pb._colours[which] != host:
-            if is_capturing(self._gpu_id, self._stream):
-                raise RuntimeError(f"PyPoseDrawer: host {name} cannot be uploaded while the stream is capturing -- Run "
-                                   "once with them before the capture, or pass a device tensor")
-            buf = array.array("i", host)
-            shim.stream_sync(self._gpu_id, self._stream)      # a launch may still read the colours it replaces
-            if getattr(pb, attr):
-                shim.mem_free(self._gpu_id, getattr(pb, attr))
-                setattr(pb, attr, 0)
-            setattr(pb, attr, shim.mem_alloc(self._gpu_id, 4 * len(host)))
-            shim.memcpy2d_async(self._gpu_id, getattr(pb, attr), 4 * len(host), buf.buffer_info()[0], 4 * len(host),
-                                4 * len(host), 1, 0, self._stream)
-            shim.stream_sync(self._gpu_id, self._stream)      # `buf` goes with this call
-            pb._colours[which] = host
-        return getattr(pb, attr), len(host)
-
     def RunAsync(self, pb: PoseBatch, rects, limb_colours, joint_colours, kpt_thr=0.5, thickness=3, diameter=7,
                  alpha=None, cc_ctx=None) -> Tuple[bool, TaskExecInfo]:
         if not isinstance(pb, PoseBatch):
             raise ValueError("Run: pass a PoseBatch (Prepare)")
         lhost, jhost, thr, t, dia, a = draw_spec(limb_colours, joint_colours, kpt_thr, thickness, diameter, alpha)
-        params = None
-        if pb.format in (F.NV12, F.YUV420, F.YUV444):
-            mat = PySurfacePostprocessor.Matrix(cc_ctx)
-            if mat is None:
-                return _S_UNSUPP_CC.success, _S_UNSUPP_CC.info
-            params = _params(rgb2yuv=mat)
-        dlc, nlc = self._device_colours(pb, 0, "limb_colours", limb_colours, lhost)
-        djc, njc = self._device_colours(pb, 1, "joint_colours", joint_colours, jhost)
-        if _is_device(rects):
-            d_rects, pb._rects_keep = _device_rects(rects, pb.n, self._gpu_id)
-        else:
-            rows = _host_rects(rects, pb.n)
-            buf = array.array("i", [v for r in rows for v in r])
-            nbytes = 32 * pb.n
-            shim.memcpy2d_async(self._gpu_id, pb.d_rects, nbytes, buf.buffer_info()[0], nbytes, nbytes, 1, 0, self._stream)
-            shim.stream_sync(self._gpu_id, self._stream)      # `buf` goes with this call
-            d_rects = pb.d_rects
+        supported, params = _rgb2yuv_params(pb.format, cc_ctx)
+        if not supported:
+            return _UNSUPP_CC_PAIR
+        dlc, nlc = run_colours("PyPoseDrawer", pb, "limb_colours", limb_colours, lhost, self._gpu_id, self._stream)
+        djc, njc = run_colours("PyPoseDrawer", pb, "joint_colours", joint_colours, jhost, self._gpu_id, self._stream)
+        d_rects = run_rects(pb, rects, self._gpu_id, self._stream)
         d = _status(shim.pose_paint(pb.descs, pb.d_frames, int(pb.format), pb.kpts, pb.kdim, pb.k, pb.p, pb.D, pb.d_limbs,
                                     pb.L, pb.d_dets, d_rects, dlc, nlc, djc, njc, thr, t, dia, a, pb.d_points, params,
                                     pb.d_ws, pb.ws_bytes, self._stream))

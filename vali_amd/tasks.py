@@ -11,10 +11,12 @@ import operator
 from typing import List, Optional, Sequence, Tuple
 
 from ._native import shim
-from .enums import (ColorRange, ColorSpace, ColorspaceConversionContext, DLDeviceType, Interpolation, PixelFormat,
-                    TaskExecDetails, TaskExecInfo)
+from ._runargs import device_rects
+from .enums import (ColorRange, ColorSpace, ColorspaceConversionContext, Interpolation, PixelFormat, TaskExecDetails,
+                    TaskExecInfo)
 from .runtime import CudaStreamEvent, HipResMgr, is_capturing
 from .surface import Surface
+from .tensors import DTYPES, FLOAT_DTYPES, device_float, device_i32, is_tensor, upload_i32
 
 F = PixelFormat
 
@@ -819,7 +821,7 @@ class PySurfacePreprocessor(_SurfaceTask):
         p = self._params(None if is_rgb else cc_ctx)
         if p is None:
             return False, TaskExecInfo.UNSUPPORTED_FMT_CONV_PARAMS
-        d_roi, _hold = (batch.d_roi, None) if rects is None else _device_rects(rects, batch.n, batch.gpu_id)
+        d_roi, _hold = (batch.d_roi, None) if rects is None else device_rects(rects, batch.n, batch.gpu_id)
         if is_rgb:
             d = _status(shim.rgb_preproc_roi_batch(batch.d_src, batch.d_dst, d_roi, batch.n, int(batch.src_format),
                                                    batch.dst_size[0], batch.dst_size[1], int(batch.dst_format), p, on,
@@ -856,7 +858,7 @@ class PySurfacePreprocessor(_SurfaceTask):
         p = self._params(None if is_rgb else cc_ctx)
         if p is None:
             return False, TaskExecInfo.UNSUPPORTED_FMT_CONV_PARAMS
-        d_roi, _hold = (batch.d_roi, None) if rects is None else _device_rects(rects, batch.n, batch.gpu_id)
+        d_roi, _hold = (batch.d_roi, None) if rects is None else device_rects(rects, batch.n, batch.gpu_id)
         if is_rgb:
             d = _status(shim.rgb_preproc_roi_tensor(batch.d_src, d_roi, int(batch.src_format), batch.dst, p, on, rgb,
                                                     self._stream))
@@ -950,37 +952,6 @@ def _pad_colour(pad):
     return True, rgb
 
 
-def _device_rects(rects, n, gpu_id):
-    """(device pointer, holder) of an int32 (n, 8) contiguous device tensor; shape, dtype, device and contiguity are
-    all the host checks -- the values are the kernel's to sanitise."""
-    if hasattr(rects, "__cuda_array_interface__"):
-        cai = rects.__cuda_array_interface__
-        shape = tuple(int(v) for v in cai["shape"])
-        strides = cai.get("strides")
-        if cai["typestr"] not in ("<i4", "|i4") or shape != (n, 8):
-            raise ValueError(f"rects: need an int32 tensor of shape ({n}, 8), got {cai['typestr']} {shape}")
-        if strides is not None and (int(strides[1]) != 4 or (n > 1 and int(strides[0]) != 32)):
-            raise ValueError("rects: the tensor must be contiguous")
-        ptr, holder = int(cai["data"][0]), rects
-        dev = getattr(rects, "device", None)
-        device = dev.index if getattr(dev, "type", None) == "cuda" and dev.index is not None else shim.ptr_device(ptr)
-    elif hasattr(rects, "__dlpack__"):
-        info, holder = shim.dlpack_import(rects.__dlpack__())
-        shape, strides = tuple(info["shape"]), tuple(info["strides"])
-        if info["code"] != 0 or info["bits"] != 32 or info["lanes"] != 1 or shape != (n, 8):
-            raise ValueError(f"rects: need an int32 tensor of shape ({n}, 8)")
-        if strides[1] != 1 or (n > 1 and strides[0] != 8):
-            raise ValueError("rects: the tensor must be contiguous")
-        if info["device_type"] not in (int(DLDeviceType.kDLROCM), int(DLDeviceType.kDLCUDA)):
-            raise ValueError("rects: the tensor must live on the GPU")
-        ptr, device = int(info["ptr"]), int(info["device_id"])
-    else:
-        raise ValueError("rects: a device tensor with __cuda_array_interface__ or __dlpack__")
-    if device != gpu_id:
-        raise ValueError(f"rects: the tensor is on device {device}, the batch on {gpu_id}")
-    return ptr, holder
-
-
 class RoiBatch:
     """Device-resident arrays for n region items: source descriptors (one format, any sizes, repeats allowed),
     destination descriptors (one format and size) and rectangle records, uploaded once
@@ -1012,11 +983,8 @@ class RoiBatch:
         _release(self, ("d_src", "d_dst", "d_roi"))
 
 
-# DLPack dtype (code, bits) -> (name, enum vali_dtype): kDLFloat = 2, kDLBfloat = 4
-_TENSOR_DTYPES = {(2, 32): ("float32", 0), (2, 16): ("float16", 1), (4, 16): ("bfloat16", 2)}
-# ... and what the JPEG encoder also reads: kDLUInt = 1
-_TENSOR_SRC_DTYPES = dict(_TENSOR_DTYPES)
-_TENSOR_SRC_DTYPES[(1, 8)] = ("uint8", 3)
+# DLPack dtype (code, bits) -> (name, enum vali_dtype) of a destination tensor, and of one the JPEG encoder reads: uint8 too
+_TENSOR_DTYPES, _TENSOR_SRC_DTYPES = FLOAT_DTYPES, DTYPES
 
 
 def _layout(who, dtypes, shape, strides, code, bits):
@@ -1074,50 +1042,19 @@ def tensor_src_layout(shape, strides, code, bits):
 
 def _tensor_view(who, layout_of, cai_types, t, gpu_id):
     """(ptr, layout, dtype name, (n, h, w), (sn, sc, sy) in elements, holder) of a device tensor on `gpu_id`, seen
-    through __dlpack__ or __cuda_array_interface__ (`cai_types`: typestr -> (DLPack code, bits))"""
-    if hasattr(t, "__dlpack__"):
-        info, holder = shim.dlpack_import(t.__dlpack__())
-        if info["lanes"] != 1:
-            raise ValueError(f"{who}: vector dtypes are not supported")
-        shape, strides, code, bits = tuple(info["shape"]), tuple(info["strides"]), info["code"], info["bits"]
-        layout, dtype = layout_of(shape, strides, code, bits)
-        if info["device_type"] not in (int(DLDeviceType.kDLROCM), int(DLDeviceType.kDLCUDA)):
-            raise ValueError(f"{who}: the tensor must live on the GPU")
-        ptr, device = int(info["ptr"]), int(info["device_id"])
-    elif hasattr(t, "__cuda_array_interface__"):
-        cai = t.__cuda_array_interface__
-        typestr = cai["typestr"]
-        if typestr not in cai_types:
-            names = " or ".join(_TENSOR_SRC_DTYPES[v][0] for v in cai_types.values())
-            raise ValueError(f"{who}: the dtype must be {names} through __cuda_array_interface__, got {typestr}")
-        code, bits = cai_types[typestr]
-        shape = tuple(int(v) for v in cai["shape"])
-        strides = cai.get("strides")
-        if strides is not None:
-            if any(int(v) % (bits // 8) for v in strides):
-                raise ValueError(f"{who}: strides that are no multiple of the element size")
-            strides = tuple(int(v) // (bits // 8) for v in strides)
-        layout, dtype = layout_of(shape, strides, code, bits)
-        if strides is None:
-            strides = (3 * shape[2] * shape[3], shape[2] * shape[3], shape[3], 1)
-        ptr, holder = int(cai["data"][0]), t
-        dev = getattr(t, "device", None)
-        device = dev.index if getattr(dev, "type", None) == "cuda" and dev.index is not None else shim.ptr_device(ptr)
-    else:
-        raise ValueError(f"{who}: a device tensor with __dlpack__ or __cuda_array_interface__")
-    if device != gpu_id:
-        raise ValueError(f"{who}: the tensor is on device {device}, the task on {gpu_id}")
-    n, _, h, w = shape
-    sn, sc, sy, _ = strides
+    through __dlpack__ or __cuda_array_interface__ (`cai_types`: the typestrs it may have there)"""
+    seen, (layout, dtype) = device_float(who, t, layout_of, gpu_id, cai_types)
+    n, _, h, w = seen.shape
+    sn, sc, sy, _ = seen.strides or (3 * h * w, h * w, w, 1)
     row = w if layout == "planar" else 3 * w
     # strides of dimensions of size 1 are arbitrary: the kernel's addressing needs them positive and rows apart
-    return ptr, layout, dtype, (n, h, w), (max(sn, 1), max(sc, 1), max(sy, row)), holder
+    return seen.ptr, layout, dtype, (n, h, w), (max(sn, 1), max(sc, 1), max(sy, row)), seen.holder
 
 
 def _tensor_dst(out, gpu_id):
     """(shim.TensorDst, layout, dtype name, (n, h, w), holder) of a destination tensor on `gpu_id`"""
     ptr, layout, dtype, (n, h, w), (sn, sc, sy), holder = _tensor_view(
-        "out", tensor_layout, {"<f4": (2, 32), "<f2": (2, 16)}, out, gpu_id)
+        "out", tensor_layout, ("<f4", "<f2"), out, gpu_id)
     code = {"float32": shim.DTYPE_F32, "float16": shim.DTYPE_F16, "bfloat16": shim.DTYPE_BF16}[dtype]
     dst = shim.TensorDst(ptr, code, 1 if layout == "packed" else 0, n, w, h, sn, sc, sy)
     return dst, layout, dtype, (n, h, w), holder
@@ -1127,7 +1064,7 @@ def _tensor_src(tensor, gpu_id):
     """(shim.TensorSrc, layout, dtype name, (n, h, w), (ptr, stride_n, stride_c, stride_y), holder) of a tensor the
     JPEG encoder on `gpu_id` reads; strides in elements"""
     ptr, layout, dtype, (n, h, w), (sn, sc, sy), holder = _tensor_view(
-        "tensor", tensor_src_layout, {"<f4": (2, 32), "<f2": (2, 16), "|u1": (1, 8)}, tensor, gpu_id)
+        "tensor", tensor_src_layout, ("<f4", "<f2", "|u1"), tensor, gpu_id)
     code = {"float32": shim.DTYPE_F32, "float16": shim.DTYPE_F16, "bfloat16": shim.DTYPE_BF16,
             "uint8": shim.DTYPE_U8}[dtype]
     src = shim.TensorSrc(ptr, code, 1 if layout == "packed" else 0, n, w, h, sn, sc, sy)
@@ -1285,12 +1222,9 @@ class PySurfacePostprocessor(_SurfaceTask):
             raise ValueError(f"channels: 'RGB' or 'BGR', got {channels!r}")
         offset = _triple("offset", offset)
         scale = _triple("scale", (1.0 if batch.dtype == "uint8" else 255.0) if scale is None else scale)
-        params = None
-        if batch.dst_format in (F.NV12, F.YUV420, F.YUV444):
-            m = self.Matrix(cc_ctx)
-            if m is None:
-                return _S_UNSUPP_CC.success, _S_UNSUPP_CC.info
-            params = _params(rgb2yuv=m)
+        supported, params = _rgb2yuv_params(batch.dst_format, cc_ctx)
+        if not supported:
+            return _UNSUPP_CC_PAIR
         d = _status(shim.tensor_to_surfaces(batch.src, scale, offset, 1 if channels == "BGR" else 0, batch.d_dst,
                                             int(batch.dst_format), params, self._stream))
         return d.success, d.info
@@ -1300,6 +1234,18 @@ class PySurfacePostprocessor(_SurfaceTask):
         r = self.RunTensorBatchAsync(batch, scale, offset, cc_ctx, channels)
         self._sync()
         return r
+
+
+_UNSUPP_CC_PAIR = (_S_UNSUPP_CC.success, _S_UNSUPP_CC.info)
+
+
+def _rgb2yuv_params(fmt, cc_ctx):
+    """(supported, params) for a task that writes RGB values into frames of `fmt`: the params carry the RGB -> YUV matrix
+    `cc_ctx` picks (PySurfacePostprocessor.Matrix) and are None for the RGB formats; not supported: it picks none"""
+    if fmt not in (F.NV12, F.YUV420, F.YUV444):
+        return True, None
+    mat = PySurfacePostprocessor.Matrix(cc_ctx)
+    return (False, None) if mat is None else (True, _params(rgb2yuv=mat))
 
 
 # ---- PySurfaceAnnotator: outlines, fills and pixelation from GPU-held marks ------------------------------
@@ -1364,41 +1310,6 @@ def _host_marks(rows, sizes, is420, atlas_size=None):
         if x0 >= fw or y0 >= fh or x1 <= 0 or y1 <= 0:
             raise ValueError(f"marks: row {i}: the rectangle ({x}, {y}, {w}, {h}) does not meet frame {frame} ({fw}x{fh})")
     return out
-
-
-def _device_marks(marks, gpu_id):
-    """(device pointer, rows, holder) of an int32 (M, 8) contiguous device tensor: _device_rects' checks; the values are
-    the kernel's to sanitise"""
-    if hasattr(marks, "__cuda_array_interface__"):
-        cai = marks.__cuda_array_interface__
-        shape = tuple(int(v) for v in cai["shape"])
-        strides = cai.get("strides")
-        if cai["typestr"] not in ("<i4", "|i4") or len(shape) != 2 or shape[1] != 8:
-            raise ValueError(f"marks: need an int32 tensor of shape (M, 8), got {cai['typestr']} {shape}")
-        if strides is not None and (int(strides[1]) != 4 or (shape[0] > 1 and int(strides[0]) != 32)):
-            raise ValueError("marks: the tensor must be contiguous")
-        ptr, holder = int(cai["data"][0]), marks
-        dev = getattr(marks, "device", None)
-        if getattr(dev, "type", "cuda") != "cuda":
-            raise ValueError("marks: the tensor must live on the GPU")
-        device = dev.index if dev is not None and dev.index is not None else (shim.ptr_device(ptr) if ptr else gpu_id)
-    elif hasattr(marks, "__dlpack__"):
-        info, holder = shim.dlpack_import(marks.__dlpack__())
-        shape, strides = tuple(info["shape"]), tuple(info["strides"])
-        if info["code"] != 0 or info["bits"] != 32 or info["lanes"] != 1 or len(shape) != 2 or shape[1] != 8:
-            raise ValueError(f"marks: need an int32 tensor of shape (M, 8), got shape {shape}")
-        if strides[1] != 1 or (shape[0] > 1 and strides[0] != 8):
-            raise ValueError("marks: the tensor must be contiguous")
-        if info["device_type"] not in (int(DLDeviceType.kDLROCM), int(DLDeviceType.kDLCUDA)):
-            raise ValueError("marks: the tensor must live on the GPU")
-        ptr, device = int(info["ptr"]), int(info["device_id"])
-    else:
-        raise ValueError("marks: a device tensor with __cuda_array_interface__ or __dlpack__, or a sequence of 8-tuples")
-    if device != gpu_id:
-        raise ValueError(f"marks: the tensor is on device {device}, the batch on {gpu_id}")
-    if shape[0] > MAX_MARKS:
-        raise ValueError(f"marks: {shape[0]} rows; at most {MAX_MARKS} per call")
-    return ptr, shape[0], holder
 
 
 def _atlas_size(atlas, gpu_id):
@@ -1486,8 +1397,11 @@ class PySurfaceAnnotator(_SurfaceTask):
         if not isinstance(batch, AnnotateBatch):
             raise ValueError("RunBatch: pass an AnnotateBatch (PrepareBatch)")
         atlas_size = _atlas_size(atlas, self._gpu_id) if atlas is not None else None
-        if hasattr(marks, "__cuda_array_interface__") or hasattr(marks, "__dlpack__"):
-            ptr, m, batch._marks_keep = _device_marks(marks, self._gpu_id)
+        if is_tensor(marks):      # the values are the kernel's to sanitise
+            ptr, (m, _), batch._marks_keep = device_i32("marks", marks, (None, 8), self._gpu_id, "the batch", "(M, 8)",
+                                                        least=0)
+            if m > MAX_MARKS:
+                raise ValueError(f"marks: {m} rows; at most {MAX_MARKS} per call")
             host = None
         else:
             try:
@@ -1499,21 +1413,13 @@ class PySurfaceAnnotator(_SurfaceTask):
                 raise ValueError(f"marks: {len(rows)} rows; at most {MAX_MARKS} per call")
             host = _host_marks(rows, batch.sizes, batch.format in (F.NV12, F.YUV420), atlas_size)
             ptr, m = batch.d_marks, len(host)
-        params = None
-        if batch.format in (F.NV12, F.YUV420, F.YUV444):
-            mat = PySurfacePostprocessor.Matrix(cc_ctx)
-            if mat is None:
-                return _S_UNSUPP_CC.success, _S_UNSUPP_CC.info
-            params = _params(rgb2yuv=mat)
+        supported, params = _rgb2yuv_params(batch.format, cc_ctx)
+        if not supported:
+            return _UNSUPP_CC_PAIR
         if batch.n == 0 or m == 0:
             return _OK_PAIR
         if host is not None:
-            import array
-
-            buf = array.array("i", [v for r in host for v in r])
-            src, nbytes = buf.buffer_info()[0], 32 * m
-            shim.memcpy2d_async(self._gpu_id, ptr, nbytes, src, nbytes, nbytes, 1, 0, self._stream)
-            shim.stream_sync(self._gpu_id, self._stream)      # `buf` goes with this call
+            upload_i32(self._gpu_id, self._stream, [v for r in host for v in r], ptr)
         batch._atlas_keep = atlas
         d = _status(shim.annotate_batch(batch.descs, batch.d_frames, int(batch.format), ptr, m, params, batch.d_ws,
                                         batch.ws_bytes, self._stream, atlas.desc() if atlas is not None else None))
