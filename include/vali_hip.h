@@ -740,6 +740,56 @@ VALI_API int vali_mask_paint(const vali_surface* frames, const vali_surface* d_f
                              const int32_t* d_colours, int n_colours, int alpha, const vali_cvt_params* params,
                              void* d_ws, size_t ws_bytes, vali_stream_t stream);
 
+/* ---- semantic maps: a segmentation head's class logits as a class map per frame, tinted onto the frames ---------------
+ *
+ * logits (n, c, hs, ws), float32, float16 or bfloat16 (x stride 1, the n, c and y strides any values >= 0: a broadcast, a
+ * slice of a larger head) and d_rects[i] the record frame i was placed with.  Every frame pixel inside the record's source
+ * rectangle gets the class whose bilinearly upsampled logit is largest; the classes are written to label surfaces and / or
+ * blended IN PLACE onto n frames of one format (the six of vali_annotate_batch, under its rules for frames) in ONE launch
+ * whatever the data; nothing is allocated and nothing synchronises, so the call can be captured and replayed after logits,
+ * d_rects, d_colours and the frames were rewritten in place.  The reference has no such task.
+ * All arithmetic is IEEE float32, one rounding per operation, never a fused multiply-add; (float) of an integer rounds
+ * to nearest.  Frame i is W x H with record src_x, src_y, src_w, src_h, dst_x, dst_y, dst_w, dst_h:
+ *   1. skipped  a record with src_w, src_h, dst_w or dst_h below 1 paints nothing on its frame; its label surface becomes
+ *               all 255.
+ *   2. region   only frame pixels inside frame ^ [src_x, src_x + src_w) x [src_y, src_y + src_h) are classified: the
+ *               intersection is formed in 64 bits, every int32 value is handled, and the region is NOT snapped to even
+ *               coordinates.  Every other pixel is left as it is and has label 255.
+ *   3. sample   steps 3 and 4 of vali_mask_paint with ws / net_w and hs / net_h in place of wp / net_w and hp / net_h,
+ *               on the plane L = (float)logits[i][c]: v_c for every class c.
+ *   4. label    c >= 2: best = -inf, label = 0; for c ascending: if v_c > best then best = v_c, label = c (the lowest
+ *               class wins ties, a NaN never wins, all NaN or all -inf gives 0).  c = 1, a binary head: label = v_0 > 0 ?
+ *               1 : 0, so there are two classes.
+ *   5. blend    bit for bit what vali_annotate_batch_atlas gives for one VALI_MARK_STAMP row per class, in ascending
+ *               class order, over an atlas holding each class's mask as 255 / 0, in the colour d_colours[class mod
+ *               n_colours], a its alpha or, with alpha in 0..255, alpha (alpha = -1 keeps the colour's).  A
+ *               full-resolution sample has exactly one class: one blend with k = 255.  A 4:2:0 chroma sample blends the
+ *               classes present among its four luma pixels in ascending order, each with k = (255 * count + 2) >> 2;
+ *               pixels outside the region count for no class.  a_eff, the rounding and the YUV colour of an RGB triple
+ *               (params->rgb2yuv) are STAMP's.  Samples whose value does not change are not stored; nothing outside a
+ *               plane's image area is written; a tile no region pixel meets is not read.
+ *   6. labels   labels[i][y][x] = the label, or 255 outside the region: every pixel of every label surface is rewritten
+ *               by every call.
+ * Limits: n 1..1024, c 1..255, hs and ws 1..4096, net_w and net_h 1..65535.
+ * labels / d_labels: both NULL, or the host copy and the device array of n descriptors of VALI_FMT_Y surfaces, labels[i] of
+ * the size of frames[i], at any address and pitch.  d_colours NULL: nothing is painted, only the labels are written.
+ * VALI_ERR_INVALID_ARG, before any device is touched: null frames, d_frames, in or d_rects, only one of labels and d_labels,
+ * neither d_labels nor d_colours, null params for a YUV format that is painted; a null tensor pointer, a dtype outside the
+ * three, a pointer not aligned to its element, a stride outside 0..2^40; a limit above broken; n_colours < 1 with
+ * d_colours; alpha outside -1..255; d_rects or d_colours not 4-byte aligned; a frame that breaks vali_annotate_batch's
+ * rules; a label surface whose format is not Y, whose size differs from its frame's, with a null plane or a pitch shorter
+ * than a row.  VALI_ERR_UNSUPPORTED for a format outside the six.
+ */
+typedef struct vali_semantic_in {
+  vali_mask_tensor logits;               /* the (n, c, hs, ws) tensor; strides read as n, c, y */
+  int32_t c, hs, ws, net_w, net_h, reserved;
+} vali_semantic_in;                      /* 64 bytes */
+
+VALI_API int vali_semantic_paint(const vali_surface* frames, const vali_surface* d_frames, int n, int format,
+                                 const vali_semantic_in* in, const vali_roi* d_rects, const vali_surface* labels,
+                                 const vali_surface* d_labels, const int32_t* d_colours, int n_colours, int alpha,
+                                 const vali_cvt_params* params, vali_stream_t stream);
+
 /* ---- pose skeletons: a keypoint head's points in frame pixels, drawn as limbs and joints ---------------
  *
  * kpts (n, k, p, kdim), float32, float16 or bfloat16 with any four element strides >= 0 (a transposed, unflattened head

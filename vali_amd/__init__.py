@@ -25,6 +25,7 @@ if not _BUILDING:
     from .detect import DetectionStyle, PyDetectionSelector, SelectBatch
     from .mask import MaskBatch, PyInstanceMasker
     from .pose import COCO_SKELETON, PoseBatch, PyPoseDrawer
+    from .semantic import PySemanticPainter, SemanticBatch
     from .pipeline import BatchedFramePipeline, broadcast_coefficients, shard_frames
     from .transfer import PyFrameUploader, PySurfaceDownloader
     from . import tuning

@@ -18,10 +18,12 @@
 //                   registers, applies all hits in order -- the logits come through the L2 -- and stores a piece only if a
 //                   mask changed it.  The blend is STAMP's (cover_piece) with the coverage made on the fly.
 // The formats and the frame rules, the tile's pieces, the hit list and the coverage blend are tile_paint.hpp's, shared
-// with annotate.hip, the rows det_rows.hpp's, shared with pose.hip; here are the sampler and the coverage of a hit.
+// with annotate.hip, the rows det_rows.hpp's, shared with pose.hip, the sampler (step 3) head_sampler.hpp's, shared with
+// semantic.hip; here is the coverage of a hit.
 #include <math.h>
 
 #include "det_rows.hpp"
+#include "head_sampler.hpp"
 #include "tensor_in.hpp"
 
 #pragma clang fp contract(off)
@@ -47,34 +49,6 @@ struct MaskArgs {
   int n_colours, alpha;
   float m[3][4];  // rgb2yuv rows (YUV formats)
 };
-
-// step 3 of the definition along one axis
-struct Axis {
-  float src, scale, dst, k;
-  int P;
-};
-__device__ __forceinline__ Axis make_axis(int src, int src_n, int dst, int dst_n, int P, int net) {
-  Axis a;
-  a.src = (float)src, a.scale = __fdiv_rn((float)dst_n, (float)src_n), a.dst = (float)dst;
-  a.k = __fdiv_rn((float)P, (float)net);
-  a.P = P;
-  return a;
-}
-struct Tap {
-  int i0, i1;
-  float t;
-};
-__device__ __forceinline__ Tap axis_tap(const Axis& a, int px) {
-  const float g = __fadd_rn(__fmul_rn(__fsub_rn(__fadd_rn((float)px, 0.5f), a.src), a.scale), a.dst);
-  const float f = __fsub_rn(__fmul_rn(g, a.k), 0.5f);
-  float x0 = floorf(f);
-  Tap t;
-  t.t = __fsub_rn(f, x0);
-  x0 = fminf(fmaxf(x0, -1.0f), (float)a.P);
-  const int i = (int)x0;
-  t.i0 = min(max(i, 0), a.P - 1), t.i1 = min(max(i + 1, 0), a.P - 1);
-  return t;
-}
 
 // ---- launch 1: the logits a row's box can sample ------------------------------------------------------------------------
 template <int DT>

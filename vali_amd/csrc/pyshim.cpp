@@ -778,6 +778,32 @@ PYBIND11_MODULE(_vali_shim, m) {
                                  ws_bytes, P(stream));
         });
 
+  // semantic maps: logits = (ptr, dtype, stride_n, stride_c, stride_y); descs / labels = the host copies of the
+  // descriptors in d_frames / d_labels (labels empty and d_labels 0: no label surfaces); d_colours 0: labels only
+  m.def("semantic_paint",
+        [](const std::vector<SurfaceDesc>& descs, uintptr_t d_frames, int format, const std::array<int64_t, 5>& logits,
+           int c, int hs, int ws, int net_w, int net_h, uintptr_t d_rects, const std::vector<SurfaceDesc>& labels,
+           uintptr_t d_labels, uintptr_t d_colours, int n_colours, int alpha, const CvtParams* p, uintptr_t stream) {
+          std::vector<vali_surface> host(descs.size()), lab(labels.size());
+          for (size_t i = 0; i < descs.size(); ++i)
+            host[i] = descs[i].s;
+          for (size_t i = 0; i < labels.size(); ++i)
+            lab[i] = labels[i].s;
+          if (!lab.empty() && lab.size() != host.size())
+            throw py::value_error("semantic_paint: as many label descriptors as frames, or none");
+          vali_semantic_in in;
+          std::memset(&in, 0, sizeof(in));
+          in.logits.data = P((uintptr_t)logits[0]);
+          in.logits.dtype = (int32_t)logits[1];
+          in.logits.stride_n = logits[2]; in.logits.stride_m = logits[3]; in.logits.stride_y = logits[4];
+          in.c = c; in.hs = hs; in.ws = ws; in.net_w = net_w; in.net_h = net_h;
+          py::gil_scoped_release nogil;
+          return vali_semantic_paint(host.empty() ? nullptr : host.data(), (const vali_surface*)P(d_frames),
+                                     (int)host.size(), format, &in, (const vali_roi*)P(d_rects),
+                                     lab.empty() ? nullptr : lab.data(), (const vali_surface*)P(d_labels),
+                                     (const int32_t*)P(d_colours), n_colours, alpha, p ? &p->p : nullptr, P(stream));
+        });
+
   // pose skeletons: kpts = (ptr, dtype, stride_n, stride_k, stride_p, stride_c); descs = the host copy of the descriptors
   // in d_frames; d_points may be 0 (the rows go to the workspace); everything else as in the header
   m.def("pose_workspace_size", [](int n, int max_det, int p) { return vali_pose_workspace_size(n, max_det, p); });
