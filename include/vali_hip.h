@@ -861,6 +861,81 @@ VALI_API int vali_pose_paint(const vali_surface* frames, const vali_surface* d_f
                              const vali_pose_style* style, int32_t* d_points, const vali_cvt_params* params,
                              void* d_ws, size_t ws_bytes, vali_stream_t stream);
 
+/* ---- aligned crops: affine views of frames, from the caller's matrices or fitted to keypoints, into a batch tensor -----
+ *
+ * The second stage that needs a rotated or aligned crop: a face onto the 112 x 112 ArcFace canvas by its five landmarks,
+ * a rotated rectangle (licence plate, scene text, oriented box) to an upright crop, any per-crop transform computed on
+ * the GPU.  The reference has no such task.  Slot m of an (M, 3, h, w) tensor (vali_tensor_dst: float32, float16 or
+ * bfloat16, planar or channels last, addressed as for vali_nv12_preproc_roi_tensor) is one affine view of one of n frames
+ * of ONE format among NV12 (even sizes), RGB, BGR and RGB_PLANAR, of any sizes, addresses and pitches, read only.
+ * d_matrices: M rows of 8 int32 in device memory, (frame, a, b, c, d, e, f, status), the six middle values float32 bit
+ * patterns: the caller's, or vali_warp_fit's.  Nothing is allocated, nothing synchronises, no matrix, keypoint or box
+ * reaches the host: both calls can be captured and replayed after the matrices, kpts, d_dets, d_rects and the frames were
+ * rewritten in place.  Float arithmetic is IEEE float32, one rounding per operation, never a fused multiply-add unless
+ * written fma(); (float) of an integer is exact here.
+ * Coordinates: frame and canvas positions are continuous; pixel X covers [X, X + 1) and its centre is X + 0.5 (the
+ * convention in which vali_pose_paint takes X = floor(fx)).
+ *
+ * vali_warp_tensor (ONE launch), slot m with its row and the W x H frame `frame`:
+ *   1. skipped  when frame is outside 0..n-1: the canvas is all pad, or untouched with pad == 0; no frame is read.
+ *   2. position canvas pixel (x, y): u = (float)x + 0.5f, v = (float)y + 0.5f, sx = ((a * u) + (b * v)) + c,
+ *               sy = ((d * u) + (e * v)) + f, per pixel as written (never stepped from a neighbour).  The pixel is inside
+ *               when 0 <= sx < W and 0 <= sy < H, tested on the floats: a NaN never is, and every float32 bit pattern in
+ *               a row is handled.  A pixel that is not inside is pad, or is not written.
+ *   3. taps     along x: g = sx - 0.5f, x0 = floor(g), t = g - x0, indices clamp(x0, 0, W - 1) and clamp(x0 + 1, 0,
+ *               W - 1) (edge replication); along y likewise.  Per 8-bit channel top = p00 + tx * (p01 - p00), bot = p10 +
+ *               tx * (p11 - p10), val = top + ty * (bot - top), q = round-half-even of val to 0..255.
+ *   4. colour   RGB, BGR, RGB_PLANAR: q_R, q_G, q_B by name, as in vali_rgb_preproc_roi.  NV12: Y by step 3 on the luma
+ *               plane; U and V independently on the (W / 2) x (H / 2) chroma plane at sx * 0.5f and sy * 0.5f in place of
+ *               sx and sy (centre-sited chroma, the same tap rule); (q_Y, q_U, q_V) then becomes q_R, q_G, q_B by the
+ *               YUV444 -> RGB arithmetic of vali_convert with yuv2rgb = params->csc (oracle/vali_oracle.c).
+ *   5. element  out[m, c, y, x] = convert(dtype, ((q_c / 255.0f) / div - mean[c]) / std_[c]): step 3 and the convert of
+ *               vali_nv12_preproc_roi_tensor, bit for bit.  The pad colour pad_rgb goes through the same step.
+ * frames is the HOST copy of the n descriptors in d_frames (the rules are checked on it); dst and params are host structs
+ * that travel in the kernel arguments; for the RGB family params->csc is ignored.
+ * VALI_ERR_INVALID_ARG, before any device is touched: null frames, d_frames, d_matrices, dst or params; pad without a
+ * colour; n outside 1..1024; a frame of another format than `format`, of a size outside 1..65535, of odd size (NV12),
+ * with a null plane or a pitch shorter than a row; everything vali_rgb_preproc_roi_tensor refuses of dst (dst->n = M is
+ * 1..65535); d_frames or d_matrices not 4-byte aligned; a canvas of more than 2^31 - 1 tiles.  VALI_ERR_UNSUPPORTED for a
+ * format outside the four.
+ *
+ * vali_warp_fit (ONE launch) writes row i * D + r of d_matrices (16-byte aligned, n * D rows, every row rewritten by every
+ * call) from row i * D + r of d_dets (vali_detect_select's, D = max_det), kpts (vali_pose_paint's, with its strides and
+ * dtypes), the record d_rects[i] and d_template, p pairs (u, v) of float32 in canvas coordinates in device memory:
+ *   1. skipped  exactly when vali_pose_paint skips the row (its step 1).  The row is then (-1, 0, 0, 0, 0, 0, 0, 0).
+ *   2. used     keypoint j maps to (fx, fy) by step 2 of vali_pose_paint; it is used when it is visible by its step 3
+ *               under kpt_thr and neither u_j nor v_j is a NaN (a template pair with a NaN takes no part: a 17-point head
+ *               is aligned by its eyes alone).
+ *   3. fit      over the used j in ascending order: n, Su, Sv, Sfx, Sfy; mu = Su / (float)n, mv, mx, my likewise; then
+ *               with du = u - mu, dv = v - mv, dx = fx - mx, dy = fy - my: A += (du * dx) + (dv * dy), B += (du * dy) -
+ *               (dv * dx), Dn += (du * du) + (dv * dv); al = A / Dn, be = B / Dn.  The row is
+ *               (i, al, -be, mx - ((al * mu) - (be * mv)), be, al, my - ((be * mu) + (al * mv)), n):
+ *               the least-squares similarity (rotation, uniform scale, shift, no reflection) that takes the template
+ *               onto the keypoints; with two points it is exact.
+ *   4. skipped  as in step 1 when n < min_points, Dn == 0, or al or be is not finite.
+ * VALI_ERR_INVALID_ARG, before any device is touched: null d_frames, in, d_dets, d_rects, d_matrices, kpts or d_template;
+ * n outside 1..1024, k outside 1..2^20, p outside 2..64, kdim other than 2 or 3, max_det outside 1..1024, n * max_det
+ * above 65535, min_points outside 2..p; a dtype outside the three, a kpts pointer not aligned to its element, a stride
+ * outside 0..2^40; a NaN kpt_thr; d_frames, d_dets, d_rects or d_template not 4-byte aligned, d_matrices not 16-byte
+ * aligned.
+ */
+typedef struct vali_warp_fit_in {
+  const void* kpts;                      /* element (0, 0, 0, 0) */
+  int32_t dtype;                         /* VALI_DTYPE_F32, _F16 or _BF16 */
+  int32_t kdim;                          /* 3: (kx, ky, conf); 2: (kx, ky), conf = 1.0 */
+  int64_t stride_n, stride_k, stride_p, stride_c; /* in elements, >= 0 */
+  int32_t k, p, max_det, min_points;
+  const float* d_template;               /* device, p pairs (u, v) */
+  float kpt_thr;
+  int32_t reserved;
+} vali_warp_fit_in;                      /* 80 bytes */
+
+VALI_API int vali_warp_fit(const vali_surface* d_frames, int n, const vali_warp_fit_in* in, const int32_t* d_dets,
+                           const vali_roi* d_rects, int32_t* d_matrices, vali_stream_t stream);
+VALI_API int vali_warp_tensor(const vali_surface* frames, const vali_surface* d_frames, int n, int format,
+                              const int32_t* d_matrices, const vali_tensor_dst* dst, const vali_preproc_params* params,
+                              int pad, const uint8_t pad_rgb[3], vali_stream_t stream);
+
 /*
  * Rectangles of surfaces of ANY sizes as files, in one fixed set of launches.  Item i is rectangle rois[i] of the
  * surface d_src[i] (the same surface may stand behind any number of items); its file is byte for byte the file of

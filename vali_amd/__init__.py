@@ -26,6 +26,7 @@ if not _BUILDING:
     from .mask import MaskBatch, PyInstanceMasker
     from .pose import COCO_SKELETON, PoseBatch, PyPoseDrawer
     from .semantic import PySemanticPainter, SemanticBatch
+    from .warp import ARCFACE_112, PySurfaceWarper, WarpBatch
     from .pipeline import BatchedFramePipeline, broadcast_coefficients, shard_frames
     from .transfer import PyFrameUploader, PySurfaceDownloader
     from . import tuning

@@ -23,6 +23,7 @@
 #include <math.h>
 
 #include "det_rows.hpp"
+#include "kpt_map.hpp"
 #include "tensor_in.hpp"
 
 #pragma clang fp contract(off)
@@ -32,8 +33,6 @@ namespace {
 
 constexpr int kMaxN = 1024, kMaxK = 1 << 20, kMaxD = 1024, kMaxP = 64, kMaxL = 128, kMaxT = 64;
 static_assert(kMaxL + kMaxP <= kBlock, "a lane for every shape of a hit");
-// step 3: a visible keypoint has -65536 <= fx < 131072
-constexpr float kLoF = -65536.0f, kHiF = 131072.0f;
 
 struct PoseArgs {
   const vali_surface* d_frames;
@@ -54,13 +53,7 @@ struct PoseArgs {
   float m[3][4];  // rgb2yuv rows (YUV formats)
 };
 
-// ---- launch 1: the points and the box of a row --------------------------------------------------------------------------
-// step 2 along one axis: one rounding per operation
-__device__ __forceinline__ float map_axis(float v, int dst, int src_n, int dst_n, int src) {
-  const float scale = __fdiv_rn((float)src_n, (float)dst_n);
-  return __fadd_rn(__fmul_rn(__fsub_rn(v, (float)dst), scale), (float)src);
-}
-
+// ---- launch 1: the points and the box of a row (the mapping and the visibility rule: kpt_map.hpp) -----------------------
 __device__ __forceinline__ int wave_min(int v) {
 #pragma unroll
   for (int d = 1; d < kWave; d <<= 1)
@@ -105,9 +98,7 @@ __global__ void __launch_bounds__(kBlock) k_pose_points(const PoseArgs a) {
       conf = E::f((u32)p[2 * a.sc]);
     const float fx = map_axis(kx, rc.dst_x, rc.src_w, rc.dst_w, rc.src_x);
     const float fy = map_axis(ky, rc.dst_y, rc.src_h, rc.dst_h, rc.src_y);
-    // (a NaN fails every comparison; fabsf(v) < inf: v is finite)
-    const bool vis = conf > a.thr && fabsf(kx) < INFINITY && fabsf(ky) < INFINITY && fx >= kLoF && fx < kHiF &&
-                     fy >= kLoF && fy < kHiF;
+    const bool vis = kpt_visible(conf, a.thr, kx, ky, fx, fy);
     if (vis) {
       X = (int)floorf(fx), Y = (int)floorf(fy);
       flag = (X >= 0 && X < W && Y >= 0 && Y < H) ? 3 : 1;

@@ -837,6 +837,38 @@ PYBIND11_MODULE(_vali_shim, m) {
                                  (int32_t*)P(d_points), p ? &p->p : nullptr, P(workspace), ws_bytes, P(stream));
         });
 
+  // aligned crops: kpts as for pose_paint; descs = the host copy of the descriptors in d_frames; everything else as in the
+  // header
+  m.def("warp_fit",
+        [](uintptr_t d_frames, int n, const std::array<int64_t, 6>& kpts, int kdim, int k, int pp, int max_det,
+           int min_points, uintptr_t d_template, float kpt_thr, uintptr_t d_dets, uintptr_t d_rects, uintptr_t d_matrices,
+           uintptr_t stream) {
+          vali_warp_fit_in in;
+          std::memset(&in, 0, sizeof(in));
+          in.kpts = P((uintptr_t)kpts[0]);
+          in.dtype = (int32_t)kpts[1];
+          in.kdim = kdim;
+          in.stride_n = kpts[2]; in.stride_k = kpts[3]; in.stride_p = kpts[4]; in.stride_c = kpts[5];
+          in.k = k; in.p = pp; in.max_det = max_det; in.min_points = min_points;
+          in.d_template = (const float*)P(d_template);
+          in.kpt_thr = kpt_thr;
+          py::gil_scoped_release nogil;
+          return vali_warp_fit((const vali_surface*)P(d_frames), n, &in, (const int32_t*)P(d_dets),
+                               (const vali_roi*)P(d_rects), (int32_t*)P(d_matrices), P(stream));
+        });
+  m.def("warp_tensor",
+        [](const std::vector<SurfaceDesc>& descs, uintptr_t d_frames, int format, uintptr_t d_matrices,
+           const TensorDst* dst, const PreprocParams* p, bool pad, const std::array<uint8_t, 3>& pad_rgb,
+           uintptr_t stream) {
+          std::vector<vali_surface> host(descs.size());
+          for (size_t i = 0; i < descs.size(); ++i)
+            host[i] = descs[i].s;
+          py::gil_scoped_release nogil;
+          return vali_warp_tensor(host.empty() ? nullptr : host.data(), (const vali_surface*)P(d_frames), (int)host.size(),
+                                  format, (const int32_t*)P(d_matrices), dst ? &dst->t : nullptr, p ? &p->p : nullptr,
+                                  pad ? 1 : 0, pad_rgb.data(), P(stream));
+        });
+
   // ---- JPEG decoder: host-side parser and sizes, then the batched decoder --------------------------------------
   py::class_<JpegInfo>(m, "JpegInfo")
       .def_property_readonly("width", [](const JpegInfo& j) { return j.f.width; })
