@@ -861,6 +861,20 @@ VALI_API int vali_pose_paint(const vali_surface* frames, const vali_surface* d_f
                              const vali_pose_style* style, int32_t* d_points, const vali_cvt_params* params,
                              void* d_ws, size_t ws_bytes, vali_stream_t stream);
 
+/* vali_pose_paint_points (TWO launches): steps 4 to 6 above for points the CALLER holds in device memory -- those of
+ * vali_kpt_decode, an earlier vali_pose_paint, or anything computed on the GPU.  d_points: n * max_det * p rows of 4 int32
+ * (X, Y, any value, flag), 16-byte aligned, read only; point j of row i * max_det + r is drawn on frame i.  A point is
+ * visible when flag & 1 and -65536 <= X < 131072 and -65536 <= Y < 131072; the other bits of flag and every other int32
+ * value are handled and draw nothing.  The first launch copies the visible points into the workspace and forms each row's
+ * box as vali_pose_paint forms it from the points it computed; the second is vali_pose_paint's.  Frames, format, d_limbs,
+ * style (its kpt_thr is not read), params, the workspace (vali_pose_workspace_size(n, max_det, p)) and the limits are
+ * vali_pose_paint's, and so are the refusals that concern them.
+ */
+VALI_API int vali_pose_paint_points(const vali_surface* frames, const vali_surface* d_frames, int n, int format,
+                                    const int32_t* d_points, int p, int max_det, const int32_t* d_limbs, int n_limbs,
+                                    const vali_pose_style* style, const vali_cvt_params* params, void* d_ws,
+                                    size_t ws_bytes, vali_stream_t stream);
+
 /* ---- aligned crops: affine views of frames, from the caller's matrices or fitted to keypoints, into a batch tensor -----
  *
  * The second stage that needs a rotated or aligned crop: a face onto the 112 x 112 ArcFace canvas by its five landmarks,
@@ -935,6 +949,75 @@ VALI_API int vali_warp_fit(const vali_surface* d_frames, int n, const vali_warp_
 VALI_API int vali_warp_tensor(const vali_surface* frames, const vali_surface* d_frames, int n, int format,
                               const int32_t* d_matrices, const vali_tensor_dst* dst, const vali_preproc_params* params,
                               int pad, const uint8_t pad_rgb[3], vali_stream_t stream);
+
+/* ---- keypoint decode: a second-stage network's heatmaps or SimCC vectors as points in frame pixels -------------------
+ *
+ * The way back from a top-down pose or landmark network (HRNet, ViTPose, RTMPose, face landmarks) that ran on the crops
+ * of vali_warp_tensor or vali_nv12_preproc_roi_tensor: slot m of its output holds one map per keypoint j, and the map's
+ * peak becomes a point of the FRAME the crop was cut from, through the row the crop was cut with.  ONE launch, nothing
+ * allocated, nothing synchronises: the call can be captured and replayed after the tensors were rewritten in place.  The
+ * reference has no such task.  Float arithmetic is IEEE float32, one rounding per operation, never a fused multiply-add;
+ * (float) of an integer is exact here.  Where a step yields a NaN, which NaN (sign, payload) is not defined.
+ * Inputs, float32, float16 or bfloat16 in device memory, aligned to their element only:
+ *   form (a)  heat (m, p, hh, wh): x stride 1, the strides of m, p and y in elements, any values >= 0 (slices, pitched
+ *             rows, a broadcast).
+ *   form (b)  simcc_x (m, p, wx) and simcc_y (m, p, wy), last stride 1, the others >= 0; wx goes in `wh`, wy in `hh`.
+ * Mapping, exactly one of: d_matrices, m rows (frame, a, b, c, d, e, f, status) as vali_warp_tensor reads them; d_rois, m
+ * = n * max_det vali_roi records as vali_detect_select writes them (source rectangle in the frame, placement on the
+ * canvas), slot i * max_det + r belonging to frame i.  canvas_w x canvas_h is the size the crops were cut to; d_frames
+ * are the n frames' descriptors, read for their sizes only.  Slot m, keypoint j:
+ *   1. skipped  matrices: frame is outside 0..n-1; rois: src_w, src_h, dst_w or dst_h is below 1.  The slot's rows of
+ *               d_points and d_kpts are all zero and no map of it is read.  Every int32 value and every float32 bit
+ *               pattern in a row is handled.
+ *   2. peak     over the map's elements in row-major order, converted to float32: the lowest index among the elements
+ *               that compare equal to the greatest non-NaN element (-0.0 equals 0.0; +-inf are ordinary values; a NaN
+ *               never wins); conf is the element at that index, xp = index % wh, yp = index / wh.  A map of NaNs only has
+ *               no peak: the points row is (0, 0, the bits 0x7fc00000, 0) and the kpts row (0, 0, NaN).  Form (b): xp is
+ *               the peak of the x vector with value vx, yp that of the y vector with vy, conf = vy < vx ? vy : vx; no
+ *               peak in either vector is no peak.
+ *   3. refine   VALI_KPT_REFINE_QUARTER, form (a) only: if 0 < xp < wh - 1, d = heat[yp][xp + 1] - heat[yp][xp - 1] and
+ *               ox = 0.25 when d > 0, -0.25 when d < 0; otherwise (a NaN, a border column) ox = 0.  oy likewise along y.
+ *               VALI_KPT_REFINE_NONE and form (b): ox = oy = 0.
+ *   4. canvas   sx = (float)canvas_w / (float)wh.  VALI_KPT_ALIGN_CENTRE: cu = (((float)xp + 0.5f) + ox) * sx;
+ *               VALI_KPT_ALIGN_INDEX: cu = (((float)xp + ox) * sx) + 0.5f (codecs that label in pixel-index coordinates).
+ *               cv likewise with canvas_h and hh.
+ *   5. frame    matrices: fx = ((a * cu) + (b * cv)) + c, fy = ((d * cu) + (e * cv)) + f (vali_warp_tensor's step 2).
+ *               rois: fx = (cu - (float)dst_x) * ((float)src_w / (float)dst_w) + (float)src_x, fy likewise
+ *               (vali_pose_paint's step 2).
+ *   6. visible  by vali_pose_paint's step 3 with (cu, cv) in the place of (kx, ky): conf > kpt_thr, -65536 <= fx < 131072
+ *               and -65536 <= fy < 131072.  d_points[m * p + j] = X, Y, the bits of conf, flag exactly as there (flag 3:
+ *               inside the W x H frame the slot belongs to); d_kpts[m * p + j] = fx, fy, conf whether visible or not.
+ * d_points: m * p rows of 4 int32, 16-byte aligned; d_kpts: NULL or m * p rows of 3 float32.  Every row of both is
+ * rewritten by every call.  Limits: n 1..1024, m 1..65535, p 1..64, hh and wh 1..4096, hh * wh <= 2^20 in form (a), the
+ * canvas 1..65535 a side, max_det 1..1024.
+ * VALI_ERR_INVALID_ARG, before any device is touched: null d_frames, in or d_points; both or neither of d_matrices and
+ * d_rois; heat together with a SimCC vector, or neither heat nor both vectors; a dtype outside the three, a tensor not
+ * aligned to its element, a stride outside 0..2^40; a limit above broken; with d_rois, m other than n * max_det; an
+ * unknown refine or align, a refinement in form (b); a NaN kpt_thr; d_frames, d_matrices, d_rois or d_kpts not 4-byte
+ * aligned, d_points not 16-byte aligned.
+ */
+#define VALI_KPT_REFINE_NONE 0
+#define VALI_KPT_REFINE_QUARTER 1
+#define VALI_KPT_ALIGN_CENTRE 0
+#define VALI_KPT_ALIGN_INDEX 1
+typedef struct vali_kpt_decode_in {
+  const void* heat;                      /* form (a): element (0, 0, 0, 0); NULL: form (b) */
+  const void* simcc_x;                   /* form (b): element (0, 0, 0) of each; NULL in form (a) */
+  const void* simcc_y;
+  int32_t dtype;                         /* VALI_DTYPE_F32, _F16 or _BF16 */
+  int32_t refine, align;
+  int32_t max_det;                       /* with d_rois */
+  int64_t stride_m, stride_p, stride_y;  /* heat, in elements, >= 0 */
+  int64_t x_stride_m, x_stride_p, y_stride_m, y_stride_p; /* the vectors */
+  int32_t m, p, hh, wh;
+  int32_t canvas_w, canvas_h;
+  float kpt_thr;
+  int32_t reserved;
+} vali_kpt_decode_in;                    /* 128 bytes */
+
+VALI_API int vali_kpt_decode(const vali_surface* d_frames, int n, const vali_kpt_decode_in* in,
+                             const int32_t* d_matrices, const vali_roi* d_rois, int32_t* d_points, float* d_kpts,
+                             vali_stream_t stream);
 
 /*
  * Rectangles of surfaces of ANY sizes as files, in one fixed set of launches.  Item i is rectangle rois[i] of the

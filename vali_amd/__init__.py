@@ -24,7 +24,8 @@ if not _BUILDING:
                         letterbox_rect, pack_colour, pack_uv, render_labels)
     from .detect import DetectionStyle, PyDetectionSelector, SelectBatch
     from .mask import MaskBatch, PyInstanceMasker
-    from .pose import COCO_SKELETON, PoseBatch, PyPoseDrawer
+    from .pose import COCO_SKELETON, PointsBatch, PoseBatch, PyPoseDrawer
+    from .keypoints import KeypointBatch, PyKeypointDecoder
     from .semantic import PySemanticPainter, SemanticBatch
     from .warp import ARCFACE_112, PySurfaceWarper, WarpBatch
     from .pipeline import BatchedFramePipeline, broadcast_coefficients, shard_frames

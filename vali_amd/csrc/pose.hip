@@ -18,6 +18,8 @@
 //                      applies them to its 16-byte pieces in registers with cover_piece, the coverage computed per
 //                      pixel in exact integers, and stores a piece only if a shape changed it.  The pieces are loaded
 //                      once a pass has a shape on the tile.
+// vali_pose_paint_points draws points the caller holds: k_pose_boxes in the place of k_pose_points, then the same
+// k_pose_paint.
 // The formats and the frame rules, the tile's pieces, the hit list and the coverage blend are tile_paint.hpp's, the rows
 // det_rows.hpp's; here are the points, the shapes and their coverage.
 #include <math.h>
@@ -393,6 +395,55 @@ __global__ void __launch_bounds__(kBlock) k_pose_paint(const PoseArgs a) {
 }
 #undef VALI_SLOTS
 
+// ---- vali_pose_paint_points' launch 1: the caller's points, sanitised into the workspace, and the box of a row ----------
+// One wave per row, lane p = point p, as k_pose_points: a point is visible when flag & 1 and -65536 <= X, Y < 131072, for
+// every int32 value; the copy k_pose_paint reads keeps X, Y and the third value of a visible point and flag 0 / 1 / 3 (3:
+// inside the frame, formed here), and is all zero for any other.  (Its own arguments: PoseArgs, and with it what
+// vali_pose_paint compiles to, stays as it is.)
+struct BoxArgs {
+  const vali_surface* d_frames;
+  const int4* src;  // n * D * P rows, the caller's
+  int4* points;     // the workspace's copy
+  int4* boxes;
+  int n, D, P;
+  int thickness, diameter;
+};
+
+__global__ void __launch_bounds__(kBlock) k_pose_boxes(const BoxArgs a) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int row = (int)blockIdx.x * kWavesPerBlock + (int)threadIdx.x / kWave;
+  if (row >= a.n * a.D)
+    return;
+  const int f = row / a.D;
+  const int W = a.d_frames[f].width, H = a.d_frames[f].height;
+  int X = 0, Y = 0, flag = 0;
+  if (lane < a.P) {
+    const int4 p = a.src[(size_t)row * (size_t)a.P + lane];
+    const int lo = -65536, hi = 131072;
+    int4 o = make_int4(0, 0, 0, 0);
+    if ((p.w & 1) && p.x >= lo && p.x < hi && p.y >= lo && p.y < hi) {
+      X = p.x, Y = p.y;
+      flag = (X >= 0 && X < W && Y >= 0 && Y < H) ? 3 : 1;
+      o = make_int4(X, Y, p.z, flag);
+    }
+    a.points[(size_t)row * (size_t)a.P + lane] = o;
+  }
+  const int big = 1 << 30;
+  const int x0 = wave_min(flag ? X : big), y0 = wave_min(flag ? Y : big);
+  const int x1 = wave_max(flag ? X : -big), y1 = wave_max(flag ? Y : -big);
+  if (lane == 0) {
+    const int g = (max(a.thickness, a.diameter) + 1) / 2;
+    int4 b = make_int4(0, 0, 0, 0);
+    if (x0 <= x1) {
+      b = make_int4(clampi((long long)x0 - g, 0, W), clampi((long long)y0 - g, 0, H), clampi((long long)x1 + g + 1, 0, W),
+                    clampi((long long)y1 + g + 1, 0, H));
+      if (b.x >= b.z || b.y >= b.w)
+        b = make_int4(0, 0, 0, 0);
+    }
+    a.boxes[row] = b;
+  }
+}
+
 bool dims_ok(int n, int D, int p) {
   return n >= 1 && n <= kMaxN && D >= 1 && D <= kMaxD && (long long)n * D <= 65535 && p >= 1 && p <= kMaxP;
 }
@@ -485,6 +536,69 @@ int vali_pose_paint(const vali_surface* frames, const vali_surface* d_frames, in
   case VALI_DTYPE_F16: hipLaunchKernelGGL(k_pose_points<VALI_DTYPE_F16>, pgrid, dim3(kBlock), 0, s, a); break;
   default: hipLaunchKernelGGL(k_pose_points<VALI_DTYPE_BF16>, pgrid, dim3(kBlock), 0, s, a); break;
   }
+  VALI_LAUNCH_CHECK();
+  const dim3 grid(tiles, n);
+  switch (fmt) {
+  case A_NV12: launch_paint<A_NV12>(grid, s, a); break;
+  case A_YUV420: launch_paint<A_YUV420>(grid, s, a); break;
+  case A_YUV444: launch_paint<A_YUV444>(grid, s, a); break;
+  case A_RGB: launch_paint<A_RGB>(grid, s, a); break;
+  case A_BGR: launch_paint<A_BGR>(grid, s, a); break;
+  default: launch_paint<A_RGBP>(grid, s, a); break;
+  }
+  VALI_LAUNCH_CHECK();
+  return VALI_OK;
+}
+
+int vali_pose_paint_points(const vali_surface* frames, const vali_surface* d_frames, int n, int format,
+                           const int32_t* d_points, int p, int max_det, const int32_t* d_limbs, int n_limbs,
+                           const vali_pose_style* style, const vali_cvt_params* params, void* d_ws, size_t ws_bytes,
+                           vali_stream_t stream) {
+  VALI_REQUIRE(frames && d_frames && d_points && style && d_ws, "null argument");
+  VALI_REQUIRE(n >= 1 && n <= kMaxN, "n outside 1..1024");
+  VALI_REQUIRE(p >= 1 && p <= kMaxP, "p outside 1..64");
+  VALI_REQUIRE(max_det >= 1 && max_det <= kMaxD, "max_det outside 1..1024");
+  VALI_REQUIRE((long long)n * max_det <= 65535, "n * max_det exceeds 65535");
+  VALI_REQUIRE(n_limbs >= 0 && n_limbs <= kMaxL, "n_limbs outside 0..128");
+  VALI_REQUIRE(d_limbs || n_limbs == 0, "limbs has a null pointer");
+  VALI_REQUIRE(style->d_limb_colours && style->d_joint_colours, "limb_colours or joint_colours has a null pointer");
+  VALI_REQUIRE(style->n_limb_colours >= 1 && style->n_joint_colours >= 1, "n_limb_colours or n_joint_colours below 1");
+  VALI_REQUIRE(style->thickness >= 1 && style->thickness <= kMaxT, "thickness outside 1..64");
+  VALI_REQUIRE(style->diameter >= 1 && style->diameter <= kMaxT, "diameter outside 1..64");
+  VALI_REQUIRE(style->alpha >= -1 && style->alpha <= 255, "alpha outside -1..255");
+  VALI_REQUIRE((((uintptr_t)style->d_limb_colours | (uintptr_t)style->d_joint_colours | (uintptr_t)d_limbs) & 3u) == 0,
+               "limbs or colours are not 4-byte aligned");
+  VALI_REQUIRE(((uintptr_t)d_points & 15u) == 0, "points is not 16-byte aligned");
+  int tiles = 0;
+  int rc = check_frames(__func__, n, frames, format, &tiles);
+  if (rc != VALI_OK)
+    return rc;
+  const int fmt = tile_format(format);
+  VALI_REQUIRE(params || !a_isyuv(fmt), "a YUV format needs params (rgb2yuv)");
+  VALI_REQUIRE(((uintptr_t)d_ws & 15u) == 0, "the workspace is not 16-byte aligned");
+  VALI_REQUIRE(ws_bytes >= vali_pose_workspace_size(n, max_det, p), "the workspace is smaller than vali_pose_workspace_size");
+
+  const size_t rows = (size_t)n * (size_t)max_det;
+  PoseArgs a = {};
+  a.d_frames = d_frames, a.limbs = d_limbs;
+  a.limb_colours = style->d_limb_colours, a.joint_colours = style->d_joint_colours;
+  a.boxes = (int4*)d_ws;
+  a.points = (int4*)d_ws + rows;
+  a.n = n, a.D = max_det, a.P = p, a.L = n_limbs;
+  a.n_limb_colours = style->n_limb_colours, a.n_joint_colours = style->n_joint_colours;
+  a.thickness = style->thickness, a.diameter = style->diameter, a.alpha = style->alpha;
+  if (a_isyuv(fmt))
+    for (int k = 0; k < 3; ++k)
+      for (int j = 0; j < 4; ++j)
+        a.m[k][j] = params->rgb2yuv[k][j];
+  BoxArgs b = {};
+  b.d_frames = d_frames, b.src = (const int4*)d_points, b.points = a.points, b.boxes = a.boxes;
+  b.n = n, b.D = max_det, b.P = p;
+  b.thickness = style->thickness, b.diameter = style->diameter;
+
+  hipStream_t s = as_stream(stream);
+  VALI_ENTRY(s);
+  hipLaunchKernelGGL(k_pose_boxes, dim3((unsigned)((rows + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, s, b);
   VALI_LAUNCH_CHECK();
   const dim3 grid(tiles, n);
   switch (fmt) {

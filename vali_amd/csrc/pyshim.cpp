@@ -837,6 +837,51 @@ PYBIND11_MODULE(_vali_shim, m) {
                                  (int32_t*)P(d_points), p ? &p->p : nullptr, P(workspace), ws_bytes, P(stream));
         });
 
+  // ... from the caller's points (d_points: n * max_det * p rows of 4 int32)
+  m.def("pose_paint_points",
+        [](const std::vector<SurfaceDesc>& descs, uintptr_t d_frames, int format, uintptr_t d_points, int pp, int max_det,
+           uintptr_t d_limbs, int n_limbs, uintptr_t d_limb_colours, int n_limb_colours, uintptr_t d_joint_colours,
+           int n_joint_colours, int thickness, int diameter, int alpha, const CvtParams* p, uintptr_t workspace,
+           size_t ws_bytes, uintptr_t stream) {
+          std::vector<vali_surface> host(descs.size());
+          for (size_t i = 0; i < descs.size(); ++i)
+            host[i] = descs[i].s;
+          vali_pose_style st;
+          std::memset(&st, 0, sizeof(st));
+          st.d_limb_colours = (const int32_t*)P(d_limb_colours);
+          st.d_joint_colours = (const int32_t*)P(d_joint_colours);
+          st.n_limb_colours = n_limb_colours; st.n_joint_colours = n_joint_colours;
+          st.thickness = thickness; st.diameter = diameter; st.alpha = alpha;
+          py::gil_scoped_release nogil;
+          return vali_pose_paint_points(host.empty() ? nullptr : host.data(), (const vali_surface*)P(d_frames),
+                                        (int)host.size(), format, (const int32_t*)P(d_points), pp, max_det,
+                                        (const int32_t*)P(d_limbs), n_limbs, &st, p ? &p->p : nullptr, P(workspace),
+                                        ws_bytes, P(stream));
+        });
+
+  // keypoint decode: heat = (ptr, stride_m, stride_p, stride_y) or all zero; simcc = (x ptr, x stride_m, x stride_p,
+  // y ptr, y stride_m, y stride_p) or all zero; dims = (m, p, hh, wh); one of d_matrices and d_rois is 0
+  m.def("kpt_decode",
+        [](uintptr_t d_frames, int n, int dtype, const std::array<int64_t, 4>& heat, const std::array<int64_t, 6>& simcc,
+           const std::array<int, 4>& dims, int canvas_w, int canvas_h, int refine, int align, float kpt_thr, int max_det,
+           uintptr_t d_matrices, uintptr_t d_rois, uintptr_t d_points, uintptr_t d_kpts, uintptr_t stream) {
+          vali_kpt_decode_in in;
+          std::memset(&in, 0, sizeof(in));
+          in.heat = P((uintptr_t)heat[0]);
+          in.stride_m = heat[1]; in.stride_p = heat[2]; in.stride_y = heat[3];
+          in.simcc_x = P((uintptr_t)simcc[0]);
+          in.x_stride_m = simcc[1]; in.x_stride_p = simcc[2];
+          in.simcc_y = P((uintptr_t)simcc[3]);
+          in.y_stride_m = simcc[4]; in.y_stride_p = simcc[5];
+          in.dtype = dtype; in.refine = refine; in.align = align; in.max_det = max_det;
+          in.m = dims[0]; in.p = dims[1]; in.hh = dims[2]; in.wh = dims[3];
+          in.canvas_w = canvas_w; in.canvas_h = canvas_h;
+          in.kpt_thr = kpt_thr;
+          py::gil_scoped_release nogil;
+          return vali_kpt_decode((const vali_surface*)P(d_frames), n, &in, (const int32_t*)P(d_matrices),
+                                 (const vali_roi*)P(d_rois), (int32_t*)P(d_points), (float*)P(d_kpts), P(stream));
+        });
+
   // aligned crops: kpts as for pose_paint; descs = the host copy of the descriptors in d_frames; everything else as in the
   // header
   m.def("warp_fit",

@@ -19,7 +19,7 @@ from .runtime import is_capturing
 from .surface import Surface
 from .tasks import (PySurfaceAnnotator, _UNSUPP_CC_PAIR, _SurfaceTask, _frames_of_one_format, _release, _rgb2yuv_params,
                     _status)
-from .tensors import HEAD_CAI, device_float, device_i32, strided_layout, upload_i32
+from .tensors import HEAD_CAI, declared_shape, device_float, device_i32, strided_layout, upload_i32
 
 MAX_FRAMES, MAX_HEAD, MAX_POINTS, MAX_LIMBS, MAX_DET, MAX_WIDTH = 1024, 1 << 20, 64, 128, 1024, 64
 
@@ -129,6 +129,63 @@ class PoseBatch:
         _release(self, ("d_frames", "d_ws", "d_rects", "d_limbs", "d_limb_colours", "d_joint_colours"))
 
 
+def points_spec(n_frames, points_shape, max_det, limbs=COCO_SKELETON):
+    """What PreparePoints checks, without a device: `points_shape` is the shape the tensor declares.  Returns (n, p, D,
+    limbs as a flat list)."""
+    if not 1 <= n_frames <= MAX_FRAMES:
+        raise ValueError(f"frames: {n_frames} surfaces; need 1..{MAX_FRAMES}")
+    if max_det is None:
+        raise ValueError("max_det is required: row i * max_det + r of points is drawn on frame i")
+    shape = tuple(int(v) for v in points_shape)
+    if len(shape) != 3 or shape[2] != 4:
+        raise ValueError(f"points: need an int32 tensor of shape (N * max_det, P, 4), got {shape}")
+    p = shape[1]
+    if not 1 <= p <= MAX_POINTS:
+        raise ValueError(f"points: P = {p} is outside 1..{MAX_POINTS}")
+    # the rules for max_det and limbs are Prepare's
+    n, _, p, _, D, flat = pose_spec(n_frames, (None, (n_frames, 1, p, 3), None), max_det, limbs)
+    if shape[0] != n * D:
+        raise ValueError(f"points: {shape[0]} rows for N * max_det = {n} * {D} = {n * D}")
+    return n, p, D, flat
+
+
+class PointsBatch:
+    """What PyPoseDrawer.RunPoints works on: the frames, the caller's points, the limb table and the workspace, checked
+    and set up once (PyPoseDrawer.PreparePoints).  Keeps the surfaces and the tensor alive."""
+
+    def __init__(self, gpu_id: int, stream: int, frames: Sequence[Surface], points, max_det=None, limbs=COCO_SKELETON):
+        frames = list(frames)
+        fmt = _frames_of_one_format("PointsBatch", frames, PySurfaceAnnotator._FORMATS, gpu_id)
+        if points is None:
+            raise ValueError("points: an int32 (N * max_det, P, 4) device tensor is required")
+        n, p, D, flat = points_spec(len(frames), declared_shape(points), max_det, limbs)
+        self.d_points, _, ph = device_i32("points", points, (n * D, p, 4), gpu_id)
+        if self.d_points % 16:
+            raise ValueError("points: the tensor must be 16-byte aligned")
+        if is_capturing(gpu_id, stream):
+            raise RuntimeError("PointsBatch: cannot be created while the stream is capturing -- PreparePoints() before "
+                               "the StreamCapture block and Keep() the batch with the capture")
+        self.gpu_id, self._stream = gpu_id, stream
+        self.n, self.p, self.D, self.L = n, p, D, len(flat) // 2
+        self.format = fmt
+        self.sizes = [(d.Width, d.Height) for d in frames]
+        self.descs = [d.desc() for d in frames]
+        self._keep = [frames, ph]
+        self._colours_keep, self._colours = {}, {}        # run_colours: the device tensors, the last host colours
+        self.d_frames = self.d_ws = self.d_limbs = self.d_limb_colours = self.d_joint_colours = 0
+        self.ws_bytes = shim.pose_workspace_size(n, D, p)
+        self.d_frames = shim.descs_upload(gpu_id, self.descs, stream)
+        self.d_ws = shim.mem_alloc(gpu_id, self.ws_bytes)
+        if flat:
+            self.d_limbs = upload_i32(gpu_id, stream, flat)
+
+    def __len__(self):
+        return self.n
+
+    def __del__(self):
+        _release(self, ("d_frames", "d_ws", "d_limbs", "d_limb_colours", "d_joint_colours"))
+
+
 class PyPoseDrawer(_SurfaceTask):
     """The keypoints of a pose network (YOLOv8-pose and its relatives) for the selector's detections: mapped to frame
     pixels, written to `points` and drawn IN PLACE as skeletons onto a batch of NV12, YUV420, YUV444, RGB, BGR or
@@ -151,6 +208,12 @@ class PyPoseDrawer(_SurfaceTask):
     uploaded when they change, or int32 device tensors, at `alpha` (None: the colour's own).  A keypoint is visible when
     its confidence is above `kpt_thr`; a limb needs both of its keypoints.  `thickness` and `diameter` are 1..64 pixels.
     `cc_ctx` picks the RGB -> YUV matrix as PySurfaceAnnotator.RunBatch does.
+
+    pb = PreparePoints(frames, points, max_det=D, limbs=COCO_SKELETON) and RunPoints(pb, limb_colours, joint_colours,
+    thickness=3, diameter=7, alpha=None, cc_ctx=None) draw points the CALLER holds -- PyKeypointDecoder's, an earlier
+    Run's, anything computed on the GPU -- as Run draws its own (vali_pose_paint_points, two launches): `points` is a
+    contiguous, 16-byte aligned (N * max_det, P, 4) int32 GPU tensor, read only; point j of row i * max_det + r is drawn
+    on frame i when its flag has bit 0 set and -65536 <= X, Y < 131072.  Every other int32 value draws nothing.
     """
 
     def Prepare(self, frames: Sequence[Surface], kpts, dets, max_det=100, limbs=COCO_SKELETON, points=None) -> PoseBatch:
@@ -175,5 +238,29 @@ class PyPoseDrawer(_SurfaceTask):
     def Run(self, pb: PoseBatch, rects, limb_colours, joint_colours, kpt_thr=0.5, thickness=3, diameter=7, alpha=None,
             cc_ctx=None) -> Tuple[bool, TaskExecInfo]:
         r = self.RunAsync(pb, rects, limb_colours, joint_colours, kpt_thr, thickness, diameter, alpha, cc_ctx)
+        self._sync()
+        return r
+
+    def PreparePoints(self, frames: Sequence[Surface], points, max_det=None, limbs=COCO_SKELETON) -> PointsBatch:
+        return PointsBatch(self._gpu_id, self._stream, frames, points, max_det, limbs)
+
+    def RunPointsAsync(self, pb: PointsBatch, limb_colours, joint_colours, thickness=3, diameter=7, alpha=None,
+                       cc_ctx=None) -> Tuple[bool, TaskExecInfo]:
+        if not isinstance(pb, PointsBatch):
+            raise ValueError("RunPoints: pass a PointsBatch (PreparePoints)")
+        lhost, jhost, _, t, dia, a = draw_spec(limb_colours, joint_colours, 0.0, thickness, diameter, alpha)
+        supported, params = _rgb2yuv_params(pb.format, cc_ctx)
+        if not supported:
+            return _UNSUPP_CC_PAIR
+        dlc, nlc = run_colours("PyPoseDrawer", pb, "limb_colours", limb_colours, lhost, self._gpu_id, self._stream)
+        djc, njc = run_colours("PyPoseDrawer", pb, "joint_colours", joint_colours, jhost, self._gpu_id, self._stream)
+        d = _status(shim.pose_paint_points(pb.descs, pb.d_frames, int(pb.format), pb.d_points, pb.p, pb.D, pb.d_limbs,
+                                           pb.L, dlc, nlc, djc, njc, t, dia, a, params, pb.d_ws, pb.ws_bytes,
+                                           self._stream))
+        return d.success, d.info
+
+    def RunPoints(self, pb: PointsBatch, limb_colours, joint_colours, thickness=3, diameter=7, alpha=None,
+                  cc_ctx=None) -> Tuple[bool, TaskExecInfo]:
+        r = self.RunPointsAsync(pb, limb_colours, joint_colours, thickness, diameter, alpha, cc_ctx)
         self._sync()
         return r
