@@ -124,21 +124,13 @@ def test_cubic_identity_integer_factors_and_float64_model():
         assert np.array_equal(o.resize_plane(src, 2, 33, 48, "cubic"), o.resize_plane(src, 2, 33, 48, "linear"))
     flat = np.full((20, 30), 177, np.uint8)
     assert np.array_equal(o.resize_plane(flat, 1, 77, 41, "cubic"), np.full((41, 77), 177, np.uint8))
-    # separable float64 model on the same grid with clamped indices
+    # separable float64 model on the same grid with clamped indices (tests/filter_model.py; every element type, channel
+    # count and geometry: tests/test_filter_model_host.py)
+    import filter_model
+
     src = rng.random((23, 31), dtype=np.float32)
     dw, dh = 50, 37
-
-    def taps(n_dst, n_src):
-        f = np.arange(n_dst, dtype=np.float32) * (np.float32(n_src) / np.float32(n_dst))
-        i = np.floor(f).astype(int)
-        a = (f - np.floor(f)).astype(np.float64)
-        idx = np.clip(i[:, None] + np.arange(-1, 3)[None, :], 0, n_src - 1)
-        return idx, _keys(a[:, None] - np.arange(-1, 3)[None, :])
-
-    ix, wx = taps(dw, 31)
-    iy, wy = taps(dh, 23)
-    hor = (src.astype(np.float64)[:, ix] * wx[None]).sum(-1)          # (23, dw)
-    model = (hor[iy] * wy[:, :, None]).sum(1)                          # (dh, dw)
+    model, _ = filter_model.resize(src, 1, dw, dh, "cubic")
     assert np.abs(o.resize_plane(src, 1, dw, dh, "cubic") - model).max() < 2e-6
 
 
