@@ -1,12 +1,56 @@
-"""What the tasks fed by detections (PyDetectionSelector, PyInstanceMasker, PyPoseDrawer) share at Run time: `rects`,
-colours and `alpha`, each as a device tensor or as host values."""
+"""The argument rules the tasks fed by a network's head share, each stated once.  At Prepare time: the number of frames,
+`max_det` and `net_size`; at Run time: `kpt_thr`, and `rects`, colours and `alpha`, each as a device tensor or as host
+values."""
 from __future__ import annotations
 
+import math
 import operator
 
 from ._native import shim
 from .runtime import is_capturing
 from .tensors import device_i32, is_device, upload_i32
+
+MAX_FRAMES, MAX_NET = 1024, 65535
+
+
+def batch_size(n, who=None):
+    """the N of the head tensor `who`, or the number of frames: 1..MAX_FRAMES"""
+    if not 1 <= n <= MAX_FRAMES:
+        raise ValueError(f"{who}: N = {n} is outside 1..{MAX_FRAMES}" if who else
+                         f"frames: {n} surfaces; need 1..{MAX_FRAMES}")
+
+
+def max_det_arg(max_det, n, most, most_text=None, cap=65535, slots=None):
+    """`max_det` as an integer D in 1..most (`most_text`: how the message names that bound) with N * D <= cap (None: no
+    cap).  `slots` = (who, M, what they are): the tensor `who` has one slot per detection, M = N * D."""
+    D = operator.index(max_det)
+    if not 1 <= D <= most:
+        raise ValueError(f"max_det = {D} is outside 1..{most_text or most}")
+    if cap is not None and n * D > cap:
+        raise ValueError(f"N * max_det = {n * D} exceeds {cap}")
+    if slots is not None:
+        who, m, what = slots
+        if m != n * D:
+            raise ValueError(f"{who}: M = {m} slots for N * max_det = {n} * {D} = {n * D}{what}")
+    return D
+
+
+def net_size_arg(net_size):
+    """(width, height) of the network's input, each 1..MAX_NET"""
+    try:
+        net_w, net_h = (operator.index(v) for v in net_size)
+    except (TypeError, ValueError):
+        raise ValueError("net_size: two integers (width, height) of the network's input") from None
+    if not (1 <= net_w <= MAX_NET and 1 <= net_h <= MAX_NET):
+        raise ValueError(f"net_size = ({net_w}, {net_h}) is outside 1..{MAX_NET}")
+    return net_w, net_h
+
+
+def kpt_thr_arg(kpt_thr):
+    thr = float(kpt_thr)
+    if math.isnan(thr):
+        raise ValueError("kpt_thr must not be a NaN")
+    return thr
 
 
 def device_rects(rects, n, gpu_id):

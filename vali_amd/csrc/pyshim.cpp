@@ -65,6 +65,44 @@ struct JpegInfo {
   vali_jpeg_info f;
 };
 
+// the host copy of a list of descriptors, as the C ABI takes it
+std::vector<vali_surface> host_surfaces(const std::vector<SurfaceDesc>& descs) {
+  std::vector<vali_surface> host(descs.size());
+  for (size_t i = 0; i < descs.size(); ++i)
+    host[i] = descs[i].s;
+  return host;
+}
+
+// (ptr, dtype, stride_n, stride_k, stride_c) -> vali_detect_tensor
+vali_detect_tensor detect_tensor(const std::array<int64_t, 5>& t) {
+  vali_detect_tensor d;
+  std::memset(&d, 0, sizeof(d));
+  d.data = P((uintptr_t)t[0]);
+  d.dtype = (int32_t)t[1];
+  d.stride_n = t[2]; d.stride_k = t[3]; d.stride_c = t[4];
+  return d;
+}
+
+// (ptr, dtype, stride_n, stride_m, stride_y) -> vali_mask_tensor
+vali_mask_tensor mask_tensor(const std::array<int64_t, 5>& t) {
+  vali_mask_tensor d;
+  std::memset(&d, 0, sizeof(d));
+  d.data = P((uintptr_t)t[0]);
+  d.dtype = (int32_t)t[1];
+  d.stride_n = t[2]; d.stride_m = t[3]; d.stride_y = t[4];
+  return d;
+}
+
+// (ptr, dtype, stride_n, stride_k, stride_p, stride_c) and kdim into vali_pose_in / vali_warp_fit_in, which spell the
+// keypoint tensor's fields alike
+template <class In>
+void fill_kpts(In& in, const std::array<int64_t, 6>& kpts, int kdim) {
+  in.kpts = P((uintptr_t)kpts[0]);
+  in.dtype = (int32_t)kpts[1];
+  in.kdim = kdim;
+  in.stride_n = kpts[2]; in.stride_k = kpts[3]; in.stride_p = kpts[4]; in.stride_c = kpts[5];
+}
+
 vali_roi to_roi(const std::array<int32_t, 8>& v) {
   vali_roi r;
   r.src_x = v[0]; r.src_y = v[1]; r.src_w = v[2]; r.src_h = v[3];
@@ -398,9 +436,7 @@ PYBIND11_MODULE(_vali_shim, m) {
   m.def("descs_upload", [](int device, const std::vector<SurfaceDesc>& descs, uintptr_t stream) {
     if (descs.empty())
       throw py::value_error("descs_upload: empty list");
-    std::vector<vali_surface> host(descs.size());
-    for (size_t i = 0; i < descs.size(); ++i)
-      host[i] = descs[i].s;
+    const std::vector<vali_surface> host = host_surfaces(descs);
     const size_t bytes = host.size() * sizeof(vali_surface);
     void* d = nullptr;
     check(vali_mem_alloc(device, bytes, &d), "vali_mem_alloc");
@@ -685,9 +721,7 @@ PYBIND11_MODULE(_vali_shim, m) {
 
   // marks on frames: descs = the host copy of the descriptors in d_frames; d_marks = device rows of 8 int32
   m.def("annotate_workspace_size", [](const std::vector<SurfaceDesc>& descs) {
-    std::vector<vali_surface> host(descs.size());
-    for (size_t i = 0; i < descs.size(); ++i)
-      host[i] = descs[i].s;
+    const std::vector<vali_surface> host = host_surfaces(descs);
     size_t bytes = 0;
     check(vali_annotate_workspace_size((int)host.size(), host.data(), &bytes), "vali_annotate_workspace_size");
     return bytes;
@@ -695,9 +729,7 @@ PYBIND11_MODULE(_vali_shim, m) {
   m.def("annotate_batch",
         [](const std::vector<SurfaceDesc>& descs, uintptr_t d_frames, int format, uintptr_t d_marks, int m,
            const CvtParams* p, uintptr_t workspace, size_t ws_bytes, uintptr_t stream, const SurfaceDesc* atlas) {
-          std::vector<vali_surface> host(descs.size());
-          for (size_t i = 0; i < descs.size(); ++i)
-            host[i] = descs[i].s;
+          const std::vector<vali_surface> host = host_surfaces(descs);
           py::gil_scoped_release nogil;
           return vali_annotate_batch_atlas(host.data(), (const vali_surface*)P(d_frames), (int)host.size(), format,
                                            (const vali_mark*)P(d_marks), m, atlas ? &atlas->s : nullptr,
@@ -720,16 +752,8 @@ PYBIND11_MODULE(_vali_shim, m) {
            uintptr_t colours, uintptr_t label_rects, uintptr_t workspace, size_t ws_bytes, uintptr_t stream) {
           vali_detect_in in;
           std::memset(&in, 0, sizeof(in));
-          const auto tensor = [](const std::array<int64_t, 5>& t) {
-            vali_detect_tensor d;
-            std::memset(&d, 0, sizeof(d));
-            d.data = P((uintptr_t)t[0]);
-            d.dtype = (int32_t)t[1];
-            d.stride_n = t[2]; d.stride_k = t[3]; d.stride_c = t[4];
-            return d;
-          };
-          in.boxes = tensor(boxes);
-          in.scores = tensor(scores);
+          in.boxes = detect_tensor(boxes);
+          in.scores = detect_tensor(scores);
           in.n = n; in.k = k; in.c = c;
           vali_detect_params p;
           std::memset(&p, 0, sizeof(p));
@@ -758,17 +782,11 @@ PYBIND11_MODULE(_vali_shim, m) {
            const std::array<int64_t, 5>& coeffs, int mm, int hp, int wp, int k, int max_det, int net_w, int net_h,
            uintptr_t d_dets, uintptr_t d_rects, uintptr_t d_colours, int n_colours, int alpha, const CvtParams* p,
            uintptr_t workspace, size_t ws_bytes, uintptr_t stream) {
-          std::vector<vali_surface> host(descs.size());
-          for (size_t i = 0; i < descs.size(); ++i)
-            host[i] = descs[i].s;
+          const std::vector<vali_surface> host = host_surfaces(descs);
           vali_mask_in in;
           std::memset(&in, 0, sizeof(in));
-          in.protos.data = P((uintptr_t)protos[0]);
-          in.protos.dtype = (int32_t)protos[1];
-          in.protos.stride_n = protos[2]; in.protos.stride_m = protos[3]; in.protos.stride_y = protos[4];
-          in.coeffs.data = P((uintptr_t)coeffs[0]);
-          in.coeffs.dtype = (int32_t)coeffs[1];
-          in.coeffs.stride_n = coeffs[2]; in.coeffs.stride_k = coeffs[3]; in.coeffs.stride_c = coeffs[4];
+          in.protos = mask_tensor(protos);
+          in.coeffs = detect_tensor(coeffs);
           in.m = mm; in.hp = hp; in.wp = wp; in.k = k;
           in.max_det = max_det; in.net_w = net_w; in.net_h = net_h;
           py::gil_scoped_release nogil;
@@ -784,18 +802,12 @@ PYBIND11_MODULE(_vali_shim, m) {
         [](const std::vector<SurfaceDesc>& descs, uintptr_t d_frames, int format, const std::array<int64_t, 5>& logits,
            int c, int hs, int ws, int net_w, int net_h, uintptr_t d_rects, const std::vector<SurfaceDesc>& labels,
            uintptr_t d_labels, uintptr_t d_colours, int n_colours, int alpha, const CvtParams* p, uintptr_t stream) {
-          std::vector<vali_surface> host(descs.size()), lab(labels.size());
-          for (size_t i = 0; i < descs.size(); ++i)
-            host[i] = descs[i].s;
-          for (size_t i = 0; i < labels.size(); ++i)
-            lab[i] = labels[i].s;
+          const std::vector<vali_surface> host = host_surfaces(descs), lab = host_surfaces(labels);
           if (!lab.empty() && lab.size() != host.size())
             throw py::value_error("semantic_paint: as many label descriptors as frames, or none");
           vali_semantic_in in;
           std::memset(&in, 0, sizeof(in));
-          in.logits.data = P((uintptr_t)logits[0]);
-          in.logits.dtype = (int32_t)logits[1];
-          in.logits.stride_n = logits[2]; in.logits.stride_m = logits[3]; in.logits.stride_y = logits[4];
+          in.logits = mask_tensor(logits);
           in.c = c; in.hs = hs; in.ws = ws; in.net_w = net_w; in.net_h = net_h;
           py::gil_scoped_release nogil;
           return vali_semantic_paint(host.empty() ? nullptr : host.data(), (const vali_surface*)P(d_frames),
@@ -813,15 +825,10 @@ PYBIND11_MODULE(_vali_shim, m) {
            uintptr_t d_limb_colours, int n_limb_colours, uintptr_t d_joint_colours, int n_joint_colours, float kpt_thr,
            int thickness, int diameter, int alpha, uintptr_t d_points, const CvtParams* p, uintptr_t workspace,
            size_t ws_bytes, uintptr_t stream) {
-          std::vector<vali_surface> host(descs.size());
-          for (size_t i = 0; i < descs.size(); ++i)
-            host[i] = descs[i].s;
+          const std::vector<vali_surface> host = host_surfaces(descs);
           vali_pose_in in;
           std::memset(&in, 0, sizeof(in));
-          in.kpts = P((uintptr_t)kpts[0]);
-          in.dtype = (int32_t)kpts[1];
-          in.kdim = kdim;
-          in.stride_n = kpts[2]; in.stride_k = kpts[3]; in.stride_p = kpts[4]; in.stride_c = kpts[5];
+          fill_kpts(in, kpts, kdim);
           in.k = k; in.p = pp; in.max_det = max_det; in.n_limbs = n_limbs;
           in.d_limbs = (const int32_t*)P(d_limbs);
           vali_pose_style st;
@@ -843,9 +850,7 @@ PYBIND11_MODULE(_vali_shim, m) {
            uintptr_t d_limbs, int n_limbs, uintptr_t d_limb_colours, int n_limb_colours, uintptr_t d_joint_colours,
            int n_joint_colours, int thickness, int diameter, int alpha, const CvtParams* p, uintptr_t workspace,
            size_t ws_bytes, uintptr_t stream) {
-          std::vector<vali_surface> host(descs.size());
-          for (size_t i = 0; i < descs.size(); ++i)
-            host[i] = descs[i].s;
+          const std::vector<vali_surface> host = host_surfaces(descs);
           vali_pose_style st;
           std::memset(&st, 0, sizeof(st));
           st.d_limb_colours = (const int32_t*)P(d_limb_colours);
@@ -890,10 +895,7 @@ PYBIND11_MODULE(_vali_shim, m) {
            uintptr_t stream) {
           vali_warp_fit_in in;
           std::memset(&in, 0, sizeof(in));
-          in.kpts = P((uintptr_t)kpts[0]);
-          in.dtype = (int32_t)kpts[1];
-          in.kdim = kdim;
-          in.stride_n = kpts[2]; in.stride_k = kpts[3]; in.stride_p = kpts[4]; in.stride_c = kpts[5];
+          fill_kpts(in, kpts, kdim);
           in.k = k; in.p = pp; in.max_det = max_det; in.min_points = min_points;
           in.d_template = (const float*)P(d_template);
           in.kpt_thr = kpt_thr;
@@ -905,9 +907,7 @@ PYBIND11_MODULE(_vali_shim, m) {
         [](const std::vector<SurfaceDesc>& descs, uintptr_t d_frames, int format, uintptr_t d_matrices,
            const TensorDst* dst, const PreprocParams* p, bool pad, const std::array<uint8_t, 3>& pad_rgb,
            uintptr_t stream) {
-          std::vector<vali_surface> host(descs.size());
-          for (size_t i = 0; i < descs.size(); ++i)
-            host[i] = descs[i].s;
+          const std::vector<vali_surface> host = host_surfaces(descs);
           py::gil_scoped_release nogil;
           return vali_warp_tensor(host.empty() ? nullptr : host.data(), (const vali_surface*)P(d_frames), (int)host.size(),
                                   format, (const int32_t*)P(d_matrices), dst ? &dst->t : nullptr, p ? &p->p : nullptr,

@@ -11,14 +11,15 @@ import operator
 from functools import partial
 from typing import Optional, Tuple
 
+from ._batch import PreparedBatch
 from ._native import shim
-from ._runargs import host_rects as _host_rects, run_rects
+from ._runargs import batch_size, host_rects as _host_rects, max_det_arg, run_rects
 from .enums import TaskExecInfo
 from .runtime import is_capturing
-from .tasks import MAX_MARKS, _SurfaceTask, _release, _status, pack_colour
+from .tasks import MAX_MARKS, _SurfaceTask, _status, pack_colour
 from .tensors import HEAD_CAI, declared_shape, device_float, device_i32, is_device, strided_layout, upload_i32
 
-MAX_FRAMES, MAX_HEAD, MAX_CLASSES, MAX_CANDIDATES = 1024, 1 << 20, 4096, 1024
+MAX_HEAD, MAX_CLASSES, MAX_CANDIDATES = 1 << 20, 4096, 1024
 
 _FORMATS = {"xyxy": 0, "cxcywh": 1}
 
@@ -30,8 +31,7 @@ def head_layout(who, shape, strides, code, bits, last=None):
         n, k, c = shape
         if last is not None and c != last:
             raise ValueError(f"{who}: the last dimension must be {last}, got {shape}")
-        if not 1 <= n <= MAX_FRAMES:
-            raise ValueError(f"{who}: N = {n} is outside 1..{MAX_FRAMES}")
+        batch_size(n, who)
         if not 1 <= k <= MAX_HEAD:
             raise ValueError(f"{who}: K = {k} is outside 1..2^20")
         if not 1 <= c <= MAX_CLASSES:
@@ -121,10 +121,7 @@ def select_spec(boxes_view, scores_view, box_format="xyxy", max_candidates=1024,
     T, D = operator.index(max_candidates), operator.index(max_det)
     if not 1 <= T <= MAX_CANDIDATES:
         raise ValueError(f"max_candidates = {T} is outside 1..{MAX_CANDIDATES}")
-    if not 1 <= D <= T:
-        raise ValueError(f"max_det = {D} is outside 1..max_candidates ({T})")
-    if n * D > 65535:
-        raise ValueError(f"N * max_det = {n * D} exceeds 65535")
+    max_det_arg(D, n, T, f"max_candidates ({T})")
     R = 0
     if rows[1]:
         m = rows[2]
@@ -159,9 +156,11 @@ def run_spec(R, has_rois, score_thr, iou_thr, crop_placement, style):
     return score_thr, iou_thr, crop
 
 
-class SelectBatch:
+class SelectBatch(PreparedBatch):
     """What PyDetectionSelector.Run works on: the head's two tensors, the output tensors and the workspace, checked and
     set up once (PyDetectionSelector.Prepare).  Keeps the tensors alive."""
+
+    _owned = ("d_ws", "d_rects")
 
     def __init__(self, gpu_id: int, stream: int, boxes, scores, dets, counts=None, rois=None, marks=None,
                  box_format="xyxy", max_candidates=1024, max_det=100):
@@ -183,26 +182,15 @@ class SelectBatch:
                 ptr, _, h = device_i32(name, t, shape, gpu_id)
                 setattr(self, "d_" + name, ptr)
                 keep.append(h)
-        if is_capturing(gpu_id, stream):
-            raise RuntimeError("SelectBatch: cannot be created while the stream is capturing -- Prepare() before the "
-                               "StreamCapture block and Keep() the batch with the capture")
-        self.gpu_id, self._stream = gpu_id, stream
+        self._begin(gpu_id, stream, "Prepare()", rects=n)
         self.n, self.k, self.c, self.T, self.D, self.R = n, k, c, T, D, R
         self.box_format = fmt
         self.boxes = (bseen.ptr, bcode, *bstr)
         self.scores = (sseen.ptr, scode, *sstr)
         self._keep = keep
-        self._rects_keep = self._style_keep = None
-        self.d_ws = self.d_rects = 0
+        self._style_keep = None
         self.ws_bytes = shim.detect_workspace_size(n, k, T)
         self.d_ws = shim.mem_alloc(gpu_id, self.ws_bytes)
-        self.d_rects = shim.mem_alloc(gpu_id, 32 * n)
-
-    def __len__(self):
-        return self.n
-
-    def __del__(self):
-        _release(self, ("d_ws", "d_rects"))
 
 
 class PyDetectionSelector(_SurfaceTask):

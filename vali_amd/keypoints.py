@@ -9,16 +9,16 @@ tests/kpt_decode_model.py restates it in numpy.
 """
 from __future__ import annotations
 
-import math
 import operator
 from typing import Sequence, Tuple
 
+from ._batch import PreparedBatch, surfaces_on_device
 from ._native import shim
+from ._runargs import batch_size, kpt_thr_arg, max_det_arg
 from .enums import TaskExecInfo
-from .pose import MAX_DET, MAX_FRAMES, MAX_POINTS
-from .runtime import is_capturing
+from .pose import MAX_DET, MAX_POINTS
 from .surface import Surface
-from .tasks import _SurfaceTask, _release, _status
+from .tasks import _SurfaceTask, _status
 from .tensors import HEAD_CAI, device_float, device_i32, strided_layout
 
 MAX_SLOTS, MAX_SIDE, MAX_ELEMS, MAX_CANVAS = 65535, 4096, 1 << 20, 65535
@@ -75,8 +75,7 @@ def simcc_pair(xview, yview):
 def mapping_spec(n_frames, m, canvas, matrices, rois, max_det):
     """What Prepare checks of the mapping, without a device; `matrices` and `rois` are the tensors or None.  Returns
     (canvas w, canvas h, D or 0)."""
-    if not 1 <= n_frames <= MAX_FRAMES:
-        raise ValueError(f"frames: {n_frames} surfaces; need 1..{MAX_FRAMES}")
+    batch_size(n_frames)
     try:
         w, h = (operator.index(v) for v in canvas)
     except (TypeError, ValueError):
@@ -91,19 +90,13 @@ def mapping_spec(n_frames, m, canvas, matrices, rois, max_det):
         return w, h, 0
     if max_det is None:
         raise ValueError("rois: max_det is required (slot i * max_det + r belongs to frame i)")
-    D = operator.index(max_det)
-    if not 1 <= D <= MAX_DET:
-        raise ValueError(f"max_det = {D} is outside 1..{MAX_DET}")
-    if m != n_frames * D:
-        raise ValueError(f"rois: M = {m} slots for N * max_det = {n_frames} * {D} = {n_frames * D}")
-    return w, h, D
+    # (no cap on N * max_det: M, which it must equal, has its own in the layouts)
+    return w, h, max_det_arg(max_det, n_frames, MAX_DET, cap=None, slots=("rois", m, ""))
 
 
 def run_spec(kpt_thr, refine, align, simcc):
     """What Run checks of its arguments: (kpt_thr, refine code, align code)"""
-    thr = float(kpt_thr)
-    if math.isnan(thr):
-        raise ValueError("kpt_thr must not be a NaN")
+    thr = kpt_thr_arg(kpt_thr)
     if refine not in REFINES:
         raise ValueError(f"refine = {refine!r}; one of {', '.join(repr(v) for v in REFINES)}")
     if align not in ALIGNS:
@@ -113,19 +106,16 @@ def run_spec(kpt_thr, refine, align, simcc):
     return thr, REFINES[refine], ALIGNS[align]
 
 
-class KeypointBatch:
+class KeypointBatch(PreparedBatch):
     """What PyKeypointDecoder.Run works on: the frames, the maps, the mapping rows and the outputs, checked and set up
     once (PrepareHeatmaps / PrepareSimcc).  Keeps the surfaces and tensors alive."""
+
+    _owned = ("d_frames",)
 
     def __init__(self, gpu_id: int, stream: int, frames: Sequence[Surface], heat, simcc, points, canvas, matrices, rois,
                  max_det, kpts):
         frames = list(frames)
-        for i, d in enumerate(frames):
-            if d is None or d.IsEmpty:
-                raise ValueError(f"frames: surface {i} is empty")
-            dev = getattr(d, "DeviceId", gpu_id)
-            if dev != gpu_id:
-                raise ValueError(f"frames: surface {i} is on device {dev}, the task on {gpu_id}")
+        surfaces_on_device("frames", frames, gpu_id)
         self.simcc = heat is None
         self.heat, self.vectors, keep = (0, 0, 0, 0), (0, 0, 0, 0, 0, 0), []
         if self.simcc:
@@ -162,21 +152,12 @@ class KeypointBatch:
                 return None
             ks, _ = device_float("kpts", kpts, kpts_layout, gpu_id, ("<f4",))
             self.d_kpts, kh = ks.ptr, ks.holder
-        if is_capturing(gpu_id, stream):
-            raise RuntimeError("KeypointBatch: cannot be created while the stream is capturing -- Prepare before the "
-                               "StreamCapture block and Keep() the batch with the capture")
-        self.gpu_id, self._stream = gpu_id, stream
+        self._begin(gpu_id, stream, "Prepare", frames)
         self.n, self.m, self.p, self.hh, self.wh, self.canvas = len(frames), m, p, hh, wh, (w, h)
-        self.descs = [d.desc() for d in frames]
         self._keep = [frames, keep, mh, ph, kh]
-        self.d_frames = 0
-        self.d_frames = shim.descs_upload(gpu_id, self.descs, stream)
 
     def __len__(self):
         return self.m
-
-    def __del__(self):
-        _release(self, ("d_frames",))
 
 
 class PyKeypointDecoder(_SurfaceTask):

@@ -8,19 +8,17 @@ in numpy.
 """
 from __future__ import annotations
 
-import operator
 from typing import Sequence, Tuple
 
+from ._batch import PAINT_FORMATS, PreparedBatch, frames_of_one_format
 from ._native import shim
-from ._runargs import alpha_arg, host_colours, run_colours, run_rects
+from ._runargs import alpha_arg, batch_size, host_colours, max_det_arg, net_size_arg, run_colours, run_rects
 from .enums import TaskExecInfo
-from .runtime import is_capturing
 from .surface import Surface
-from .tasks import (PySurfaceAnnotator, _UNSUPP_CC_PAIR, _SurfaceTask, _frames_of_one_format, _release, _rgb2yuv_params,
-                    _status)
+from .tasks import _UNSUPP_CC_PAIR, _SurfaceTask, _rgb2yuv_params, _status
 from .tensors import HEAD_CAI, device_float, device_i32, strided_layout
 
-MAX_FRAMES, MAX_PROTOS, MAX_SIDE, MAX_HEAD, MAX_DET, MAX_NET = 1024, 64, 1024, 1 << 20, 1024, 65535
+MAX_PROTOS, MAX_SIDE, MAX_HEAD, MAX_DET = 64, 1024, 1 << 20, 1024
 
 
 def protos_layout(shape, strides, code, bits):
@@ -28,8 +26,7 @@ def protos_layout(shape, strides, code, bits):
     strides); ValueError, naming what is wrong, otherwise."""
     code, shape, strides = strided_layout("protos", ("N", "M", "Hp", "Wp"), shape, strides, code, bits)
     n, m, hp, wp = shape
-    if not 1 <= n <= MAX_FRAMES:
-        raise ValueError(f"protos: N = {n} is outside 1..{MAX_FRAMES}")
+    batch_size(n, "protos")
     if not 1 <= m <= MAX_PROTOS:
         raise ValueError(f"protos: M = {m} is outside 1..{MAX_PROTOS}")
     if not (1 <= hp <= MAX_SIDE and 1 <= wp <= MAX_SIDE):
@@ -43,8 +40,7 @@ def coeffs_layout(shape, strides, code, bits):
     """The rules for `coeffs`, without a device: (N, K, M) with any element strides >= 0"""
     code, shape, strides = strided_layout("coeffs", ("N", "K", "M"), shape, strides, code, bits)
     n, k, m = shape
-    if not 1 <= n <= MAX_FRAMES:
-        raise ValueError(f"coeffs: N = {n} is outside 1..{MAX_FRAMES}")
+    batch_size(n, "coeffs")
     if not 1 <= k <= MAX_HEAD:
         raise ValueError(f"coeffs: K = {k} is outside 1..2^20")
     if not 1 <= m <= MAX_PROTOS:
@@ -60,18 +56,8 @@ def mask_spec(n_frames, protos_view, coeffs_view, max_det=100, net_size=(640, 64
         raise ValueError(f"protos and coeffs disagree: protos are ({n}, {m}, {hp}, {wp}), coeffs ({n2}, {k}, {m2})")
     if n_frames != n:
         raise ValueError(f"frames: {n_frames} surfaces for tensors of N = {n}")
-    D = operator.index(max_det)
-    if not 1 <= D <= MAX_DET:
-        raise ValueError(f"max_det = {D} is outside 1..{MAX_DET}")
-    if n * D > 65535:
-        raise ValueError(f"N * max_det = {n * D} exceeds 65535")
-    try:
-        net_w, net_h = (operator.index(v) for v in net_size)
-    except (TypeError, ValueError):
-        raise ValueError("net_size: two integers (width, height) of the network's input") from None
-    if not (1 <= net_w <= MAX_NET and 1 <= net_h <= MAX_NET):
-        raise ValueError(f"net_size = ({net_w}, {net_h}) is outside 1..{MAX_NET}")
-    return n, m, hp, wp, k, D, net_w, net_h
+    D = max_det_arg(max_det, n, MAX_DET)
+    return (n, m, hp, wp, k, D) + net_size_arg(net_size)
 
 
 def paint_spec(colours, alpha):
@@ -80,14 +66,16 @@ def paint_spec(colours, alpha):
     return host_colours("colours", colours), a
 
 
-class MaskBatch:
+class MaskBatch(PreparedBatch):
     """What PyInstanceMasker.Run works on: the frames, the head's two tensors, the selector's dets and the workspace,
     checked and set up once (PyInstanceMasker.Prepare).  Keeps the surfaces and tensors alive."""
+
+    _owned = ("d_frames", "d_ws", "d_rects", "d_colours")
 
     def __init__(self, gpu_id: int, stream: int, frames: Sequence[Surface], protos, coeffs, dets, max_det=100,
                  net_size=(640, 640)):
         frames = list(frames)
-        fmt = _frames_of_one_format("MaskBatch", frames, PySurfaceAnnotator._FORMATS, gpu_id)
+        fmt = frames_of_one_format("MaskBatch", frames, PAINT_FORMATS, gpu_id)
         pseen, (pcode, pshape, pstr) = device_float("protos", protos, protos_layout, gpu_id, *HEAD_CAI)
         cseen, (ccode, cshape, cstr) = device_float("coeffs", coeffs, coeffs_layout, gpu_id, *HEAD_CAI)
         n, m, hp, wp, k, D, net_w, net_h = mask_spec(len(frames), (pcode, pshape, pstr), (ccode, cshape, cstr), max_det,
@@ -95,31 +83,15 @@ class MaskBatch:
         if dets is None:
             raise ValueError(f"dets: an int32 ({n * D}, 8) device tensor is required")
         self.d_dets, _, dh = device_i32("dets", dets, (n * D, 8), gpu_id)
-        if is_capturing(gpu_id, stream):
-            raise RuntimeError("MaskBatch: cannot be created while the stream is capturing -- Prepare() before the "
-                               "StreamCapture block and Keep() the batch with the capture")
-        self.gpu_id, self._stream = gpu_id, stream
+        self._begin(gpu_id, stream, "Prepare()", frames, rects=n, colours=True)
         self.n, self.m, self.hp, self.wp, self.k, self.D = n, m, hp, wp, k, D
         self.net_w, self.net_h = net_w, net_h
         self.format = fmt
-        self.sizes = [(d.Width, d.Height) for d in frames]
-        self.descs = [d.desc() for d in frames]
         self.protos = (pseen.ptr, pcode, pstr[0], pstr[1], pstr[2])
         self.coeffs = (cseen.ptr, ccode, *cstr)
         self._keep = [frames, pseen.holder, cseen.holder, dh]
-        self._rects_keep = None
-        self._colours_keep, self._colours = {}, {}        # run_colours: the device tensor, the last host colours
-        self.d_frames = self.d_ws = self.d_rects = self.d_colours = 0
         self.ws_bytes = shim.mask_workspace_size(n, D, hp, wp)
-        self.d_frames = shim.descs_upload(gpu_id, self.descs, stream)
         self.d_ws = shim.mem_alloc(gpu_id, self.ws_bytes)
-        self.d_rects = shim.mem_alloc(gpu_id, 32 * n)
-
-    def __len__(self):
-        return self.n
-
-    def __del__(self):
-        _release(self, ("d_frames", "d_ws", "d_rects", "d_colours"))
 
 
 class PyInstanceMasker(_SurfaceTask):

@@ -8,20 +8,18 @@ tests/pose_model.py restates it in numpy.
 """
 from __future__ import annotations
 
-import math
 import operator
 from typing import Sequence, Tuple
 
+from ._batch import PAINT_FORMATS, PreparedBatch, frames_of_one_format
 from ._native import shim
-from ._runargs import alpha_arg, host_colours, run_colours, run_rects
+from ._runargs import alpha_arg, batch_size, host_colours, kpt_thr_arg, max_det_arg, run_colours, run_rects
 from .enums import TaskExecInfo
-from .runtime import is_capturing
 from .surface import Surface
-from .tasks import (PySurfaceAnnotator, _UNSUPP_CC_PAIR, _SurfaceTask, _frames_of_one_format, _release, _rgb2yuv_params,
-                    _status)
+from .tasks import _UNSUPP_CC_PAIR, _SurfaceTask, _rgb2yuv_params, _status
 from .tensors import HEAD_CAI, declared_shape, device_float, device_i32, strided_layout, upload_i32
 
-MAX_FRAMES, MAX_HEAD, MAX_POINTS, MAX_LIMBS, MAX_DET, MAX_WIDTH = 1024, 1 << 20, 64, 128, 1024, 64
+MAX_HEAD, MAX_POINTS, MAX_LIMBS, MAX_DET, MAX_WIDTH = 1 << 20, 64, 128, 1024, 64
 
 # the 19 limbs of the 17 COCO keypoints, 0-based
 COCO_SKELETON = ((15, 13), (13, 11), (16, 14), (14, 12), (11, 12), (5, 11), (6, 12), (5, 6), (5, 7), (6, 8), (7, 9),
@@ -33,8 +31,7 @@ def kpts_layout(shape, strides, code, bits):
     (dtype code, shape, strides); ValueError, naming what is wrong, otherwise."""
     code, shape, strides = strided_layout("kpts", ("N", "K", "P", "3 or 2"), shape, strides, code, bits)
     n, k, p, c = shape
-    if not 1 <= n <= MAX_FRAMES:
-        raise ValueError(f"kpts: N = {n} is outside 1..{MAX_FRAMES}")
+    batch_size(n, "kpts")
     if not 1 <= k <= MAX_HEAD:
         raise ValueError(f"kpts: K = {k} is outside 1..2^20")
     if not 1 <= p <= MAX_POINTS:
@@ -50,11 +47,7 @@ def pose_spec(n_frames, kpts_view, max_det=100, limbs=COCO_SKELETON):
     _, (n, k, p, kdim), _ = kpts_view
     if n_frames != n:
         raise ValueError(f"frames: {n_frames} surfaces for a tensor of N = {n}")
-    D = operator.index(max_det)
-    if not 1 <= D <= MAX_DET:
-        raise ValueError(f"max_det = {D} is outside 1..{MAX_DET}")
-    if n * D > 65535:
-        raise ValueError(f"N * max_det = {n * D} exceeds 65535")
+    D = max_det_arg(max_det, n, MAX_DET)
     try:
         pairs = [tuple(operator.index(v) for v in pair) for pair in limbs]
     except TypeError:
@@ -72,9 +65,7 @@ def pose_spec(n_frames, kpts_view, max_det=100, limbs=COCO_SKELETON):
 def draw_spec(limb_colours, joint_colours, kpt_thr, thickness, diameter, alpha):
     """What Run checks of its host arguments: (host limb colours or None for a device tensor, host joint colours or None,
     kpt_thr, thickness, diameter, alpha as the C ABI takes it)"""
-    thr = float(kpt_thr)
-    if math.isnan(thr):
-        raise ValueError("kpt_thr must not be a NaN")
+    thr = kpt_thr_arg(kpt_thr)
     t, d = operator.index(thickness), operator.index(diameter)
     if not 1 <= t <= MAX_WIDTH:
         raise ValueError(f"thickness = {t} is outside 1..{MAX_WIDTH}")
@@ -84,14 +75,16 @@ def draw_spec(limb_colours, joint_colours, kpt_thr, thickness, diameter, alpha):
     return host_colours("limb_colours", limb_colours), host_colours("joint_colours", joint_colours), thr, t, d, a
 
 
-class PoseBatch:
+class PoseBatch(PreparedBatch):
     """What PyPoseDrawer.Run works on: the frames, the head's keypoints, the selector's dets, the limb table, the points
     and the workspace, checked and set up once (PyPoseDrawer.Prepare).  Keeps the surfaces and tensors alive."""
+
+    _owned = ("d_frames", "d_ws", "d_rects", "d_limbs", "d_limb_colours", "d_joint_colours")
 
     def __init__(self, gpu_id: int, stream: int, frames: Sequence[Surface], kpts, dets, max_det=100, limbs=COCO_SKELETON,
                  points=None):
         frames = list(frames)
-        fmt = _frames_of_one_format("PoseBatch", frames, PySurfaceAnnotator._FORMATS, gpu_id)
+        fmt = frames_of_one_format("PoseBatch", frames, PAINT_FORMATS, gpu_id)
         kseen, (kcode, kshape, kstr) = device_float("kpts", kpts, kpts_layout, gpu_id, *HEAD_CAI)
         n, k, p, kdim, D, flat = pose_spec(len(frames), (kcode, kshape, kstr), max_det, limbs)
         if dets is None:
@@ -102,38 +95,21 @@ class PoseBatch:
             self.d_points, _, ph = device_i32("points", points, (n * D, p, 4), gpu_id)
             if self.d_points % 16:
                 raise ValueError("points: the tensor must be 16-byte aligned")
-        if is_capturing(gpu_id, stream):
-            raise RuntimeError("PoseBatch: cannot be created while the stream is capturing -- Prepare() before the "
-                               "StreamCapture block and Keep() the batch with the capture")
-        self.gpu_id, self._stream = gpu_id, stream
+        self._begin(gpu_id, stream, "Prepare()", frames, rects=n, colours=True)
         self.n, self.k, self.p, self.kdim, self.D, self.L = n, k, p, kdim, D, len(flat) // 2
         self.format = fmt
-        self.sizes = [(d.Width, d.Height) for d in frames]
-        self.descs = [d.desc() for d in frames]
         self.kpts = (kseen.ptr, kcode, *kstr)
         self._keep = [frames, kseen.holder, dh, ph]
-        self._rects_keep = None
-        self._colours_keep, self._colours = {}, {}        # run_colours: the device tensors, the last host colours
-        self.d_frames = self.d_ws = self.d_rects = self.d_limbs = self.d_limb_colours = self.d_joint_colours = 0
         self.ws_bytes = shim.pose_workspace_size(n, D, p)
-        self.d_frames = shim.descs_upload(gpu_id, self.descs, stream)
         self.d_ws = shim.mem_alloc(gpu_id, self.ws_bytes)
-        self.d_rects = shim.mem_alloc(gpu_id, 32 * n)
         if flat:
             self.d_limbs = upload_i32(gpu_id, stream, flat)
-
-    def __len__(self):
-        return self.n
-
-    def __del__(self):
-        _release(self, ("d_frames", "d_ws", "d_rects", "d_limbs", "d_limb_colours", "d_joint_colours"))
 
 
 def points_spec(n_frames, points_shape, max_det, limbs=COCO_SKELETON):
     """What PreparePoints checks, without a device: `points_shape` is the shape the tensor declares.  Returns (n, p, D,
     limbs as a flat list)."""
-    if not 1 <= n_frames <= MAX_FRAMES:
-        raise ValueError(f"frames: {n_frames} surfaces; need 1..{MAX_FRAMES}")
+    batch_size(n_frames)
     if max_det is None:
         raise ValueError("max_det is required: row i * max_det + r of points is drawn on frame i")
     shape = tuple(int(v) for v in points_shape)
@@ -149,41 +125,29 @@ def points_spec(n_frames, points_shape, max_det, limbs=COCO_SKELETON):
     return n, p, D, flat
 
 
-class PointsBatch:
+class PointsBatch(PreparedBatch):
     """What PyPoseDrawer.RunPoints works on: the frames, the caller's points, the limb table and the workspace, checked
     and set up once (PyPoseDrawer.PreparePoints).  Keeps the surfaces and the tensor alive."""
 
+    _owned = ("d_frames", "d_ws", "d_limbs", "d_limb_colours", "d_joint_colours")
+
     def __init__(self, gpu_id: int, stream: int, frames: Sequence[Surface], points, max_det=None, limbs=COCO_SKELETON):
         frames = list(frames)
-        fmt = _frames_of_one_format("PointsBatch", frames, PySurfaceAnnotator._FORMATS, gpu_id)
+        fmt = frames_of_one_format("PointsBatch", frames, PAINT_FORMATS, gpu_id)
         if points is None:
             raise ValueError("points: an int32 (N * max_det, P, 4) device tensor is required")
         n, p, D, flat = points_spec(len(frames), declared_shape(points), max_det, limbs)
         self.d_points, _, ph = device_i32("points", points, (n * D, p, 4), gpu_id)
         if self.d_points % 16:
             raise ValueError("points: the tensor must be 16-byte aligned")
-        if is_capturing(gpu_id, stream):
-            raise RuntimeError("PointsBatch: cannot be created while the stream is capturing -- PreparePoints() before "
-                               "the StreamCapture block and Keep() the batch with the capture")
-        self.gpu_id, self._stream = gpu_id, stream
+        self._begin(gpu_id, stream, "PreparePoints()", frames, colours=True)
         self.n, self.p, self.D, self.L = n, p, D, len(flat) // 2
         self.format = fmt
-        self.sizes = [(d.Width, d.Height) for d in frames]
-        self.descs = [d.desc() for d in frames]
         self._keep = [frames, ph]
-        self._colours_keep, self._colours = {}, {}        # run_colours: the device tensors, the last host colours
-        self.d_frames = self.d_ws = self.d_limbs = self.d_limb_colours = self.d_joint_colours = 0
         self.ws_bytes = shim.pose_workspace_size(n, D, p)
-        self.d_frames = shim.descs_upload(gpu_id, self.descs, stream)
         self.d_ws = shim.mem_alloc(gpu_id, self.ws_bytes)
         if flat:
             self.d_limbs = upload_i32(gpu_id, stream, flat)
-
-    def __len__(self):
-        return self.n
-
-    def __del__(self):
-        _release(self, ("d_frames", "d_ws", "d_limbs", "d_limb_colours", "d_joint_colours"))
 
 
 class PyPoseDrawer(_SurfaceTask):

@@ -8,19 +8,17 @@ restates it in numpy.
 """
 from __future__ import annotations
 
-import operator
 from typing import Optional, Sequence, Tuple
 
+from ._batch import PAINT_FORMATS, PreparedBatch, frames_of_one_format, surfaces_on_device
 from ._native import shim
-from ._runargs import alpha_arg, host_colours, run_colours, run_rects
+from ._runargs import alpha_arg, batch_size, host_colours, net_size_arg, run_colours, run_rects
 from .enums import PixelFormat, TaskExecInfo
-from .runtime import is_capturing
 from .surface import Surface
-from .tasks import (PySurfaceAnnotator, _UNSUPP_CC_PAIR, _SurfaceTask, _frames_of_one_format, _release, _rgb2yuv_params,
-                    _status)
+from .tasks import _UNSUPP_CC_PAIR, _SurfaceTask, _rgb2yuv_params, _status
 from .tensors import HEAD_CAI, device_float, strided_layout
 
-MAX_FRAMES, MAX_CLASSES, MAX_SIDE, MAX_NET = 1024, 255, 4096, 65535
+MAX_CLASSES, MAX_SIDE = 255, 4096
 
 
 def logits_layout(shape, strides, code, bits):
@@ -28,8 +26,7 @@ def logits_layout(shape, strides, code, bits):
     strides); ValueError, naming what is wrong, otherwise."""
     code, shape, strides = strided_layout("logits", ("N", "C", "Hs", "Ws"), shape, strides, code, bits)
     n, c, hs, ws = shape
-    if not 1 <= n <= MAX_FRAMES:
-        raise ValueError(f"logits: N = {n} is outside 1..{MAX_FRAMES}")
+    batch_size(n, "logits")
     if not 1 <= c <= MAX_CLASSES:
         raise ValueError(f"logits: C = {c} is outside 1..{MAX_CLASSES}")
     if not (1 <= hs <= MAX_SIDE and 1 <= ws <= MAX_SIDE):
@@ -46,12 +43,7 @@ def semantic_spec(frame_sizes, logits_view, label_views=None, net_size=(512, 512
     _, (n, c, hs, ws), _ = logits_view
     if len(frame_sizes) != n:
         raise ValueError(f"frames: {len(frame_sizes)} surfaces for logits of N = {n}")
-    try:
-        net_w, net_h = (operator.index(v) for v in net_size)
-    except (TypeError, ValueError):
-        raise ValueError("net_size: two integers (width, height) of the network's input") from None
-    if not (1 <= net_w <= MAX_NET and 1 <= net_h <= MAX_NET):
-        raise ValueError(f"net_size = ({net_w}, {net_h}) is outside 1..{MAX_NET}")
+    net_w, net_h = net_size_arg(net_size)
     if label_views is not None:
         if len(label_views) != n:
             raise ValueError(f"labels: {len(label_views)} surfaces for {n} frames")
@@ -74,52 +66,32 @@ def paint_spec(colours, alpha, has_labels):
     return host_colours("colours", colours), a
 
 
-class SemanticBatch:
+class SemanticBatch(PreparedBatch):
     """What PySemanticPainter.Run works on: the frames, the logits and the label surfaces, checked and set up once
     (PySemanticPainter.Prepare).  Keeps the surfaces and the tensor alive."""
 
+    _owned = ("d_frames", "d_labels", "d_rects", "d_colours")
+
     def __init__(self, gpu_id: int, stream: int, frames: Sequence[Surface], logits, labels=None, net_size=(512, 512)):
         frames = list(frames)
-        fmt = _frames_of_one_format("SemanticBatch", frames, PySurfaceAnnotator._FORMATS, gpu_id)
+        fmt = frames_of_one_format("SemanticBatch", frames, PAINT_FORMATS, gpu_id)
         seen, view = device_float("logits", logits, logits_layout, gpu_id, *HEAD_CAI)
         label_views = None
         if labels is not None:
             labels = list(labels)
-            for i, s in enumerate(labels):
-                if s is None or s.IsEmpty:
-                    raise ValueError(f"labels: surface {i} is empty")
-                dev = getattr(s, "DeviceId", gpu_id)
-                if dev != gpu_id:
-                    raise ValueError(f"labels: surface {i} is on device {dev}, the task on {gpu_id}")
+            surfaces_on_device("labels", labels, gpu_id)
             label_views = [(s.Format, s.Width, s.Height) for s in labels]
-        sizes = [(d.Width, d.Height) for d in frames]
-        n, c, hs, ws, net_w, net_h = semantic_spec(sizes, view, label_views, net_size)
-        if is_capturing(gpu_id, stream):
-            raise RuntimeError("SemanticBatch: cannot be created while the stream is capturing -- Prepare() before the "
-                               "StreamCapture block and Keep() the batch with the capture")
+        n, c, hs, ws, net_w, net_h = semantic_spec([(d.Width, d.Height) for d in frames], view, label_views, net_size)
+        self._begin(gpu_id, stream, "Prepare()", frames, rects=n, colours=True)
         code, _, strides = view
-        self.gpu_id, self._stream = gpu_id, stream
         self.n, self.c, self.hs, self.ws = n, c, hs, ws
         self.net_w, self.net_h = net_w, net_h
         self.format = fmt
-        self.sizes = sizes
-        self.descs = [d.desc() for d in frames]
         self.label_descs = [s.desc() for s in labels] if labels is not None else []
         self.logits = (seen.ptr, code, strides[0], strides[1], strides[2])
         self._keep = [frames, labels, seen.holder]
-        self._rects_keep = None
-        self._colours_keep, self._colours = {}, {}        # run_colours: the device tensor, the last host colours
-        self.d_frames = self.d_labels = self.d_rects = self.d_colours = 0
-        self.d_frames = shim.descs_upload(gpu_id, self.descs, stream)
         if self.label_descs:
             self.d_labels = shim.descs_upload(gpu_id, self.label_descs, stream)
-        self.d_rects = shim.mem_alloc(gpu_id, 32 * n)
-
-    def __len__(self):
-        return self.n
-
-    def __del__(self):
-        _release(self, ("d_frames", "d_labels", "d_rects", "d_colours"))
 
 
 class PySemanticPainter(_SurfaceTask):

@@ -10,6 +10,7 @@ from __future__ import annotations
 import operator
 from typing import List, Optional, Sequence, Tuple
 
+from ._batch import PAINT_FORMATS, PreparedBatch, frames_of_one_format
 from ._native import shim
 from ._runargs import device_rects
 from .enums import (ColorRange, ColorSpace, ColorspaceConversionContext, Interpolation, PixelFormat, TaskExecDetails,
@@ -431,50 +432,10 @@ class PySurfaceConverter(_SurfaceTask):
         return r
 
 
-def _release(batch, names):
-    """The teardown of a prepared batch (its __del__): free the device arrays it names, after the batch's stream."""
-    if any(getattr(batch, name, 0) for name in names):
-        try:    # a launch issued on the batch's stream may still be using the arrays
-            shim.stream_sync(batch.gpu_id, batch._stream)
-        except Exception:
-            pass
-    for name in names:
-        p = getattr(batch, name, 0)
-        if p:
-            try:
-                shim.mem_free(batch.gpu_id, p)
-            except Exception:
-                pass
-            setattr(batch, name, 0)
-
-
-def _frames_of_one_format(who, frames, formats, gpu_id, also=None):
-    """The rules for the surfaces a batch writes to: none empty, one of `formats` and the same for all, 4:2:0 ones of even
-    size, all on `gpu_id`.  `also(i, surface)`: the caller's own check, made once the surface's format is known.
-    Returns the format (None for no surfaces)."""
-    fmt = None
-    for i, d in enumerate(frames):
-        if d is None or d.IsEmpty:
-            raise ValueError(f"{who}: surface {i} is empty")
-        if d.Format not in formats:
-            raise ValueError(f"{who}: surface {i} has format {d.Format!r}; supported: "
-                             f"{', '.join(f.name for f in formats)}")
-        if fmt is not None and d.Format != fmt:
-            raise ValueError(f"{who}: surface {i} has format {d.Format!r}, surface 0 {fmt!r}: one format per batch")
-        fmt = d.Format
-        if also is not None:
-            also(i, d)
-        if fmt in (F.NV12, F.YUV420) and (d.Width | d.Height) & 1:
-            raise ValueError(f"{who}: surface {i}: {fmt.name} is 4:2:0 and needs an even width and height, "
-                             f"got {d.Width}x{d.Height}")
-        dev = getattr(d, "DeviceId", gpu_id)
-        if dev != gpu_id:
-            raise ValueError(f"{who}: surface {i} is on device {dev}, the task on {gpu_id}")
-    return fmt
-
-
-class SurfaceBatch:
+class SurfaceBatch(PreparedBatch):
     """Device-resident descriptor arrays for n (src, dst) surface pairs of one geometry."""
+
+    _owned = ("d_src", "d_dst")
 
     def __init__(self, gpu_id: int, stream: int, srcs: Sequence[Surface], dsts: Sequence[Surface]):
         srcs, dsts = list(srcs), list(dsts)
@@ -485,13 +446,7 @@ class SurfaceBatch:
             for s in group:
                 if s.Format != f0 or (s.Width, s.Height) != s0 or s.IsEmpty:
                     raise ValueError("SurfaceBatch: surfaces of a batch must share format and size")
-        if is_capturing(gpu_id, stream):
-            # the upload allocates and synchronises: both are illegal while the stream records a graph, and the
-            # recorded launches would keep reading arrays that die with this object
-            raise RuntimeError("SurfaceBatch: cannot be created while the stream is capturing -- PrepareBatch() "
-                               "before the StreamCapture block and Keep() the batch with the capture")
-        self.gpu_id = gpu_id
-        self._stream = stream
+        self._begin(gpu_id, stream, "PrepareBatch()")
         self.n = len(srcs)
         self.src_format, self.dst_format = srcs[0].Format, dsts[0].Format
         self.src_size = (srcs[0].Width, srcs[0].Height)
@@ -500,12 +455,6 @@ class SurfaceBatch:
         self.src_components, self.src_planes = srcs[0].NumComponents, srcs[0].NumPlanes
         self.d_src = shim.descs_upload(gpu_id, [s.desc() for s in srcs], stream)
         self.d_dst = shim.descs_upload(gpu_id, [s.desc() for s in dsts], stream)
-
-    def __len__(self):
-        return self.n
-
-    def __del__(self):
-        _release(self, ("d_src", "d_dst"))
 
 
 # ---- PySurfaceUD -------------------------------------------------------------------------
@@ -952,10 +901,12 @@ def _pad_colour(pad):
     return True, rgb
 
 
-class RoiBatch:
+class RoiBatch(PreparedBatch):
     """Device-resident arrays for n region items: source descriptors (one format, any sizes, repeats allowed),
     destination descriptors (one format and size) and rectangle records, uploaded once
     (PySurfacePreprocessor.PrepareRoiBatch)."""
+
+    _owned = ("d_src", "d_dst", "d_roi")
 
     def __init__(self, gpu_id: int, stream: int, srcs: Sequence[Surface], dsts: Sequence[Surface], src_rects=None,
                  dst_rects=None):
@@ -963,11 +914,7 @@ class RoiBatch:
         self.src_format, self.rects = _roi_batch_records(srcs, dsts, src_rects, dst_rects)
         n = len(srcs)
         f0, s0 = dsts[0].Format, (dsts[0].Width, dsts[0].Height)
-        if is_capturing(gpu_id, stream):
-            raise RuntimeError("RoiBatch: cannot be created while the stream is capturing -- PrepareRoiBatch() "
-                               "before the StreamCapture block and Keep() the batch with the capture")
-        self.gpu_id = gpu_id
-        self._stream = stream
+        self._begin(gpu_id, stream, "PrepareRoiBatch()")
         self.n = n
         self.src_formats = tuple(s.Format for s in srcs)
         self.dst_format, self.dst_size = f0, s0
@@ -975,12 +922,6 @@ class RoiBatch:
         self.d_src = shim.descs_upload(gpu_id, [s.desc() for s in srcs], stream)
         self.d_dst = shim.descs_upload(gpu_id, [d.desc() for d in dsts], stream)
         self.d_roi = shim.rois_upload(gpu_id, self.rects, stream)
-
-    def __len__(self):
-        return self.n
-
-    def __del__(self):
-        _release(self, ("d_src", "d_dst", "d_roi"))
 
 
 # DLPack dtype (code, bits) -> (name, enum vali_dtype) of a destination tensor, and of one the JPEG encoder reads: uint8 too
@@ -1079,10 +1020,12 @@ class _Canvas:
         self.Format, self.Width, self.Height = F.RGB_32F_PLANAR, w, h
 
 
-class TensorBatch:
+class TensorBatch(PreparedBatch):
     """Device-resident arrays for n region items that land in ONE batch tensor: source descriptors (one format, any
     sizes, repeats allowed) and rectangle records, uploaded once (PySurfacePreprocessor.PrepareTensorBatch).  Keeps the
     sources and the tensor alive."""
+
+    _owned = ("d_src", "d_roi")
 
     def __init__(self, gpu_id: int, stream: int, srcs: Sequence[Surface], out, src_rects=None, dst_rects=None):
         srcs = list(srcs)
@@ -1091,23 +1034,13 @@ class TensorBatch:
             raise ValueError(f"TensorBatch: {len(srcs)} sources for a tensor of {n} items")
         canvas = _Canvas(w, h)
         self.src_format, self.rects = _roi_batch_records(srcs, [canvas] * n, src_rects, dst_rects)
-        if is_capturing(gpu_id, stream):
-            raise RuntimeError("TensorBatch: cannot be created while the stream is capturing -- PrepareTensorBatch() "
-                               "before the StreamCapture block and Keep() the batch with the capture")
-        self.gpu_id = gpu_id
-        self._stream = stream
+        self._begin(gpu_id, stream, "PrepareTensorBatch()")
         self.n = n
         self.dst_size = (w, h)
         self.out = out
         self._keep = (srcs, out, holder)
         self.d_src = shim.descs_upload(gpu_id, [s.desc() for s in srcs], stream)
         self.d_roi = shim.rois_upload(gpu_id, self.rects, stream)
-
-    def __len__(self):
-        return self.n
-
-    def __del__(self):
-        _release(self, ("d_src", "d_roi"))
 
 
 # ---- PySurfaceRotator --------------------------------------------------------------------
@@ -1134,9 +1067,11 @@ RGB2YUV_BT709_JPEG = _bt709_rgb2yuv(False)
 RGB2YUV_BT709_MPEG = _bt709_rgb2yuv(True)
 
 
-class FrameBatch:
+class FrameBatch(PreparedBatch):
     """One (N, 3, H, W) tensor and the N surfaces it is written into: the destination descriptors uploaded once
     (PySurfacePostprocessor.PrepareTensorBatch).  Keeps the tensor and the surfaces alive."""
+
+    _owned = ("d_dst",)
 
     def __init__(self, gpu_id: int, stream: int, tensor, dsts: Sequence[Surface]):
         self.src, self.layout, self.dtype, (n, h, w), _, holder = _tensor_src(tensor, gpu_id)
@@ -1149,24 +1084,14 @@ class FrameBatch:
                 raise ValueError(f"FrameBatch: surface {i} is {d.Width}x{d.Height}, the tensor's items are {w}x{h}: "
                                  "the sizes must be equal (no resizing on the way out)")
 
-        fmt = _frames_of_one_format("FrameBatch", dsts, PySurfacePostprocessor._DST, gpu_id, same_size)
-        if is_capturing(gpu_id, stream):
-            raise RuntimeError("FrameBatch: cannot be created while the stream is capturing -- PrepareTensorBatch() "
-                               "before the StreamCapture block and Keep() the batch with the capture")
-        self.gpu_id = gpu_id
-        self._stream = stream
+        fmt = frames_of_one_format("FrameBatch", dsts, PySurfacePostprocessor._DST, gpu_id, same_size)
+        self._begin(gpu_id, stream, "PrepareTensorBatch()")
         self.n = n
         self.size = (w, h)
         self.dst_format = fmt
         self.tensor = tensor
         self._keep = (tensor, holder, dsts)
         self.d_dst = shim.descs_upload(gpu_id, [d.desc() for d in dsts], stream)
-
-    def __len__(self):
-        return self.n
-
-    def __del__(self):
-        _release(self, ("d_dst",))
 
 
 class PySurfacePostprocessor(_SurfaceTask):
@@ -1327,38 +1252,26 @@ def _atlas_size(atlas, gpu_id):
     return atlas.Width, atlas.Height
 
 
-class AnnotateBatch:
+class AnnotateBatch(PreparedBatch):
     """The frames PySurfaceAnnotator.RunBatch draws on: N >= 0 surfaces of one format, any sizes; descriptors, the
     kernel's workspace and a staging buffer for host-side marks are set up once (PySurfaceAnnotator.PrepareBatch).
     Keeps the surfaces alive."""
 
+    _owned = ("d_frames", "d_ws", "d_marks")
+
     def __init__(self, gpu_id: int, stream: int, frames: Sequence[Surface]):
         frames = list(frames)
-        fmt = _frames_of_one_format("AnnotateBatch", frames, PySurfaceAnnotator._FORMATS, gpu_id)
-        if frames and is_capturing(gpu_id, stream):
-            raise RuntimeError("AnnotateBatch: cannot be created while the stream is capturing -- PrepareBatch() "
-                               "before the StreamCapture block and Keep() the batch with the capture")
-        self.gpu_id = gpu_id
-        self._stream = stream
+        fmt = frames_of_one_format("AnnotateBatch", frames, PAINT_FORMATS, gpu_id)
+        self._begin(gpu_id, stream, "PrepareBatch()" if frames else None, frames)     # no frames: nothing is allocated
         self.n = len(frames)
         self.format = fmt
-        self.sizes = [(d.Width, d.Height) for d in frames]
-        self.descs = [d.desc() for d in frames]
         self._keep = frames
         self._marks_keep = None
-        self.d_frames = self.d_ws = self.d_marks = 0
         self.ws_bytes = 0
         if frames:
             self.ws_bytes = shim.annotate_workspace_size(self.descs)
-            self.d_frames = shim.descs_upload(gpu_id, self.descs, stream)
             self.d_ws = shim.mem_alloc(gpu_id, self.ws_bytes)
             self.d_marks = shim.mem_alloc(gpu_id, MAX_MARKS * 32)
-
-    def __len__(self):
-        return self.n
-
-    def __del__(self):
-        _release(self, ("d_frames", "d_ws", "d_marks"))
 
 
 class PySurfaceAnnotator(_SurfaceTask):
@@ -1384,11 +1297,11 @@ class PySurfaceAnnotator(_SurfaceTask):
     unsupported one gives (False, UNSUPPORTED_FMT_CONV_PARAMS) and nothing is launched.  Ignored for RGB formats.
     """
 
-    _FORMATS = (F.NV12, F.YUV420, F.YUV444, F.RGB, F.BGR, F.RGB_PLANAR)
+    _FORMATS = PAINT_FORMATS
 
     @staticmethod
     def SupportedFormats() -> List[PixelFormat]:
-        return list(PySurfaceAnnotator._FORMATS)
+        return list(PAINT_FORMATS)
 
     def PrepareBatch(self, frames: Sequence[Surface]) -> AnnotateBatch:
         return AnnotateBatch(self._gpu_id, self._stream, frames)

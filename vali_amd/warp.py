@@ -15,13 +15,13 @@ import math
 import operator
 from typing import Sequence, Tuple
 
+from ._batch import PreparedBatch, surfaces_on_device
 from ._native import shim
-from ._runargs import run_rects
+from ._runargs import batch_size, kpt_thr_arg, max_det_arg, run_rects
 from .enums import PixelFormat, TaskExecInfo
-from .pose import MAX_DET, MAX_FRAMES, kpts_layout
-from .runtime import is_capturing
+from .pose import MAX_DET, kpts_layout
 from .surface import Surface
-from .tasks import (_UNSUPP_CC_PAIR, _SurfaceTask, _csc, _nv12_variant, _pad_colour, _release, _status, _tensor_dst)
+from .tasks import _UNSUPP_CC_PAIR, _SurfaceTask, _csc, _nv12_variant, _pad_colour, _status, _tensor_dst
 from .tensors import HEAD_CAI, device_float, device_i32
 
 F = PixelFormat
@@ -39,8 +39,7 @@ def frames_spec(frames):
     """The rules for the frames, without a device: `frames` is a sequence of (format, width, height).  Returns the
     format."""
     frames = list(frames)
-    if not 1 <= len(frames) <= MAX_FRAMES:
-        raise ValueError(f"frames: {len(frames)} surfaces; need 1..{MAX_FRAMES}")
+    batch_size(len(frames))
     fmt = frames[0][0]
     for i, (f, w, h) in enumerate(frames):
         if f not in FORMATS:
@@ -68,13 +67,7 @@ def keypoints_spec(n_frames, kpts_view, m_out, max_det, template):
     _, (n, k, p, kdim), _ = kpts_view
     if n_frames != n:
         raise ValueError(f"frames: {n_frames} surfaces for a tensor of N = {n}")
-    D = operator.index(max_det)
-    if not 1 <= D <= MAX_DET:
-        raise ValueError(f"max_det = {D} is outside 1..{MAX_DET}")
-    if n * D > MAX_SLOTS:
-        raise ValueError(f"N * max_det = {n * D} exceeds {MAX_SLOTS}")
-    if m_out != n * D:
-        raise ValueError(f"out: M = {m_out} slots for N * max_det = {n} * {D} = {n * D} detections")
+    D = max_det_arg(max_det, n, MAX_DET, cap=MAX_SLOTS, slots=("out", m_out, " detections"))
     try:
         pairs = [tuple(float(v) for v in pair) for pair in template]
     except TypeError:
@@ -92,35 +85,28 @@ def keypoints_spec(n_frames, kpts_view, m_out, max_det, template):
 
 def fit_spec(kpt_thr, min_points, p):
     """What Run checks of form (b)'s host arguments: (kpt_thr, min_points)"""
-    thr = float(kpt_thr)
-    if math.isnan(thr):
-        raise ValueError("kpt_thr must not be a NaN")
+    thr = kpt_thr_arg(kpt_thr)
     mp = operator.index(min_points)
     if not 2 <= mp <= p:
         raise ValueError(f"min_points = {mp} is outside 2..{p} (P = {p})")
     return thr, mp
 
 
-class WarpBatch:
+class WarpBatch(PreparedBatch):
     """What PySurfaceWarper.Run works on: the frames, the tensor, the matrices and -- form (b) -- the keypoints, the
     detections and the template, checked and set up once (PrepareMatrices / PrepareKeypoints).  Keeps the surfaces and
     tensors alive."""
 
+    _owned = ("d_frames", "d_ws", "d_rects", "d_template")     # d_matrices is the caller's, or d_ws under a second name
+
     def __init__(self, gpu_id: int, stream: int, frames: Sequence[Surface], out, matrices=None, kpts=None, dets=None,
                  max_det=None, template=None):
         frames = list(frames)
-        for i, d in enumerate(frames):
-            if d is None or d.IsEmpty:
-                raise ValueError(f"frames: surface {i} is empty")
-            dev = getattr(d, "DeviceId", gpu_id)
-            if dev != gpu_id:
-                raise ValueError(f"frames: surface {i} is on device {dev}, the task on {gpu_id}")
+        surfaces_on_device("frames", frames, gpu_id)
         self.format = frames_spec([(d.Format, d.Width, d.Height) for d in frames])
         self.dst, self.layout, self.dtype, (m, h, w), oh = _tensor_dst(out, gpu_id)
         self.fitted = kpts is not None
         self.d_matrices, mh, kh, dh = 0, None, None, None
-        self.d_frames = self.d_ws = self.d_rects = self.d_template = 0
-        self.gpu_id, self._stream = gpu_id, stream
         if self.fitted:
             kseen, (kcode, kshape, kstr) = device_float("kpts", kpts, kpts_layout, gpu_id, *HEAD_CAI)
             n, self.k, self.p, self.kdim, self.D, flat = keypoints_spec(len(frames), (kcode, kshape, kstr), m, max_det,
@@ -137,18 +123,11 @@ class WarpBatch:
             self.d_matrices, _, mh = device_i32("matrices", matrices, (m, 8), gpu_id)
             if self.d_matrices % 16:
                 raise ValueError("matrices: the tensor must be 16-byte aligned")
-        if is_capturing(gpu_id, stream):
-            raise RuntimeError("WarpBatch: cannot be created while the stream is capturing -- Prepare before the "
-                               "StreamCapture block and Keep() the batch with the capture")
+        self._begin(gpu_id, stream, "Prepare", frames, rects=len(frames) if self.fitted else 0)
         self.n, self.m, self.size = len(frames), m, (w, h)
-        self.sizes = [(d.Width, d.Height) for d in frames]
-        self.descs = [d.desc() for d in frames]
         self.out = out
         self._keep = [frames, out, oh, mh, kh, dh]
-        self._rects_keep = None
-        self.d_frames = shim.descs_upload(gpu_id, self.descs, stream)
         if self.fitted:
-            self.d_rects = shim.mem_alloc(gpu_id, 32 * self.n)
             buf = array.array("f", flat)
             self.d_template = shim.mem_alloc(gpu_id, 4 * len(buf))
             shim.memcpy2d_async(gpu_id, self.d_template, 4 * len(buf), buf.buffer_info()[0], 4 * len(buf), 4 * len(buf), 1,
@@ -160,9 +139,6 @@ class WarpBatch:
 
     def __len__(self):
         return self.m
-
-    def __del__(self):
-        _release(self, ("d_frames", "d_ws", "d_rects", "d_template"))
 
 
 class PySurfaceWarper(_SurfaceTask):
