@@ -519,14 +519,7 @@ int vali_annotate_batch_atlas(const vali_surface* frames, const vali_surface* d_
                      (uint8_t*)workspace);
   VALI_LAUNCH_CHECK();
   const dim3 grid(tiles, n);
-  switch (fmt) {
-  case A_NV12: launch_tiles<A_NV12>(grid, s, a, t); break;
-  case A_YUV420: launch_tiles<A_YUV420>(grid, s, a, t); break;
-  case A_YUV444: launch_tiles<A_YUV444>(grid, s, a, t); break;
-  case A_RGB: launch_tiles<A_RGB>(grid, s, a, t); break;
-  case A_BGR: launch_tiles<A_BGR>(grid, s, a, t); break;
-  default: launch_tiles<A_RGBP>(grid, s, a, t); break;
-  }
+  with_tile_format(fmt, [&](auto f) { launch_tiles<f>(grid, s, a, t); });
   VALI_LAUNCH_CHECK();
   return VALI_OK;
 }

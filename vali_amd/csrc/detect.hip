@@ -559,18 +559,8 @@ WsLayout ws_layout(int n, int k, int T) {
 bool dims_ok(int n, int k, int T) { return n >= 1 && n <= kMaxN && k >= 1 && k <= kMaxK && T >= 1 && T <= kMaxT; }
 
 int check_tensor(const char* who, const vali_detect_tensor& t, const char* name) {
-  if (!t.data)
-    return fail(VALI_ERR_INVALID_ARG, "%s: %s has a null pointer", who, name);
-  if (t.dtype != VALI_DTYPE_F32 && t.dtype != VALI_DTYPE_F16 && t.dtype != VALI_DTYPE_BF16)
-    return fail(VALI_ERR_INVALID_ARG, "%s: %s: dtype %d is not float32, float16 or bfloat16", who, name, t.dtype);
-  const int es = t.dtype == VALI_DTYPE_F32 ? 4 : 2;
-  if (((uintptr_t)t.data & (uintptr_t)(es - 1)) != 0)
-    return fail(VALI_ERR_INVALID_ARG, "%s: %s is not aligned to its element size", who, name);
-  const int64_t lim = (int64_t)1 << 40;
-  if (t.stride_n < 0 || t.stride_k < 0 || t.stride_c < 0 || t.stride_n > lim || t.stride_k > lim || t.stride_c > lim)
-    return fail(VALI_ERR_INVALID_ARG, "%s: %s: strides (%lld, %lld, %lld) outside 0..2^40", who, name,
-                (long long)t.stride_n, (long long)t.stride_k, (long long)t.stride_c);
-  return VALI_OK;
+  const int64_t strides[3] = {t.stride_n, t.stride_k, t.stride_c};
+  return check_head_tensor(who, name, t.data, t.dtype, strides, 3);
 }
 
 template <int DT>
@@ -655,11 +645,7 @@ int vali_detect_select(const vali_detect_in* in, const vali_detect_params* param
 
   hipStream_t s = as_stream(stream);
   VALI_ENTRY(s);
-  switch (a.scores.dtype) {
-  case VALI_DTYPE_F32: launch_score<VALI_DTYPE_F32>(a, s); break;
-  case VALI_DTYPE_F16: launch_score<VALI_DTYPE_F16>(a, s); break;
-  default: launch_score<VALI_DTYPE_BF16>(a, s); break;
-  }
+  with_float_dtype(a.scores.dtype, [&](auto dt) { launch_score<dt>(a, s); });
   VALI_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_det_select, dim3(a.n), dim3(1024), 0, s, a);
   VALI_LAUNCH_CHECK();

@@ -1644,26 +1644,15 @@ int vali_jpeg_encode_tensor(const vali_tensor_src* src, const float scale[3], co
                             const vali_jpeg_params* params, void* workspace, size_t ws_bytes, uint8_t* d_out,
                             size_t out_stride, uint32_t* d_sizes, vali_stream_t stream) {
   VALI_REQUIRE(src && scale && offset && params && workspace && d_out && d_sizes, "null argument");
-  VALI_REQUIRE(src->data, "null tensor data");
-  VALI_REQUIRE(src->dtype >= VALI_DTYPE_F32 && src->dtype <= VALI_DTYPE_U8,
-               "dtype must be VALI_DTYPE_F32, _F16, _BF16 or _U8");
-  VALI_REQUIRE(src->packed == 0 || src->packed == 1, "packed must be 0 or 1");
-  VALI_REQUIRE(src->n >= 1 && src->n <= 65535, "batch size out of range (1..65535)");
-  VALI_REQUIRE(src->width >= 1 && src->height >= 1 && src->width <= 65535 && src->height <= 65535,
-               "size outside 1..65535");
-  VALI_REQUIRE(src->stride_n > 0 && src->stride_y > 0 && (src->packed || src->stride_c > 0),
-               "strides must be positive");
-  VALI_REQUIRE(src->stride_y >= (int64_t)src->width * (src->packed ? 3 : 1), "stride_y is shorter than a row");
-  const uintptr_t esize = src->dtype == VALI_DTYPE_F32 ? 4 : src->dtype == VALI_DTYPE_U8 ? 1 : 2;
-  VALI_REQUIRE(((uintptr_t)src->data & (esize - 1)) == 0, "data is not aligned to its element");
-  for (int c = 0; c < 3; ++c)
-    VALI_REQUIRE(std::isfinite(scale[c]) && std::isfinite(offset[c]), "scale and offset must be finite");
+  int rc = check_tensor_src(__func__, src, scale, offset);
+  if (rc != VALI_OK)
+    return rc;
   // the channels are colours, or Y, Cb, Cr as they are: a tensor has no subsampled planes
   if (!jpeg_is_rgb(params->format) && params->format != VALI_FMT_YUV444)
     return fail(VALI_ERR_UNSUPPORTED, "%s: format %d cannot name the channels of a tensor", __func__, params->format);
   const int n = src->n;
   JpegGeom g;
-  int rc = jpeg_geom(__func__, n, src->width, src->height, params, &g);
+  rc = jpeg_geom(__func__, n, src->width, src->height, params, &g);
   if (rc != VALI_OK)
     return rc;
   JpegLaunch l;
@@ -1679,20 +1668,7 @@ int vali_jpeg_encode_tensor(const vali_tensor_src* src, const float scale[3], co
 
   hipStream_t s = as_stream(stream);
   VALI_ENTRY(s);
-  switch (src->dtype) {
-  case VALI_DTYPE_F32:
-    launch_fdct_tensor<VALI_DTYPE_F32>(packed, yuv, l.cs, l.fgrid, s, l.f, ta);
-    break;
-  case VALI_DTYPE_F16:
-    launch_fdct_tensor<VALI_DTYPE_F16>(packed, yuv, l.cs, l.fgrid, s, l.f, ta);
-    break;
-  case VALI_DTYPE_BF16:
-    launch_fdct_tensor<VALI_DTYPE_BF16>(packed, yuv, l.cs, l.fgrid, s, l.f, ta);
-    break;
-  default:
-    launch_fdct_tensor<VALI_DTYPE_U8>(packed, yuv, l.cs, l.fgrid, s, l.f, ta);
-    break;
-  }
+  with_src_dtype(src->dtype, [&](auto dt) { launch_fdct_tensor<dt>(packed, yuv, l.cs, l.fgrid, s, l.f, ta); });
   VALI_LAUNCH_CHECK();
   return jpeg_launch_rest(__func__, n, l, d_sizes, s);
 }

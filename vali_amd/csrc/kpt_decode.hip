@@ -265,13 +265,6 @@ __global__ void __launch_bounds__(kBlock) k_kpt_decode_simcc(const DecArgs a) {
   finish(a, map, r, frame, ix, iy, 0.0f, 0.0f, a.Wh, a.Hh, by < bx ? by : bx);
 }
 
-bool strides_ok(const int64_t* s, int n) {
-  for (int i = 0; i < n; ++i)
-    if (s[i] < 0 || s[i] > ((int64_t)1 << 40))
-      return false;
-  return true;
-}
-
 // the pieces a row of w elements of es bytes can meet: one more when a row may begin off the 16-byte grid
 int pieces(int w, int es, bool on_grid) { return (w * es + 15) / 16 + (on_grid ? 0 : 1); }
 
@@ -302,7 +295,8 @@ int vali_kpt_decode(const vali_surface* d_frames, int n, const vali_kpt_decode_i
   const bool simcc = in->heat == nullptr;
   VALI_REQUIRE(!simcc || (in->simcc_x && in->simcc_y), "neither heat nor both of simcc_x and simcc_y");
   VALI_REQUIRE(simcc || (!in->simcc_x && !in->simcc_y), "heat and SimCC vectors at once");
-  if (in->dtype != VALI_DTYPE_F32 && in->dtype != VALI_DTYPE_F16 && in->dtype != VALI_DTYPE_BF16)
+  // one dtype for the heatmaps or the two SimCC vectors: tensor_in.hpp's predicates under this entry point's own words
+  if (!float_dtype(in->dtype))
     return fail(VALI_ERR_INVALID_ARG, "%s: dtype %d is not float32, float16 or bfloat16", __func__, in->dtype);
   VALI_REQUIRE(in->m >= 1 && in->m <= kMaxM, "m outside 1..65535");
   VALI_REQUIRE(in->p >= 1 && in->p <= kMaxP, "p outside 1..64");
@@ -318,7 +312,7 @@ int vali_kpt_decode(const vali_surface* d_frames, int n, const vali_kpt_decode_i
     VALI_REQUIRE(in->max_det >= 1 && in->max_det <= kMaxD, "max_det outside 1..1024");
     VALI_REQUIRE((long long)n * in->max_det == in->m, "m is not n * max_det");
   }
-  const int es = in->dtype == VALI_DTYPE_F32 ? 4 : 2;
+  const int es = float_dtype_size(in->dtype);
   const uintptr_t emask = (uintptr_t)(es - 1);
   const int64_t hs[3] = {in->stride_m, in->stride_p, in->stride_y};
   const int64_t vs[4] = {in->x_stride_m, in->x_stride_p, in->y_stride_m, in->y_stride_p};
@@ -355,11 +349,7 @@ int vali_kpt_decode(const vali_surface* d_frames, int n, const vali_kpt_decode_i
 
   hipStream_t s = as_stream(stream);
   VALI_ENTRY(s);
-  switch (in->dtype) {
-  case VALI_DTYPE_F32: launch_dt<VALI_DTYPE_F32>(a, simcc, s); break;
-  case VALI_DTYPE_F16: launch_dt<VALI_DTYPE_F16>(a, simcc, s); break;
-  default: launch_dt<VALI_DTYPE_BF16>(a, simcc, s); break;
-  }
+  with_float_dtype(in->dtype, [&](auto dt) { launch_dt<dt>(a, simcc, s); });
   VALI_LAUNCH_CHECK();
   return VALI_OK;
 }

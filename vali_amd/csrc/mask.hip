@@ -249,26 +249,6 @@ bool dims_ok(int n, int D, int hp, int wp) {
          wp <= kMaxP;
 }
 
-int check_tensor(const char* who, const char* name, const void* data, int dtype, int64_t s0, int64_t s1, int64_t s2) {
-  if (!data)
-    return fail(VALI_ERR_INVALID_ARG, "%s: %s has a null pointer", who, name);
-  if (dtype != VALI_DTYPE_F32 && dtype != VALI_DTYPE_F16 && dtype != VALI_DTYPE_BF16)
-    return fail(VALI_ERR_INVALID_ARG, "%s: %s: dtype %d is not float32, float16 or bfloat16", who, name, dtype);
-  const int es = dtype == VALI_DTYPE_F32 ? 4 : 2;
-  if (((uintptr_t)data & (uintptr_t)(es - 1)) != 0)
-    return fail(VALI_ERR_INVALID_ARG, "%s: %s is not aligned to its element size", who, name);
-  const int64_t lim = (int64_t)1 << 40;
-  if (s0 < 0 || s1 < 0 || s2 < 0 || s0 > lim || s1 > lim || s2 > lim)
-    return fail(VALI_ERR_INVALID_ARG, "%s: %s: strides (%lld, %lld, %lld) outside 0..2^40", who, name, (long long)s0,
-                (long long)s1, (long long)s2);
-  return VALI_OK;
-}
-
-template <int FMT>
-void launch_paint(const dim3& grid, hipStream_t s, const MaskArgs& a) {
-  hipLaunchKernelGGL((k_mask_paint<FMT>), grid, dim3(kBlock), 0, s, a);
-}
-
 } // namespace
 } // namespace vali
 
@@ -294,12 +274,12 @@ int vali_mask_paint(const vali_surface* frames, const vali_surface* d_frames, in
   VALI_REQUIRE((long long)n * in->max_det <= 65535, "n * max_det exceeds 65535");
   VALI_REQUIRE(in->net_w >= 1 && in->net_w <= 65535 && in->net_h >= 1 && in->net_h <= 65535,
                "net_w or net_h outside 1..65535");
-  int rc = check_tensor(__func__, "protos", in->protos.data, in->protos.dtype, in->protos.stride_n, in->protos.stride_m,
-                        in->protos.stride_y);
+  const int64_t ps[3] = {in->protos.stride_n, in->protos.stride_m, in->protos.stride_y};
+  const int64_t cs[3] = {in->coeffs.stride_n, in->coeffs.stride_k, in->coeffs.stride_c};
+  int rc = check_head_tensor(__func__, "protos", in->protos.data, in->protos.dtype, ps, 3);
   if (rc != VALI_OK)
     return rc;
-  rc = check_tensor(__func__, "coeffs", in->coeffs.data, in->coeffs.dtype, in->coeffs.stride_n, in->coeffs.stride_k,
-                    in->coeffs.stride_c);
+  rc = check_head_tensor(__func__, "coeffs", in->coeffs.data, in->coeffs.dtype, cs, 3);
   if (rc != VALI_OK)
     return rc;
   VALI_REQUIRE(n_colours >= 1, "n_colours below 1");
@@ -333,21 +313,10 @@ int vali_mask_paint(const vali_surface* frames, const vali_surface* d_frames, in
   hipStream_t s = as_stream(stream);
   VALI_ENTRY(s);
   const dim3 lgrid(((a.Wp + kLogW - 1) / kLogW) * ((a.Hp + kLogH - 1) / kLogH), n * a.D);
-  switch (a.pdt) {
-  case VALI_DTYPE_F32: hipLaunchKernelGGL(k_mask_logits<VALI_DTYPE_F32>, lgrid, dim3(kBlock), 0, s, a); break;
-  case VALI_DTYPE_F16: hipLaunchKernelGGL(k_mask_logits<VALI_DTYPE_F16>, lgrid, dim3(kBlock), 0, s, a); break;
-  default: hipLaunchKernelGGL(k_mask_logits<VALI_DTYPE_BF16>, lgrid, dim3(kBlock), 0, s, a); break;
-  }
+  with_float_dtype(a.pdt, [&](auto dt) { hipLaunchKernelGGL(k_mask_logits<dt>, lgrid, dim3(kBlock), 0, s, a); });
   VALI_LAUNCH_CHECK();
   const dim3 grid(tiles, n);
-  switch (fmt) {
-  case A_NV12: launch_paint<A_NV12>(grid, s, a); break;
-  case A_YUV420: launch_paint<A_YUV420>(grid, s, a); break;
-  case A_YUV444: launch_paint<A_YUV444>(grid, s, a); break;
-  case A_RGB: launch_paint<A_RGB>(grid, s, a); break;
-  case A_BGR: launch_paint<A_BGR>(grid, s, a); break;
-  default: launch_paint<A_RGBP>(grid, s, a); break;
-  }
+  with_tile_format(fmt, [&](auto f) { hipLaunchKernelGGL(k_mask_paint<f>, grid, dim3(kBlock), 0, s, a); });
   VALI_LAUNCH_CHECK();
   return VALI_OK;
 }

@@ -448,9 +448,8 @@ bool dims_ok(int n, int D, int p) {
   return n >= 1 && n <= kMaxN && D >= 1 && D <= kMaxD && (long long)n * D <= 65535 && p >= 1 && p <= kMaxP;
 }
 
-template <int FMT>
-void launch_paint(const dim3& grid, hipStream_t s, const PoseArgs& a) {
-  hipLaunchKernelGGL((k_pose_paint<FMT>), grid, dim3(kBlock), 0, s, a);
+void launch_paint(int fmt, const dim3& grid, hipStream_t s, const PoseArgs& a) {
+  with_tile_format(fmt, [&](auto f) { hipLaunchKernelGGL(k_pose_paint<f>, grid, dim3(kBlock), 0, s, a); });
 }
 
 } // namespace
@@ -478,18 +477,10 @@ int vali_pose_paint(const vali_surface* frames, const vali_surface* d_frames, in
   VALI_REQUIRE((long long)n * in->max_det <= 65535, "n * max_det exceeds 65535");
   VALI_REQUIRE(in->n_limbs >= 0 && in->n_limbs <= kMaxL, "n_limbs outside 0..128");
   VALI_REQUIRE(in->d_limbs || in->n_limbs == 0, "limbs has a null pointer");
-  VALI_REQUIRE(in->kpts, "kpts has a null pointer");
-  if (in->dtype != VALI_DTYPE_F32 && in->dtype != VALI_DTYPE_F16 && in->dtype != VALI_DTYPE_BF16)
-    return fail(VALI_ERR_INVALID_ARG, "%s: kpts: dtype %d is not float32, float16 or bfloat16", __func__, in->dtype);
-  VALI_REQUIRE(((uintptr_t)in->kpts & (uintptr_t)(in->dtype == VALI_DTYPE_F32 ? 3 : 1)) == 0,
-               "kpts is not aligned to its element size");
-  {
-    const int64_t lim = (int64_t)1 << 40, s[4] = {in->stride_n, in->stride_k, in->stride_p, in->stride_c};
-    for (int i = 0; i < 4; ++i)
-      if (s[i] < 0 || s[i] > lim)
-        return fail(VALI_ERR_INVALID_ARG, "%s: kpts: strides (%lld, %lld, %lld, %lld) outside 0..2^40", __func__,
-                    (long long)s[0], (long long)s[1], (long long)s[2], (long long)s[3]);
-  }
+  const int64_t strides[4] = {in->stride_n, in->stride_k, in->stride_p, in->stride_c};
+  int rc = check_head_tensor(__func__, "kpts", in->kpts, in->dtype, strides, 4);
+  if (rc != VALI_OK)
+    return rc;
   VALI_REQUIRE(style->d_limb_colours && style->d_joint_colours, "limb_colours or joint_colours has a null pointer");
   VALI_REQUIRE(style->n_limb_colours >= 1 && style->n_joint_colours >= 1, "n_limb_colours or n_joint_colours below 1");
   VALI_REQUIRE(style->kpt_thr == style->kpt_thr, "kpt_thr is a NaN");
@@ -501,7 +492,7 @@ int vali_pose_paint(const vali_surface* frames, const vali_surface* d_frames, in
                "dets, rects, limbs or colours are not 4-byte aligned");
   VALI_REQUIRE(((uintptr_t)d_points & 15u) == 0, "points is not 16-byte aligned");
   int tiles = 0;
-  int rc = check_frames(__func__, n, frames, format, &tiles);
+  rc = check_frames(__func__, n, frames, format, &tiles);
   if (rc != VALI_OK)
     return rc;
   const int fmt = tile_format(format);
@@ -531,21 +522,9 @@ int vali_pose_paint(const vali_surface* frames, const vali_surface* d_frames, in
   hipStream_t s = as_stream(stream);
   VALI_ENTRY(s);
   const dim3 pgrid((unsigned)((rows + kWavesPerBlock - 1) / kWavesPerBlock));
-  switch (a.dt) {
-  case VALI_DTYPE_F32: hipLaunchKernelGGL(k_pose_points<VALI_DTYPE_F32>, pgrid, dim3(kBlock), 0, s, a); break;
-  case VALI_DTYPE_F16: hipLaunchKernelGGL(k_pose_points<VALI_DTYPE_F16>, pgrid, dim3(kBlock), 0, s, a); break;
-  default: hipLaunchKernelGGL(k_pose_points<VALI_DTYPE_BF16>, pgrid, dim3(kBlock), 0, s, a); break;
-  }
+  with_float_dtype(a.dt, [&](auto dt) { hipLaunchKernelGGL(k_pose_points<dt>, pgrid, dim3(kBlock), 0, s, a); });
   VALI_LAUNCH_CHECK();
-  const dim3 grid(tiles, n);
-  switch (fmt) {
-  case A_NV12: launch_paint<A_NV12>(grid, s, a); break;
-  case A_YUV420: launch_paint<A_YUV420>(grid, s, a); break;
-  case A_YUV444: launch_paint<A_YUV444>(grid, s, a); break;
-  case A_RGB: launch_paint<A_RGB>(grid, s, a); break;
-  case A_BGR: launch_paint<A_BGR>(grid, s, a); break;
-  default: launch_paint<A_RGBP>(grid, s, a); break;
-  }
+  launch_paint(fmt, dim3(tiles, n), s, a);
   VALI_LAUNCH_CHECK();
   return VALI_OK;
 }
@@ -600,15 +579,7 @@ int vali_pose_paint_points(const vali_surface* frames, const vali_surface* d_fra
   VALI_ENTRY(s);
   hipLaunchKernelGGL(k_pose_boxes, dim3((unsigned)((rows + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, s, b);
   VALI_LAUNCH_CHECK();
-  const dim3 grid(tiles, n);
-  switch (fmt) {
-  case A_NV12: launch_paint<A_NV12>(grid, s, a); break;
-  case A_YUV420: launch_paint<A_YUV420>(grid, s, a); break;
-  case A_YUV444: launch_paint<A_YUV444>(grid, s, a); break;
-  case A_RGB: launch_paint<A_RGB>(grid, s, a); break;
-  case A_BGR: launch_paint<A_BGR>(grid, s, a); break;
-  default: launch_paint<A_RGBP>(grid, s, a); break;
-  }
+  launch_paint(fmt, dim3(tiles, n), s, a);
   VALI_LAUNCH_CHECK();
   return VALI_OK;
 }

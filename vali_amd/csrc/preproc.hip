@@ -29,6 +29,7 @@
 // numpy arithmetic (tests/test_gpu_preproc.py, tests/test_oracle_preproc.py).
 #include "common.hpp"
 #include "dev_util.hpp"
+#include "tensor_out.hpp"
 
 namespace vali {
 
@@ -350,39 +351,6 @@ struct RoiArgs {
 // construction.
 enum : int { TD_SURF = 0, TD_F32 = 1, TD_F16 = 2, TD_BF16 = 3 };
 
-// float32 -> float16 bits, IEEE round-to-nearest-even in integers: independent of the wave's denormal mode (subnormal
-// results are kept), magnitudes of 65520 and more give +-inf, NaN gives a quiet NaN.  torch.Tensor.to(torch.float16).
-__device__ __forceinline__ u32 f32_to_f16_bits(float v) {
-  const u32 x = __builtin_bit_cast(u32, v);
-  const u32 sign = (x >> 16) & 0x8000u, a = x & 0x7fffffffu;
-  if (a > 0x7f800000u)
-    return sign | 0x7e00u;
-  if (a >= 0x477ff000u) // 65520 = the tie between 65504 and 2^16, and everything above it
-    return sign | 0x7c00u;
-  if (a >= 0x38800000u) { // 2^-14 and more: a normal half; the carry of the rounding walks into the exponent
-    const u32 r = a - 0x38000000u;
-    return sign | ((r + 0xfffu + ((r >> 13) & 1u)) >> 13);
-  }
-  const u32 e = a >> 23;
-  if (e < 102u) // below 2^-25: under half of the smallest subnormal (2^-25 itself is the tie with 0, handled below)
-    return sign;
-  // subnormal half: m * 2^(e - 150) in units of 2^-24 = m >> (126 - e), remainder rounded half to even
-  const u32 m = (a & 0x7fffffu) | 0x800000u, sh = 126u - e; // sh = 14..24
-  u32 q = m >> sh;
-  const u32 rem = m & ((1u << sh) - 1u), half = 1u << (sh - 1u);
-  if (rem > half || (rem == half && (q & 1u)))
-    ++q;
-  return sign | q;
-}
-
-// float32 -> bfloat16 bits, round-to-nearest-even (torch.Tensor.to(torch.bfloat16)); NaN gives a quiet NaN
-__device__ __forceinline__ u32 f32_to_bf16_bits(float v) {
-  const u32 x = __builtin_bit_cast(u32, v);
-  if ((x & 0x7fffffffu) > 0x7f800000u)
-    return (x >> 16) | 0x40u;
-  return (x + 0x7fffu + ((x >> 16) & 1u)) >> 16;
-}
-
 // a table entry / an output element of the form DST: the float itself, or the finished 16 bits
 template <int DST> struct TdElem {
   typedef float lut_t;
@@ -399,19 +367,6 @@ template <> struct TdElem<TD_BF16> {
   typedef u32 val_t;
   static __device__ __forceinline__ u32 make(float v) { return f32_to_bf16_bits(v); }
 };
-
-// item `frame` of the batch tensor as the planes of a surface: addresses in 64 bits, the pitch in bytes (the host has
-// checked that it and height x pitch fit the 32-bit in-plane offset)
-template <int ESIZE> __device__ __forceinline__ SurfRef tensor_ref(const vali_tensor_dst& t, u32 frame) {
-  SurfRef r;
-  uint8_t* base = (uint8_t*)t.data + (long long)frame * t.stride_n * ESIZE;
-  r.p[0] = base;
-  r.p[1] = base + (t.packed ? 0 : t.stride_c * ESIZE);
-  r.p[2] = base + (t.packed ? 0 : 2 * t.stride_c * ESIZE);
-  r.pitch[0] = r.pitch[1] = r.pitch[2] = (int)(t.stride_y * ESIZE);
-  r.width = t.width; r.height = t.height;
-  return r;
-}
 
 // the 16-bit stores of one lane and row: 4 elements of a plane (8 bytes) / its 4 channels-last pixels (24 bytes) as
 // 8-byte stores when the lane has all 4 pixels and the address is 8-byte aligned, single elements under wr[] otherwise
@@ -442,30 +397,6 @@ __device__ __forceinline__ void store_h4_packed(uint8_t* q, const u32 (&o)[3][4]
   }
 }
 
-// step 3 of the definition for (channel c, u8 value q): the operations of k_nv12_preproc's table
-__device__ __forceinline__ float preproc_step3(int q, int c, const vali_preproc_params& prm) {
-  const float f = (float)q / 255.0f;
-  const float g = f / prm.div;
-  return (g - prm.mean[c]) / prm.std_[c];
-}
-
-// Item-uniform records of the batch form (descriptor, rectangle) read through the constant address space: the index is
-// uniform, so they are scalar loads into SGPRs (through generic pointers they would be flat vector loads)
-#define VALI_CONST __attribute__((address_space(4)))
-template <typename T> __device__ __forceinline__ T load_uniform(const T* arr, const T& one, u32 index) {
-  static_assert(sizeof(T) % 4 == 0, "records of whole dwords");
-  if (!arr)
-    return one;
-  const VALI_CONST u32* q = (const VALI_CONST u32*)(arr + index);
-  u32 w[sizeof(T) / 4];
-#pragma unroll
-  for (unsigned i = 0; i < sizeof(T) / 4; ++i)
-    w[i] = q[i];
-  T v;
-  __builtin_memcpy(&v, w, sizeof(T));
-  return v;
-}
-
 __device__ __forceinline__ SurfRef surf_ref(const vali_surface& v) {
   SurfRef r;
   r.p[0] = (uint8_t*)v.plane[0]; r.p[1] = (uint8_t*)v.plane[1]; r.p[2] = (uint8_t*)v.plane[2];
@@ -492,13 +423,13 @@ __global__ void __launch_bounds__(kBlock) k_nv12_preproc_roi(const RoiArgs a) {
   u32 tile_x, tile_y, frame;
   if (!tile_of_block(a.map, tile_x, tile_y, frame))
     return;
-  const SurfRef s = surf_ref(load_uniform(a.d_src, a.src, frame));
+  const SurfRef s = surf_ref(load_uniform(a.d_src, frame, &a.src));
   SurfRef d;
   if constexpr (DST == TD_SURF)
-    d = surf_ref(load_uniform(a.d_dst, a.dst, frame));
+    d = surf_ref(load_uniform(a.d_dst, frame, &a.dst));
   else
     d = tensor_ref<kHalf ? 2 : 4>(a.tdst, frame);
-  const vali_roi r = load_uniform(a.d_roi, a.roi, frame);
+  const vali_roi r = load_uniform(a.d_roi, frame, &a.roi);
   int sx = r.src_x, sy = r.src_y, sw = r.src_w, sh = r.src_h;
   int dx = r.dst_x, dy = r.dst_y, dw = r.dst_w, dh = r.dst_h;
   if constexpr (DST != TD_SURF) {
@@ -524,7 +455,7 @@ __global__ void __launch_bounds__(kBlock) k_nv12_preproc_roi(const RoiArgs a) {
   if constexpr (kFloat) {
     if (hits) {
       for (int e = threadIdx.x; e < 3 * 256; e += kBlock)
-        lut[e >> 8][e & 255] = Elem::make(preproc_step3(e & 255, e >> 8, a.prm));
+        lut[e >> 8][e & 255] = Elem::make(normalise_u8(e & 255, e >> 8, a.prm));
       __syncthreads();
     }
   }
@@ -544,7 +475,7 @@ __global__ void __launch_bounds__(kBlock) k_nv12_preproc_roi(const RoiArgs a) {
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const int q = (a.pad_rgb >> (8 * c)) & 255u;
-    const auto v = kFloat ? Elem::make(preproc_step3(q, c, a.prm)) : Elem::make((float)q);
+    const auto v = kFloat ? Elem::make(normalise_u8(q, c, a.prm)) : Elem::make((float)q);
     pv[c] = __builtin_bit_cast(typename Elem::val_t, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); // uniform: SGPRs
   }
 
@@ -843,13 +774,13 @@ __global__ void __launch_bounds__(kBlock) k_rgb_preproc_roi(const RgbRoiArgs ar)
   u32 tile_x, tile_y, frame;
   if (!tile_of_block(a.map, tile_x, tile_y, frame))
     return;
-  const SurfRef s = surf_ref(load_uniform(a.d_src, a.src, frame));
+  const SurfRef s = surf_ref(load_uniform(a.d_src, frame, &a.src));
   SurfRef d;
   if constexpr (DST == TD_SURF)
-    d = surf_ref(load_uniform(a.d_dst, a.dst, frame));
+    d = surf_ref(load_uniform(a.d_dst, frame, &a.dst));
   else
     d = tensor_ref<kHalf ? 2 : 4>(a.tdst, frame);
-  const vali_roi r = load_uniform(a.d_roi, a.roi, frame);
+  const vali_roi r = load_uniform(a.d_roi, frame, &a.roi);
   int sx = r.src_x, sy = r.src_y, sw = r.src_w, sh = r.src_h;
   int dx = r.dst_x, dy = r.dst_y, dw = r.dst_w, dh = r.dst_h;
   if (ar.whole) {
@@ -874,7 +805,7 @@ __global__ void __launch_bounds__(kBlock) k_rgb_preproc_roi(const RgbRoiArgs ar)
   if constexpr (kFloat) {
     if (hits) {
       for (int e = threadIdx.x; e < 3 * 256; e += kBlock)
-        lut[e >> 8][e & 255] = Elem::make(preproc_step3(e & 255, e >> 8, a.prm));
+        lut[e >> 8][e & 255] = Elem::make(normalise_u8(e & 255, e >> 8, a.prm));
       __syncthreads();
     }
   }
@@ -897,7 +828,7 @@ __global__ void __launch_bounds__(kBlock) k_rgb_preproc_roi(const RgbRoiArgs ar)
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     padq[c] = (a.pad_rgb >> (8 * c)) & 255u;
-    const auto v = Elem::make(kFloat ? preproc_step3((int)padq[c], c, a.prm) : 0.0f);
+    const auto v = Elem::make(kFloat ? normalise_u8((int)padq[c], c, a.prm) : 0.0f);
     pv[c] = __builtin_bit_cast(typename Elem::val_t, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); // uniform: SGPRs
   }
 
@@ -1259,8 +1190,7 @@ int vali_nv12_preproc_roi(const vali_surface* src, const vali_surface* dst, cons
   a.roi = *roi;
   a.prm = *params;
   a.pad = pad != 0;
-  if (pad)
-    a.pad_rgb = (u32)pad_rgb[0] | (u32)pad_rgb[1] << 8 | (u32)pad_rgb[2] << 16;
+  a.pad_rgb = pad_colour(pad, pad_rgb);
   hipStream_t s = as_stream(stream);
   VALI_ENTRY(s);
   return launch_preproc_roi(a, dst->width, dst->height, dst->format, 1, s);
@@ -1281,8 +1211,7 @@ int vali_nv12_preproc_roi_batch(const vali_surface* d_src, const vali_surface* d
   a.d_roi = d_roi;
   a.prm = *params;
   a.pad = pad != 0;
-  if (pad)
-    a.pad_rgb = (u32)pad_rgb[0] | (u32)pad_rgb[1] << 8 | (u32)pad_rgb[2] << 16;
+  a.pad_rgb = pad_colour(pad, pad_rgb);
   hipStream_t s = as_stream(stream);
   VALI_ENTRY(s);
   return launch_preproc_roi(a, dst_width, dst_height, dst_format, n, s);
@@ -1320,8 +1249,7 @@ int vali_rgb_preproc_roi(const vali_surface* src, const vali_surface* dst, const
   a.roi = *roi;
   a.prm = *params;
   a.pad = pad != 0;
-  if (pad)
-    a.pad_rgb = (u32)pad_rgb[0] | (u32)pad_rgb[1] << 8 | (u32)pad_rgb[2] << 16;
+  a.pad_rgb = pad_colour(pad, pad_rgb);
   hipStream_t s = as_stream(stream);
   VALI_ENTRY(s);
   return launch_rgb_preproc_roi(ar, src->format, dst->width, dst->height, dst->format, 1, s);
@@ -1350,38 +1278,10 @@ int vali_rgb_preproc_roi_batch(const vali_surface* d_src, const vali_surface* d_
   ar.whole = d_roi == nullptr;
   a.prm = *params;
   a.pad = pad != 0;
-  if (pad)
-    a.pad_rgb = (u32)pad_rgb[0] | (u32)pad_rgb[1] << 8 | (u32)pad_rgb[2] << 16;
+  a.pad_rgb = pad_colour(pad, pad_rgb);
   hipStream_t s = as_stream(stream);
   VALI_ENTRY(s);
   return launch_rgb_preproc_roi(ar, src_format, dst_width, dst_height, dst_format, n, s);
-}
-
-// the checks the two tensor entry points share, all on the host
-static int tensor_dst_check(const char* who, const vali_tensor_dst* t, bool even) {
-#define VALI_T_REQUIRE(cond, msg)                                              \
-  do {                                                                         \
-    if (!(cond))                                                               \
-      return fail(VALI_ERR_INVALID_ARG, "%s: %s", who, msg);                   \
-  } while (0)
-  VALI_T_REQUIRE(t->data, "null tensor data");
-  VALI_T_REQUIRE(t->dtype >= VALI_DTYPE_F32 && t->dtype <= VALI_DTYPE_BF16, "dtype must be VALI_DTYPE_F32, _F16 or _BF16");
-  VALI_T_REQUIRE(t->packed == 0 || t->packed == 1, "packed must be 0 or 1");
-  VALI_T_REQUIRE(t->n >= 1 && t->n <= 65535, "batch size out of range (1..65535)");
-  if (even)
-    VALI_T_REQUIRE(t->width >= 2 && t->height >= 2 && ((t->width | t->height) & 1) == 0, "bad geometry");
-  else
-    VALI_T_REQUIRE(t->width >= 1 && t->height >= 1, "bad geometry");
-  VALI_T_REQUIRE(t->stride_n > 0 && t->stride_y > 0 && (t->packed || t->stride_c > 0), "strides must be positive");
-  VALI_T_REQUIRE(t->stride_y >= (int64_t)t->width * (t->packed ? 3 : 1), "stride_y is shorter than a row");
-  const int64_t esize = t->dtype == VALI_DTYPE_F32 ? 4 : 2;
-  VALI_T_REQUIRE(((uintptr_t)t->data & (uintptr_t)(esize - 1)) == 0, "data is not aligned to its element");
-  // the kernels address a row as (u32)(y * pitch) inside its plane
-  VALI_T_REQUIRE(t->stride_y <= (int64_t)0x7fffffff / esize &&
-                     (uint64_t)t->height * (uint64_t)(t->stride_y * esize) < (1ull << 32),
-                 "row pitch of 2 GiB or plane of 4 GiB or more");
-#undef VALI_T_REQUIRE
-  return VALI_OK;
 }
 
 static void tensor_dst_args(RoiArgs& a, const vali_surface* d_src, const vali_roi* d_roi, const vali_tensor_dst* dst,
@@ -1392,8 +1292,7 @@ static void tensor_dst_args(RoiArgs& a, const vali_surface* d_src, const vali_ro
   a.tdst = *dst;
   a.prm = *params;
   a.pad = pad != 0;
-  if (pad)
-    a.pad_rgb = (u32)pad_rgb[0] | (u32)pad_rgb[1] << 8 | (u32)pad_rgb[2] << 16;
+  a.pad_rgb = pad_colour(pad, pad_rgb);
 }
 
 int vali_nv12_preproc_roi_tensor(const vali_surface* d_src, const vali_roi* d_roi, const vali_tensor_dst* dst,
@@ -1401,7 +1300,7 @@ int vali_nv12_preproc_roi_tensor(const vali_surface* d_src, const vali_roi* d_ro
                                  vali_stream_t stream) {
   VALI_REQUIRE(d_src && dst && params, "null argument");
   VALI_REQUIRE(!pad || pad_rgb, "null pad colour");
-  if (const int rc = tensor_dst_check(__func__, dst, true))
+  if (const int rc = check_tensor_dst(__func__, dst, true))
     return rc;
   RoiArgs a = {};
   tensor_dst_args(a, d_src, d_roi, dst, params, pad, pad_rgb);
@@ -1418,7 +1317,7 @@ int vali_rgb_preproc_roi_tensor(const vali_surface* d_src, const vali_roi* d_roi
   VALI_REQUIRE(!pad || pad_rgb, "null pad colour");
   if (!rgb_src_ok(src_format))
     return fail(VALI_ERR_UNSUPPORTED, "rgb_preproc_roi_tensor: sources must be RGB, BGR or RGB_PLANAR (got %d)", src_format);
-  if (const int rc = tensor_dst_check(__func__, dst, false))
+  if (const int rc = check_tensor_dst(__func__, dst, false))
     return rc;
   RgbRoiArgs ar = {};
   tensor_dst_args(ar.r, d_src, d_roi, dst, params, pad, pad_rgb);

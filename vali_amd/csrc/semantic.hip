@@ -330,11 +330,7 @@ __global__ void __launch_bounds__(kBlock, 4) k_semantic_paint(const SemArgs a) {
 
 template <int FMT>
 void launch_semantic(const dim3& grid, hipStream_t s, const SemArgs& a, int dtype) {
-  switch (dtype) {
-  case VALI_DTYPE_F32: hipLaunchKernelGGL((k_semantic_paint<FMT, VALI_DTYPE_F32>), grid, dim3(kBlock), 0, s, a); break;
-  case VALI_DTYPE_F16: hipLaunchKernelGGL((k_semantic_paint<FMT, VALI_DTYPE_F16>), grid, dim3(kBlock), 0, s, a); break;
-  default: hipLaunchKernelGGL((k_semantic_paint<FMT, VALI_DTYPE_BF16>), grid, dim3(kBlock), 0, s, a); break;
-  }
+  with_float_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((k_semantic_paint<FMT, dt>), grid, dim3(kBlock), 0, s, a); });
 }
 
 } // namespace
@@ -357,20 +353,15 @@ int vali_semantic_paint(const vali_surface* frames, const vali_surface* d_frames
   VALI_REQUIRE(in->net_w >= 1 && in->net_w <= 65535 && in->net_h >= 1 && in->net_h <= 65535,
                "net_w or net_h outside 1..65535");
   const vali_mask_tensor& t = in->logits;
-  VALI_REQUIRE(t.data, "logits has a null pointer");
-  if (t.dtype != VALI_DTYPE_F32 && t.dtype != VALI_DTYPE_F16 && t.dtype != VALI_DTYPE_BF16)
-    return fail(VALI_ERR_INVALID_ARG, "%s: logits: dtype %d is not float32, float16 or bfloat16", __func__, t.dtype);
-  VALI_REQUIRE(((uintptr_t)t.data & (uintptr_t)(t.dtype == VALI_DTYPE_F32 ? 3 : 1)) == 0,
-               "logits is not aligned to its element size");
-  const int64_t lim = (int64_t)1 << 40;
-  if (t.stride_n < 0 || t.stride_m < 0 || t.stride_y < 0 || t.stride_n > lim || t.stride_m > lim || t.stride_y > lim)
-    return fail(VALI_ERR_INVALID_ARG, "%s: logits: strides (%lld, %lld, %lld) outside 0..2^40", __func__,
-                (long long)t.stride_n, (long long)t.stride_m, (long long)t.stride_y);
+  const int64_t strides[3] = {t.stride_n, t.stride_m, t.stride_y};
+  int rc = check_head_tensor(__func__, "logits", t.data, t.dtype, strides, 3);
+  if (rc != VALI_OK)
+    return rc;
   VALI_REQUIRE(!d_colours || n_colours >= 1, "n_colours below 1");
   VALI_REQUIRE(alpha >= -1 && alpha <= 255, "alpha outside -1..255");
   VALI_REQUIRE((((uintptr_t)d_rects | (uintptr_t)d_colours) & 3u) == 0, "rects or colours are not 4-byte aligned");
   int tiles = 0;
-  int rc = check_frames(__func__, n, frames, format, &tiles);
+  rc = check_frames(__func__, n, frames, format, &tiles);
   if (rc != VALI_OK)
     return rc;
   const int fmt = tile_format(format);
@@ -401,14 +392,7 @@ int vali_semantic_paint(const vali_surface* frames, const vali_surface* d_frames
   hipStream_t s = as_stream(stream);
   VALI_ENTRY(s);
   const dim3 grid(tiles, n);
-  switch (fmt) {
-  case A_NV12: launch_semantic<A_NV12>(grid, s, a, t.dtype); break;
-  case A_YUV420: launch_semantic<A_YUV420>(grid, s, a, t.dtype); break;
-  case A_YUV444: launch_semantic<A_YUV444>(grid, s, a, t.dtype); break;
-  case A_RGB: launch_semantic<A_RGB>(grid, s, a, t.dtype); break;
-  case A_BGR: launch_semantic<A_BGR>(grid, s, a, t.dtype); break;
-  default: launch_semantic<A_RGBP>(grid, s, a, t.dtype); break;
-  }
+  with_tile_format(fmt, [&](auto f) { launch_semantic<f>(grid, s, a, t.dtype); });
   VALI_LAUNCH_CHECK();
   return VALI_OK;
 }

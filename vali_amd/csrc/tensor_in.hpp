@@ -1,17 +1,100 @@
-// What the kernels that READ one (N, 3, H, W) batch tensor share (vali_jpeg_encode_tensor, vali_tensor_to_surfaces):
-// the element types, the row loaders and the quantiser of the definition in include/vali_hip.h.  One copy, so the two
-// entry points cannot drift apart; tests/test_jpeg_tensor_host.py and tests/test_gpu_jpeg_tensor.py pin it.
+// What the kernels that READ a tensor share.  For one (N, 3, H, W) batch tensor (vali_jpeg_encode_tensor,
+// vali_tensor_to_surfaces): the element types, the row loaders and the quantiser of the definition in include/vali_hip.h,
+// and the host rules of a vali_tensor_src.  For the heads of a network, whose strides are free (vali_detect_select,
+// vali_mask_paint, vali_semantic_paint, vali_pose_paint, vali_warp_fit, vali_kpt_decode): the element types and the host
+// rule of such a tensor.  For both: the step from a run-time dtype to a kernel of that element type.  One copy, so the
+// entry points cannot drift apart; tests/test_tensor_rules_host.py, tests/test_jpeg_tensor_host.py and
+// tests/test_gpu_jpeg_tensor.py pin it.  The tensors that are WRITTEN have tensor_out.hpp.
+// The host rules live here and not in a header of their own: every file that includes this one has common.hpp already.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <type_traits>
 
 #include "../../include/vali_hip.h"
+#include "common.hpp"
 
 namespace vali {
 namespace {
 
 typedef uint32_t u32;
 typedef uint8_t u8;
+
+// ---- the host --------------------------------------------------------------------------------------------------------------
+// A run-time dtype as a compile-time constant: f(std::integral_constant<int, DT>()) for the DT that `dtype` names, so a
+// generic lambda launches the kernel of that element type.  The caller has checked the dtype; the last case takes the rest.
+template <typename F> void with_float_dtype(int dtype, F&& f) {
+  switch (dtype) {
+  case VALI_DTYPE_F32: f(std::integral_constant<int, VALI_DTYPE_F32>()); break;
+  case VALI_DTYPE_F16: f(std::integral_constant<int, VALI_DTYPE_F16>()); break;
+  default: f(std::integral_constant<int, VALI_DTYPE_BF16>()); break;
+  }
+}
+// ... and uint8, for the entry points that read a vali_tensor_src
+template <typename F> void with_src_dtype(int dtype, F&& f) {
+  if (dtype >= VALI_DTYPE_F32 && dtype <= VALI_DTYPE_BF16)
+    with_float_dtype(dtype, f);
+  else
+    f(std::integral_constant<int, VALI_DTYPE_U8>());
+}
+
+// the predicates of a head tensor: a float dtype, its element size, strides in 0..2^40
+inline bool float_dtype(int dtype) { return dtype == VALI_DTYPE_F32 || dtype == VALI_DTYPE_F16 || dtype == VALI_DTYPE_BF16; }
+inline int float_dtype_size(int dtype) { return dtype == VALI_DTYPE_F32 ? 4 : 2; }
+inline bool strides_ok(const int64_t* s, int n) {
+  for (int i = 0; i < n; ++i)
+    if (s[i] < 0 || s[i] > ((int64_t)1 << 40))
+      return false;
+  return true;
+}
+
+// The rule of a head tensor `name` of `count` (at most 4) strides, for the entry point `who`: a pointer, a float dtype,
+// alignment to the element, strides in 0..2^40.
+int check_head_tensor(const char* who, const char* name, const void* data, int dtype, const int64_t* strides, int count) {
+  if (!data)
+    return fail(VALI_ERR_INVALID_ARG, "%s: %s has a null pointer", who, name);
+  if (!float_dtype(dtype))
+    return fail(VALI_ERR_INVALID_ARG, "%s: %s: dtype %d is not float32, float16 or bfloat16", who, name, dtype);
+  if (((uintptr_t)data & (uintptr_t)(float_dtype_size(dtype) - 1)) != 0)
+    return fail(VALI_ERR_INVALID_ARG, "%s: %s is not aligned to its element size", who, name);
+  if (!strides_ok(strides, count)) {
+    char list[4 * 24];
+    int at = 0;
+    for (int i = 0; i < count && i < 4; ++i)
+      at += snprintf(list + at, sizeof(list) - at, i ? ", %lld" : "%lld", (long long)strides[i]);
+    return fail(VALI_ERR_INVALID_ARG, "%s: %s: strides (%s) outside 0..2^40", who, name, list);
+  }
+  return VALI_OK;
+}
+
+// The rules of a vali_tensor_src and of the scale and offset that go with it, for the entry point `who`.
+int check_tensor_src(const char* who, const vali_tensor_src* src, const float scale[3], const float offset[3]) {
+#define VALI_T_REQUIRE(cond, msg)                                              \
+  do {                                                                         \
+    if (!(cond))                                                               \
+      return fail(VALI_ERR_INVALID_ARG, "%s: %s", who, msg);                   \
+  } while (0)
+  VALI_T_REQUIRE(src->data, "null tensor data");
+  VALI_T_REQUIRE(src->dtype >= VALI_DTYPE_F32 && src->dtype <= VALI_DTYPE_U8,
+                 "dtype must be VALI_DTYPE_F32, _F16, _BF16 or _U8");
+  VALI_T_REQUIRE(src->packed == 0 || src->packed == 1, "packed must be 0 or 1");
+  VALI_T_REQUIRE(src->n >= 1 && src->n <= 65535, "batch size out of range (1..65535)");
+  VALI_T_REQUIRE(src->width >= 1 && src->height >= 1 && src->width <= 65535 && src->height <= 65535,
+                 "size outside 1..65535");
+  VALI_T_REQUIRE(src->stride_n > 0 && src->stride_y > 0 && (src->packed || src->stride_c > 0),
+                 "strides must be positive");
+  VALI_T_REQUIRE(src->stride_y >= (int64_t)src->width * (src->packed ? 3 : 1), "stride_y is shorter than a row");
+  const uintptr_t esize = src->dtype == VALI_DTYPE_F32 ? 4 : src->dtype == VALI_DTYPE_U8 ? 1 : 2;
+  VALI_T_REQUIRE(((uintptr_t)src->data & (esize - 1)) == 0, "data is not aligned to its element");
+  for (int c = 0; c < 3; ++c)
+    VALI_T_REQUIRE(isfinite(scale[c]) && isfinite(offset[c]), "scale and offset must be finite");
+#undef VALI_T_REQUIRE
+  return VALI_OK;
+}
+
+// ---- the device ------------------------------------------------------------------------------------------------------------
 
 // One (N, 3, H, W) tensor (vali_jpeg_encode_tensor): elements are quantised in registers on their way in.
 struct TensorArgs {

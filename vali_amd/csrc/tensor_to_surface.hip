@@ -395,21 +395,8 @@ int vali_tensor_to_surfaces(const vali_tensor_src* src, const float scale[3], co
                 dst_format);
   }
   VALI_REQUIRE(params || !d_isyuv(dst), "a YUV destination needs params (rgb2yuv)");
-  // the tensor: the rules of vali_jpeg_encode_tensor
-  VALI_REQUIRE(src->data, "null tensor data");
-  VALI_REQUIRE(src->dtype >= VALI_DTYPE_F32 && src->dtype <= VALI_DTYPE_U8,
-               "dtype must be VALI_DTYPE_F32, _F16, _BF16 or _U8");
-  VALI_REQUIRE(src->packed == 0 || src->packed == 1, "packed must be 0 or 1");
-  VALI_REQUIRE(src->n >= 1 && src->n <= 65535, "batch size out of range (1..65535)");
-  VALI_REQUIRE(src->width >= 1 && src->height >= 1 && src->width <= 65535 && src->height <= 65535,
-               "size outside 1..65535");
-  VALI_REQUIRE(src->stride_n > 0 && src->stride_y > 0 && (src->packed || src->stride_c > 0),
-               "strides must be positive");
-  VALI_REQUIRE(src->stride_y >= (int64_t)src->width * (src->packed ? 3 : 1), "stride_y is shorter than a row");
-  const uintptr_t esize = src->dtype == VALI_DTYPE_F32 ? 4 : src->dtype == VALI_DTYPE_U8 ? 1 : 2;
-  VALI_REQUIRE(((uintptr_t)src->data & (esize - 1)) == 0, "data is not aligned to its element");
-  for (int c = 0; c < 3; ++c)
-    VALI_REQUIRE(std::isfinite(scale[c]) && std::isfinite(offset[c]), "scale and offset must be finite");
+  if (const int rc = check_tensor_src(__func__, src, scale, offset))
+    return rc;
   VALI_REQUIRE(bgr == 0 || bgr == 1, "bgr must be 0 or 1");
   VALI_REQUIRE(!d_is420(dst) || ((src->width | src->height) & 1) == 0,
                "4:2:0 destinations (NV12, YUV420) need even width and height");
@@ -437,20 +424,7 @@ int vali_tensor_to_surfaces(const vali_tensor_src* src, const float scale[3], co
 
   hipStream_t s = as_stream(stream);
   VALI_ENTRY(s);
-  switch (src->dtype) {
-  case VALI_DTYPE_F32:
-    launch_t2s<VALI_DTYPE_F32>(packed, dst, grid, block, s, a);
-    break;
-  case VALI_DTYPE_F16:
-    launch_t2s<VALI_DTYPE_F16>(packed, dst, grid, block, s, a);
-    break;
-  case VALI_DTYPE_BF16:
-    launch_t2s<VALI_DTYPE_BF16>(packed, dst, grid, block, s, a);
-    break;
-  default:
-    launch_t2s<VALI_DTYPE_U8>(packed, dst, grid, block, s, a);
-    break;
-  }
+  with_src_dtype(src->dtype, [&](auto dt) { launch_t2s<dt>(packed, dst, grid, block, s, a); });
   VALI_LAUNCH_CHECK();
   return VALI_OK;
 }

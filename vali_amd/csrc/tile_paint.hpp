@@ -208,6 +208,19 @@ int tile_format(int format) {
   }
 }
 
+// A run-time TileFmt as a compile-time constant: f(std::integral_constant<int, FMT>()), so a generic lambda launches the
+// painter of that format.  The caller has checked the format; the last case takes the rest.
+template <typename F> void with_tile_format(int fmt, F&& f) {
+  switch (fmt) {
+  case A_NV12: f(std::integral_constant<int, A_NV12>()); break;
+  case A_YUV420: f(std::integral_constant<int, A_YUV420>()); break;
+  case A_YUV444: f(std::integral_constant<int, A_YUV444>()); break;
+  case A_RGB: f(std::integral_constant<int, A_RGB>()); break;
+  case A_BGR: f(std::integral_constant<int, A_BGR>()); break;
+  default: f(std::integral_constant<int, A_RGBP>()); break;
+  }
+}
+
 // the rules for the frames of a batch; *max_tiles: the tiles of the largest one
 int check_frames(const char* who, int n, const vali_surface* frames, int format, int* max_tiles) {
   const int fmt = tile_format(format);

@@ -18,13 +18,14 @@
 //                               the vector cache and L2: neighbouring lanes read neighbouring texels; nothing is staged
 //                               in LDS but the 3 x 256 table of step 5, filled once per workgroup as k_nv12_preproc_roi
 //                               fills its own, so the per-pixel path moves finished elements.
-// The float16 / bfloat16 conversions, step 5 and the checks of the tensor are private copies of preproc.hip's: that file
-// and its kernels' resource figures stay as they are.
+// The float16 / bfloat16 conversions, step 5 (normalise_u8), the scalar loads and the checks of the tensor are
+// tensor_out.hpp's, shared with preproc.hip; the check of the keypoint head is tensor_in.hpp's.
 #include <math.h>
 
 #include "det_rows.hpp"
 #include "kpt_map.hpp"
 #include "tensor_in.hpp"
+#include "tensor_out.hpp"
 
 #pragma clang fp contract(off)
 
@@ -136,37 +137,6 @@ struct WarpArgs {
   int bgr;             // SRC_PACKED: the first stored colour is blue
 };
 
-// float32 -> float16 bits, IEEE round-to-nearest-even in integers (preproc.hip's: independent of the wave's denormal
-// mode, magnitudes of 65520 and more give +-inf, NaN gives a quiet NaN)
-__device__ __forceinline__ u32 w_f16_bits(float v) {
-  const u32 x = __builtin_bit_cast(u32, v);
-  const u32 sign = (x >> 16) & 0x8000u, a = x & 0x7fffffffu;
-  if (a > 0x7f800000u)
-    return sign | 0x7e00u;
-  if (a >= 0x477ff000u)
-    return sign | 0x7c00u;
-  if (a >= 0x38800000u) {
-    const u32 r = a - 0x38000000u;
-    return sign | ((r + 0xfffu + ((r >> 13) & 1u)) >> 13);
-  }
-  const u32 e = a >> 23;
-  if (e < 102u)
-    return sign;
-  const u32 m = (a & 0x7fffffu) | 0x800000u, sh = 126u - e;
-  u32 q = m >> sh;
-  const u32 rem = m & ((1u << sh) - 1u), half = 1u << (sh - 1u);
-  if (rem > half || (rem == half && (q & 1u)))
-    ++q;
-  return sign | q;
-}
-// float32 -> bfloat16 bits, round-to-nearest-even; NaN gives a quiet NaN (preproc.hip's)
-__device__ __forceinline__ u32 w_bf16_bits(float v) {
-  const u32 x = __builtin_bit_cast(u32, v);
-  if ((x & 0x7fffffffu) > 0x7f800000u)
-    return (x >> 16) | 0x40u;
-  return (x + 0x7fffu + ((x >> 16) & 1u)) >> 16;
-}
-
 // an element of the tensor as its bits, and the table's entry
 template <int DT> struct WElem {
   typedef u32 lut_t;
@@ -176,35 +146,13 @@ template <int DT> struct WElem {
 template <> struct WElem<VALI_DTYPE_F16> {
   typedef uint16_t lut_t;
   static constexpr int ES = 2;
-  static __device__ __forceinline__ u32 make(float v) { return w_f16_bits(v); }
+  static __device__ __forceinline__ u32 make(float v) { return f32_to_f16_bits(v); }
 };
 template <> struct WElem<VALI_DTYPE_BF16> {
   typedef uint16_t lut_t;
   static constexpr int ES = 2;
-  static __device__ __forceinline__ u32 make(float v) { return w_bf16_bits(v); }
+  static __device__ __forceinline__ u32 make(float v) { return f32_to_bf16_bits(v); }
 };
-
-// step 5 for (channel c, u8 value q): step 3 of vali_nv12_preproc, operation for operation
-__device__ __forceinline__ float warp_step5(int q, int c, const vali_preproc_params& prm) {
-  const float f = (float)q / 255.0f;
-  const float g = f / prm.div;
-  return (g - prm.mean[c]) / prm.std_[c];
-}
-
-// A workgroup-uniform record of a device array through the constant address space: the index is uniform, so these are
-// scalar loads into SGPRs (preproc.hip's idiom)
-#define VALI_WARP_CONST __attribute__((address_space(4)))
-template <typename T> __device__ __forceinline__ T warp_uniform(const T* arr, u32 index) {
-  static_assert(sizeof(T) % 4 == 0, "records of whole dwords");
-  const VALI_WARP_CONST u32* q = (const VALI_WARP_CONST u32*)(arr + index);
-  u32 w[sizeof(T) / 4];
-#pragma unroll
-  for (unsigned i = 0; i < sizeof(T) / 4; ++i)
-    w[i] = q[i];
-  T v;
-  __builtin_memcpy(&v, w, sizeof(T));
-  return v;
-}
 
 // step 3 along one axis for a position s inside [0, n): g in [-0.5, n - 0.5), so floor(g) is -1 .. n - 1
 struct WTap {
@@ -280,15 +228,15 @@ __global__ void __launch_bounds__(kBlock) k_warp_sample(const WarpArgs a) {
   if (slot >= (u32)a.t.n)
     return;
   const u32 tile_y = tile / a.tiles_x, tile_x = tile - tile_y * a.tiles_x;
-  const MatRow m = warp_uniform(a.mats, slot);
+  const MatRow m = load_uniform(a.mats, slot);
   const bool skipped = m.frame < 0 || m.frame >= a.n;  // step 1
   if (skipped && !a.pad)
     return;
   vali_surface s = {};
   if (!skipped) {
-    s = warp_uniform(a.d_frames, (u32)m.frame);
+    s = load_uniform(a.d_frames, (u32)m.frame);
     for (int e = threadIdx.x; e < 3 * 256; e += kBlock)
-      lut[e >> 8][e & 255] = (typename Elem::lut_t)Elem::make(warp_step5(e & 255, e >> 8, a.prm));
+      lut[e >> 8][e & 255] = (typename Elem::lut_t)Elem::make(normalise_u8(e & 255, e >> 8, a.prm));
     __syncthreads();
   }
   const int w = a.t.width, h = a.t.height;
@@ -299,7 +247,7 @@ __global__ void __launch_bounds__(kBlock) k_warp_sample(const WarpArgs a) {
   u32 pv[3];  // the pad colour through step 5
 #pragma unroll
   for (int c = 0; c < 3; ++c)
-    pv[c] = (u32)__builtin_amdgcn_readfirstlane((int)Elem::make(warp_step5((a.pad_rgb >> (8 * c)) & 255u, c, a.prm)));
+    pv[c] = (u32)__builtin_amdgcn_readfirstlane((int)Elem::make(normalise_u8((a.pad_rgb >> (8 * c)) & 255u, c, a.prm)));
 
   // step 2 for each of the lane's pixels, from its own (x, y)
   const float v = __fadd_rn((float)y, 0.5f);
@@ -374,29 +322,6 @@ __global__ void __launch_bounds__(kBlock) k_warp_sample(const WarpArgs a) {
   }
 }
 
-// the checks of the batch tensor (vali_nv12_preproc_roi_tensor's, for a canvas of any size from 1 x 1)
-int warp_dst_check(const char* who, const vali_tensor_dst* t) {
-#define VALI_T_REQUIRE(cond, msg)                                              \
-  do {                                                                         \
-    if (!(cond))                                                               \
-      return fail(VALI_ERR_INVALID_ARG, "%s: %s", who, msg);                   \
-  } while (0)
-  VALI_T_REQUIRE(t->data, "null tensor data");
-  VALI_T_REQUIRE(t->dtype >= VALI_DTYPE_F32 && t->dtype <= VALI_DTYPE_BF16, "dtype must be VALI_DTYPE_F32, _F16 or _BF16");
-  VALI_T_REQUIRE(t->packed == 0 || t->packed == 1, "packed must be 0 or 1");
-  VALI_T_REQUIRE(t->n >= 1 && t->n <= kMaxM, "batch size out of range (1..65535)");
-  VALI_T_REQUIRE(t->width >= 1 && t->height >= 1, "bad geometry");
-  VALI_T_REQUIRE(t->stride_n > 0 && t->stride_y > 0 && (t->packed || t->stride_c > 0), "strides must be positive");
-  VALI_T_REQUIRE(t->stride_y >= (int64_t)t->width * (t->packed ? 3 : 1), "stride_y is shorter than a row");
-  const int64_t esize = t->dtype == VALI_DTYPE_F32 ? 4 : 2;
-  VALI_T_REQUIRE(((uintptr_t)t->data & (uintptr_t)(esize - 1)) == 0, "data is not aligned to its element");
-  VALI_T_REQUIRE(t->stride_y <= (int64_t)0x7fffffff / esize &&
-                     (uint64_t)t->height * (uint64_t)(t->stride_y * esize) < (1ull << 32),
-                 "row pitch of 2 GiB or plane of 4 GiB or more");
-#undef VALI_T_REQUIRE
-  return VALI_OK;
-}
-
 template <int SRC, int DT>
 void launch_sample(const dim3& grid, hipStream_t s, const WarpArgs& a) {
   if (a.t.packed)
@@ -406,11 +331,7 @@ void launch_sample(const dim3& grid, hipStream_t s, const WarpArgs& a) {
 }
 template <int SRC>
 void launch_sample_dt(const dim3& grid, hipStream_t s, const WarpArgs& a) {
-  switch (a.t.dtype) {
-  case VALI_DTYPE_F32: launch_sample<SRC, VALI_DTYPE_F32>(grid, s, a); break;
-  case VALI_DTYPE_F16: launch_sample<SRC, VALI_DTYPE_F16>(grid, s, a); break;
-  default: launch_sample<SRC, VALI_DTYPE_BF16>(grid, s, a); break;
-  }
+  with_float_dtype(a.t.dtype, [&](auto dt) { launch_sample<SRC, dt>(grid, s, a); });
 }
 
 } // namespace
@@ -431,18 +352,10 @@ int vali_warp_fit(const vali_surface* d_frames, int n, const vali_warp_fit_in* i
   VALI_REQUIRE((long long)n * in->max_det <= kMaxM, "n * max_det exceeds 65535");
   VALI_REQUIRE(in->min_points >= 2 && in->min_points <= in->p, "min_points outside 2..p");
   VALI_REQUIRE(in->kpts, "kpts has a null pointer");
-  VALI_REQUIRE(in->d_template, "template has a null pointer");
-  if (in->dtype != VALI_DTYPE_F32 && in->dtype != VALI_DTYPE_F16 && in->dtype != VALI_DTYPE_BF16)
-    return fail(VALI_ERR_INVALID_ARG, "%s: kpts: dtype %d is not float32, float16 or bfloat16", __func__, in->dtype);
-  VALI_REQUIRE(((uintptr_t)in->kpts & (uintptr_t)(in->dtype == VALI_DTYPE_F32 ? 3 : 1)) == 0,
-               "kpts is not aligned to its element size");
-  {
-    const int64_t lim = (int64_t)1 << 40, s[4] = {in->stride_n, in->stride_k, in->stride_p, in->stride_c};
-    for (int i = 0; i < 4; ++i)
-      if (s[i] < 0 || s[i] > lim)
-        return fail(VALI_ERR_INVALID_ARG, "%s: kpts: strides (%lld, %lld, %lld, %lld) outside 0..2^40", __func__,
-                    (long long)s[0], (long long)s[1], (long long)s[2], (long long)s[3]);
-  }
+  VALI_REQUIRE(in->d_template, "template has a null pointer");  // between the null kpts above and the rest of its rule
+  const int64_t strides[4] = {in->stride_n, in->stride_k, in->stride_p, in->stride_c};
+  if (const int rc = check_head_tensor(__func__, "kpts", in->kpts, in->dtype, strides, 4))
+    return rc;
   VALI_REQUIRE(in->kpt_thr == in->kpt_thr, "kpt_thr is a NaN");
   VALI_REQUIRE((((uintptr_t)d_dets | (uintptr_t)d_rects | (uintptr_t)in->d_template | (uintptr_t)d_frames) & 3u) == 0,
                "frames, dets, rects or template are not 4-byte aligned");
@@ -459,11 +372,7 @@ int vali_warp_fit(const vali_surface* d_frames, int n, const vali_warp_fit_in* i
   hipStream_t s = as_stream(stream);
   VALI_ENTRY(s);
   const dim3 grid((unsigned)((n * in->max_det + kBlock - 1) / kBlock));
-  switch (in->dtype) {
-  case VALI_DTYPE_F32: hipLaunchKernelGGL(k_warp_fit<VALI_DTYPE_F32>, grid, dim3(kBlock), 0, s, a); break;
-  case VALI_DTYPE_F16: hipLaunchKernelGGL(k_warp_fit<VALI_DTYPE_F16>, grid, dim3(kBlock), 0, s, a); break;
-  default: hipLaunchKernelGGL(k_warp_fit<VALI_DTYPE_BF16>, grid, dim3(kBlock), 0, s, a); break;
-  }
+  with_float_dtype(in->dtype, [&](auto dt) { hipLaunchKernelGGL(k_warp_fit<dt>, grid, dim3(kBlock), 0, s, a); });
   VALI_LAUNCH_CHECK();
   return VALI_OK;
 }
@@ -479,7 +388,7 @@ int vali_warp_tensor(const vali_surface* frames, const vali_surface* d_frames, i
   int unused = 0;
   if (const int rc = check_frames(__func__, n, frames, format, &unused))
     return rc;
-  if (const int rc = warp_dst_check(__func__, dst))
+  if (const int rc = check_tensor_dst(__func__, dst, false))
     return rc;
   VALI_REQUIRE((((uintptr_t)d_matrices | (uintptr_t)d_frames) & 3u) == 0, "frames or matrices are not 4-byte aligned");
   const int px = dst->dtype == VALI_DTYPE_F32 ? 4 : 2 * 4;
@@ -493,8 +402,7 @@ int vali_warp_tensor(const vali_surface* frames, const vali_surface* d_frames, i
   a.n = n;
   a.tiles_x = (u32)tiles_x, a.tiles = (u32)(tiles_x * tiles_y);
   a.pad = pad != 0;
-  if (pad)
-    a.pad_rgb = (u32)pad_rgb[0] | (u32)pad_rgb[1] << 8 | (u32)pad_rgb[2] << 16;
+  a.pad_rgb = pad_colour(pad, pad_rgb);
   a.bgr = format == VALI_FMT_BGR;
 
   hipStream_t s = as_stream(stream);
