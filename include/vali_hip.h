@@ -1019,6 +1019,79 @@ VALI_API int vali_kpt_decode(const vali_surface* d_frames, int n, const vali_kpt
                              const int32_t* d_matrices, const vali_roi* d_rois, int32_t* d_points, float* d_kpts,
                              vali_stream_t stream);
 
+/* ---- tracks: vali_detect_select's rows associated over time with tracks held in device memory ---------------
+ *
+ * The temporal step after vali_detect_select: a greedy IoU tracker with a constant-velocity prediction whose whole
+ * state is the caller's device array `tracks`.  ONE launch whatever the data, nothing allocated, nothing synchronises:
+ * the call can be captured and replayed after dets was rewritten in place.  The reference has no such task.
+ * The n = streams * frames frames of a call are `streams` independent streams of `frames` consecutive frames each: stream
+ * s owns frames s * F .. s * F + F - 1 in time order (F = frames), rows s * T .. s * T + T - 1 of tracks (T = max_tracks)
+ * and row s of clock.  frames = 1: n live cameras; streams = 1: one file decoded in batches.  With D = max_det:
+ *   dets     n * D rows of 8 int32 as vali_detect_select writes them (frame, x, y, w, h, class, score bits, k); read only.
+ *   tracks   streams * T rows of 16 int32, 16-byte aligned, read and rewritten by every call; all zero: no tracks.  A row:
+ *            id, class, x, y, w, h, vx bits, vy bits (float32, pixels per frame), hits, misses, age, score bits, k, 0, 0, 0.
+ *            A row is LIVE when id >= 1 && w >= 1 && h >= 1; any other row is free and is written back as zeros.  hits,
+ *            misses and age are read clamped to 0..2^30; values 13..15 are written as 0.
+ *   clock    streams rows of 4 int32: next_id, frames seen, 0, 0; all zero at the start.  A next_id below 1 reads as 1.
+ * Every int32 value in dets, tracks and clock is handled.  All float arithmetic is IEEE float32 with one rounding per
+ * operation, never a fused multiply-add; divisions are correctly rounded; (float) of an integer rounds to nearest;
+ * min(p, d) is d < p ? d : p and max(p, d) is d > p ? d : p, so a NaN in p stays.  For stream s, for t = 0..F-1 in this
+ * order, frame i = s * F + t:
+ *   1. predict  per live track, g = (float)(misses + 1): px = (float)x + vx * g, py likewise; its box is [px, px +
+ *               (float)w] x [py, py + (float)h], its area pa = (float)w * (float)h.
+ *   2. rows     row i * D + r is VALID when its frame value is i, w >= 1 and h >= 1; its box is [(float)x, (float)x +
+ *               (float)w] x [(float)y, (float)y + (float)h], its area da = (float)w * (float)h, its score the float32
+ *               whose bits it carries.
+ *   3. match    the valid rows in ascending r (vali_detect_select's order: score descending).  Candidates are the tracks
+ *               that were live at step 1, are not yet matched in this frame and have the row's class (any class with
+ *               class_agnostic), with iw = min(px1, dx1) - max(px0, dx0), ih likewise, iw > 0 && ih > 0, inter = iw * ih,
+ *               uni = (pa + da) - inter, iou = inter / uni and iou > iou_thr (a NaN never passes).  The greatest iou
+ *               wins, equal values go to the lowest slot.
+ *   4. update   of the matched track, with the row's values x', y', w', h': step_x = ((float)((2x' + w') - (2x + w)) *
+ *               0.5f) / g, the integer difference formed in 64 bits and converted once; vx = vx + momentum * (step_x -
+ *               vx); y likewise.  The box, class, score bits and k become the row's; hits + 1, misses = 0, age + 1,
+ *               saturating at 2^30.
+ *   5. misses   every live track that no row matched: misses + 1, age + 1 (saturating); it is freed when misses >
+ *               max_age, and when hits < min_hits (a tentative track dies on its first miss).
+ *   6. births   the valid rows that matched nothing and have score >= new_thr (a NaN never passes), in ascending r, each
+ *               take the lowest slot that is free after step 5: id = next_id, after which next_id + 1, and 1 after
+ *               2^31 - 1; hits = 1, misses = 0, age = 1, vx = vy = 0, the rest the row's.  With no free slot the row
+ *               stays untracked.  (A row below new_thr continues a track and never starts one.)
+ * After the last frame clock[s] = next_id, frames seen + F (wrapping as a 32-bit integer), 0, 0.
+ * Outputs, int32 device arrays, every row rewritten by every call:
+ *   tracked  n * D rows of 8: row i * D + r is frame, x, y, w, h, id, score bits, k -- the dets row with its track's id
+ *            where the class was -- when the row was matched or born and its track now has hits >= min_hits; every other
+ *            row is -1, 0, 0, 0, 0, 0, 0, 0.  It goes wherever dets goes.
+ *   assoc    NULL or n * D rows of 4: id, slot (0..T-1), hits, class of the track the row was matched to or started
+ *            (tentative ones too); 0, -1, 0, 0 for every other row.
+ *   marks    NULL or R * n * D vali_mark rows, R = 3 with label_rects and 1 without, R * n * D <= VALI_MAX_MARKS: the
+ *            rows vali_detect_select writes, taken from the tracked row, with colours[id % n_colours] as the colour and
+ *            label_rects[id % n_labels] as the label; the rows of an unused tracked row are all zero.
+ * One call with F frames per stream equals F calls with one frame each on the same tracks and clock, bit for bit.
+ * Limits: streams 1..1024, frames >= 1, n <= 1024, max_det 1..1024, n * max_det <= 65535, max_tracks 1..256.
+ * VALI_ERR_INVALID_ARG, before any device is touched: null params or io; null dets, tracks, clock or tracked; a limit
+ * above broken; tracks not 16-byte aligned, any other array not 4-byte aligned; an iou_thr or new_thr that is not finite,
+ * a momentum outside 0..1, min_hits < 1, max_age outside 0..2^20; marks without colours (or n_colours < 1), with more
+ * than 4096 rows, a thickness below 1, a label_alpha outside 0..255 or label_rects with n_labels < 1.
+ */
+typedef struct vali_track_params {
+  int32_t streams, frames;               /* S and F; n = S * F */
+  int32_t max_det, max_tracks;           /* D and T */
+  float iou_thr, new_thr, momentum;
+  int32_t min_hits, max_age, class_agnostic;
+  int32_t thickness, label_alpha, text_colour, n_colours, n_labels;  /* marks */
+  int32_t reserved;
+} vali_track_params;                     /* 64 bytes */
+typedef struct vali_track_io {
+  const int32_t* dets;                   /* device memory throughout */
+  int32_t *tracks, *clock;               /* the state */
+  int32_t *tracked, *assoc, *marks;      /* assoc and marks may be NULL */
+  const int32_t* colours;                /* n_colours packed colours (marks) */
+  const int32_t* label_rects;            /* n_labels rows u, v, w, h, or NULL (marks) */
+} vali_track_io;                         /* 64 bytes */
+
+VALI_API int vali_track_update(const vali_track_params* params, const vali_track_io* io, vali_stream_t stream);
+
 /*
  * Rectangles of surfaces of ANY sizes as files, in one fixed set of launches.  Item i is rectangle rois[i] of the
  * surface d_src[i] (the same surface may stand behind any number of items); its file is byte for byte the file of

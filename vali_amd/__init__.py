@@ -23,6 +23,7 @@ if not _BUILDING:
                         PySurfaceResizer, PySurfaceRotator, PySurfaceUD, RoiBatch, SurfaceBatch, TensorBatch,
                         letterbox_rect, pack_colour, pack_uv, render_labels)
     from .detect import DetectionStyle, PyDetectionSelector, SelectBatch
+    from .track import PyDetectionTracker, TrackBatch
     from .mask import MaskBatch, PyInstanceMasker
     from .pose import COCO_SKELETON, PointsBatch, PoseBatch, PyPoseDrawer
     from .keypoints import KeypointBatch, PyKeypointDecoder

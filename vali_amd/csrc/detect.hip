@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "common.hpp"
+#include "mark_rows.hpp"
 #include "tensor_in.hpp"
 
 #pragma clang fp contract(off)
@@ -47,9 +48,8 @@ struct DetArgs {
 };
 
 struct DetOut {
-  int32_t *dets, *counts, *rois, *marks;
-  const int32_t *colours, *label_rects;
-  int n_colours, n_labels, thickness, label_alpha, text_colour;
+  int32_t *dets, *counts, *rois;
+  MarkStyle ms;  // marks: mark_rows.hpp
   int crop[4];
 };
 
@@ -407,10 +407,6 @@ __global__ __launch_bounds__(256) void k_det_iou(DetArgs a) {
 }
 
 // ---- k_det_reduce --------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void put_row(int32_t* p, int v0, int v1, int v2, int v3, int v4, int v5, int v6, int v7) {
-  p[0] = v0, p[1] = v1, p[2] = v2, p[3] = v3, p[4] = v4, p[5] = v5, p[6] = v6, p[7] = v7;
-}
-
 // rows of slot `at` = f * D + r for a detection (step 6 of the definition), or the unused forms when !used
 __device__ __forceinline__ void emit(const DetArgs& a, const DetOut& o, int f, int at, bool used, const float4& b,
                                      const uint4& m, const vali_roi& rc) {
@@ -444,27 +440,8 @@ __device__ __forceinline__ void emit(const DetArgs& a, const DetOut& o, int f, i
     else
       put_row(o.rois + (size_t)at * 8, 0, 0, 0, 0, 0, 0, 0, 0);
   }
-  if (o.marks) {
-    const int colour = used ? o.colours[cls % o.n_colours] : 0;
-    if (used)
-      put_row(o.marks + (size_t)at * 8, f, x, y, w, h, VALI_MARK_BOX, o.thickness, colour);
-    else
-      put_row(o.marks + (size_t)at * 8, 0, 0, 0, 0, 0, 0, 0, 0);
-    if (o.label_rects) {
-      int32_t* bg = o.marks + ((size_t)M + at) * 8;
-      int32_t* tx = o.marks + ((size_t)2 * M + at) * 8;
-      if (used && cls < o.n_labels) {
-        const int32_t* lr = o.label_rects + (size_t)cls * 4;
-        const int u = lr[0], v = lr[1], lw = lr[2], lh = lr[3];
-        const int ly = (int)((u32)y - (u32)lh);
-        put_row(bg, f, x, ly, lw, lh, VALI_MARK_FILL, 0, (int)(((u32)colour & 0x00FFFFFFu) | ((u32)o.label_alpha << 24)));
-        put_row(tx, f, x, ly, lw, lh, VALI_MARK_STAMP, (int)((u32)u | ((u32)v << 16)), o.text_colour);
-      } else {
-        put_row(bg, 0, 0, 0, 0, 0, 0, 0, 0);
-        put_row(tx, 0, 0, 0, 0, 0, 0, 0, 0);
-      }
-    }
-  }
+  if (o.ms.marks)
+    put_marks(o.ms, M, at, used, f, x, y, w, h, used ? cls % o.ms.n_colours : 0, cls < o.ms.n_labels ? cls : -1);
 }
 
 __device__ __forceinline__ u64 lane_u64(u64 v, int l) {
@@ -636,10 +613,9 @@ int vali_detect_select(const vali_detect_in* in, const vali_detect_params* param
   a.sbox = (float4*)(ws + l.sbox), a.smeta = (uint4*)(ws + l.smeta), a.mask = (u64*)(ws + l.mask);
   a.KS = l.KS, a.W = l.W;
   DetOut o = {};
-  o.dets = out->dets, o.counts = out->counts, o.rois = out->rois, o.marks = out->marks;
-  o.colours = out->colours, o.label_rects = out->label_rects;
-  o.n_colours = params->n_colours, o.n_labels = params->n_labels, o.thickness = params->thickness;
-  o.label_alpha = params->label_alpha, o.text_colour = params->text_colour;
+  o.dets = out->dets, o.counts = out->counts, o.rois = out->rois;
+  o.ms = {out->marks, out->colours, out->label_rects, params->n_colours, params->n_labels, params->thickness,
+          params->label_alpha, params->text_colour};
   for (int i = 0; i < 4; ++i)
     o.crop[i] = params->crop[i];
 

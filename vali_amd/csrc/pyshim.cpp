@@ -772,6 +772,28 @@ PYBIND11_MODULE(_vali_shim, m) {
           return vali_detect_select(&in, &p, (const vali_roi*)P(d_rects), &o, P(workspace), ws_bytes, P(stream));
         });
 
+  // tracks: dims = (streams, frames per stream, max_det, max_tracks); everything else as in the header
+  m.def("track_update",
+        [](const std::array<int, 4>& dims, float iou_thr, float new_thr, float momentum, int min_hits, int max_age,
+           int class_agnostic, int thickness, int label_alpha, int text_colour, int n_colours, int n_labels,
+           uintptr_t dets, uintptr_t tracks, uintptr_t clock, uintptr_t tracked, uintptr_t assoc, uintptr_t marks,
+           uintptr_t colours, uintptr_t label_rects, uintptr_t stream) {
+          vali_track_params p;
+          std::memset(&p, 0, sizeof(p));
+          p.streams = dims[0]; p.frames = dims[1]; p.max_det = dims[2]; p.max_tracks = dims[3];
+          p.iou_thr = iou_thr; p.new_thr = new_thr; p.momentum = momentum;
+          p.min_hits = min_hits; p.max_age = max_age; p.class_agnostic = class_agnostic;
+          p.thickness = thickness; p.label_alpha = label_alpha; p.text_colour = text_colour;
+          p.n_colours = n_colours; p.n_labels = n_labels;
+          vali_track_io io;
+          io.dets = (const int32_t*)P(dets);
+          io.tracks = (int32_t*)P(tracks); io.clock = (int32_t*)P(clock);
+          io.tracked = (int32_t*)P(tracked); io.assoc = (int32_t*)P(assoc); io.marks = (int32_t*)P(marks);
+          io.colours = (const int32_t*)P(colours); io.label_rects = (const int32_t*)P(label_rects);
+          py::gil_scoped_release nogil;
+          return vali_track_update(&p, &io, P(stream));
+        });
+
   // instance masks: protos = (ptr, dtype, stride_n, stride_m, stride_y), coeffs = (ptr, dtype, stride_n, stride_k,
   // stride_m); descs = the host copy of the descriptors in d_frames; everything else as in the header
   m.def("mask_workspace_size", [](int n, int max_det, int hp, int wp) {
